@@ -3,7 +3,7 @@
 the ~1M-triangle height field (BASELINE.json configs[2], "C3"), plus the roofline of the
 dominant kernel and the reference CPU path timed on this box's host cores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python bench.py --workload c5        (photon mapping alone, tools/bench_ppm.py)
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
@@ -22,6 +22,15 @@ report t1 / (N * tN), and the line carries a weak-scaling measurement (one whole
 rank per step) as an extra key.  At N = 1 the line predicts the split's efficiency for N = 2,
 4, 8 from every rank's work timed on this GPU (C3 and C4) and carries the C5 photon-mapping
 benchmark (tools/bench_ppm.py) as a `c5` sub-object.
+
+A plain run does only what `value` needs: it loads the scene, picks its render streams,
+preconditions, warms up, times exactly `--steps` steps (`ms_per_step` = that wall time over the
+steps), writes the last step's frames with `--dump-outputs DIR`, and prints the line.  Everything
+else described above and below — the roofline and the other per-kernel figures, the CPU baseline
+and the drop-in timing, the one-frame / cold-frame / host-buffer rates, the one-GPU scaling
+prediction (C3 and C4), the C5 sub-benchmark, and at N > 1 t1 and the weak-scaling measurement
+— runs only with `--full`; without it those keys of the line are null or absent.  (At N > 1 and
+in the rehearsals rank 0 still checks the assembled frame bit for bit: `--no-verify`.)
 
 Printed by rank 0: ONE JSON line (see the contract in the task statement).
 """
@@ -57,11 +66,31 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def scene_dir() -> str:
+    """Where the generated benchmark scenes are kept: $CENG795_SCENE_DIR, else scenes/ beside
+    this file, else (a checkout this user cannot write to) a per-user directory under the
+    system's temporary directory."""
+    import tempfile
+    d = os.environ.get("CENG795_SCENE_DIR")
+    if d:
+        os.makedirs(d, exist_ok=True)
+        return d
+    d = os.path.join(ROOT, "scenes")
+    try:
+        os.makedirs(d, exist_ok=True)
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    except OSError:
+        pass
+    d = os.path.join(tempfile.gettempdir(), f"ceng795_scenes_{os.getuid()}")
+    os.makedirs(d, mode=0o700, exist_ok=True)
+    return d
+
+
 def scene_path(workload: str, cameras: int) -> str:
     import gen_scene as G
     n, w, h, _ = WORKLOADS[workload]
-    d = os.environ.get("CENG795_SCENE_DIR", os.path.join(ROOT, "scenes"))
-    os.makedirs(d, exist_ok=True)
+    d = scene_dir()
     path = os.path.join(d, f"bench_{workload}_{cameras}cam.xml")
     if not os.path.exists(path):
         spec = G.heightfield_scene(n, w, h, name=f"{workload}.png", cameras=cameras)
@@ -187,6 +216,40 @@ def stream_copy_gbps(device) -> float:
     del x, y
     torch.cuda.empty_cache()
     return gbps
+
+
+# --dump-outputs: at most this many bytes of .npy data in all
+DUMP_BUDGET = 64 * 1000 * 1000
+
+
+def dump_outputs(directory: str, arrays: dict, seed: int = 795) -> dict:
+    """Write what the timed path computed in its last step: every array of `arrays` as
+    `directory/<name>.npy` in float32.  When together they exceed DUMP_BUDGET, each is cut to its
+    share of the budget: a fixed sample of its flattened elements (sorted indices drawn without
+    replacement from default_rng(seed), so two runs with the same arguments keep the same
+    elements).  Returns {name: [elements written, elements of the whole array]}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_BUDGET - 1024 * len(arrays)  # (the .npy headers)
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, a in arrays.items():
+        keep = a
+        if total > room:
+            n = int(room * (a.nbytes / total)) // a.itemsize
+            keep = a.reshape(-1)[np.sort(rng.choice(a.size, size=n, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), keep)
+        out[name] = [int(keep.size), int(a.size)]
+    return out
+
+
+def dump_frames(directory: str, frames) -> dict:
+    """--dump-outputs of the ray-tracing workloads: the frames of the last timed step (fp32 RGB,
+    one per camera, as the renderer's caller receives them) as frame_cam<c>.npy."""
+    return dump_outputs(directory, {f"frame_cam{c}": f.detach().cpu().numpy()
+                                    for c, f in enumerate(frames)})
 
 
 def file_sha256(path: str) -> str:
@@ -941,6 +1004,16 @@ def main() -> int:
                     help="c5: comma-separated device list of the multi-device scene (e.g. 0,0 "
                          "rehearses two replicas on one GPU)")
     ap.add_argument("--traversal", default="fast", choices=["fast", "reference"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline "
+                         "and per-kernel times, CPU baseline and drop-in timing, one-frame / cold-"
+                         "frame / host-buffer rates, the one-GPU scaling prediction (C3 and C4), "
+                         "the C5 sub-benchmark; N>1: t1 and weak scaling.  The --no-* options "
+                         "below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (the frame of each "
+                         "camera; c5: the frame) as DIR/<name>.npy in float32, at most 64 MB in "
+                         "all (a fixed seeded sample of larger outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5", action="store_true",
                     help="N=1: skip the C5 (photon mapping) sub-object of the line")
@@ -998,6 +1071,12 @@ def main() -> int:
                          "(default: 6 for one GPU's whole frames, 4 for the N>1 split's "
                          "smaller per-rank launches; profiles/r05/hwq_inflight/)")
     args = ap.parse_args()
+    with_cpu = args.full and not args.no_cpu_baseline  # (only --full times the CPU)
+    # rank 0's check of the assembled frames belongs to the N>1 / rehearsal paths, which a plain
+    # one-GPU run never takes: it stays on there
+    verify = not args.no_verify
+    # one scene directory for this process, its ranks and its child processes (scene_dir)
+    os.environ["CENG795_SCENE_DIR"] = scene_dir()
     if args.workload == "c5" and (int(os.environ.get("WORLD_SIZE", "1")) > 1
                                   or args.gather_rehearsal):
         # one process per GPU (launcher, or --gpus N relaunched below): the update pass
@@ -1013,7 +1092,8 @@ def main() -> int:
         os.environ.setdefault("RANK", "0")
         os.environ.setdefault("WORLD_SIZE", "1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", device))
-        line = bench_ppm.run_dist(args.steps, args.warmup, "cuda", not args.no_verify)
+        line = bench_ppm.run_dist(args.steps, args.warmup, "cuda", verify,
+                                  dump_dir=args.dump_outputs)
         if line is not None:
             print(json.dumps(line), flush=True)
         dist.destroy_process_group()
@@ -1026,7 +1106,8 @@ def main() -> int:
         elif args.gpus > 1:
             devices = list(range(args.gpus))
         print(json.dumps(bench_ppm.run(args.steps, args.warmup,
-                                       not args.no_cpu_baseline and devices is None, devices)))
+                                       with_cpu and devices is None, devices,
+                                       dump_dir=args.dump_outputs)))
         return 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return relaunch(args.gpus)
@@ -1176,11 +1257,14 @@ def main() -> int:
     kt, launches = scene.read_kernel_times()
     render_ms = [a.elapsed_time(b) for a, b in ev] if ev else [0.0]
     scene.collect_stats()  # reset counters
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_frames(args.dump_outputs, renderer.frames)
 
     verified = None
     t1_ms = None
     if use_pg and rank == 0:
-        if not args.no_verify:
+        if verify:
             # the gathered framebuffers must equal single-GPU renders of the same cameras
             verified = True
             for c, f in enumerate(renderer.frames):
@@ -1189,7 +1273,7 @@ def main() -> int:
                 torch.cuda.synchronize()
                 verified &= bool(torch.equal(ref.view(torch.int32), f.view(torch.int32)))
             log(f"[rank 0] gathered frames bit-identical to single-GPU renders: {verified}")
-        if strong:
+        if strong and args.full:
             # t1: the same job rendered by this GPU alone, in place, as the N = 1 bench renders
             # it (its frames in flight, a picked stream set)
             one_streams, _ = dist_tiles.pick_render_streams(scene, INFLIGHT_N1, 1, device=dev)
@@ -1201,7 +1285,7 @@ def main() -> int:
             t1_ms = timed_steps(one, args.steps, 1, coll_dev) / args.steps * 1e3
             scene.collect_stats()
     weak = None
-    if world > 1 and strong and not args.no_weak:
+    if world > 1 and strong and args.full and not args.no_weak:
         # extra: weak scaling, one whole frame per rank per step (camera 0 everywhere)
         owners = dist_tiles.FrameOwners(world, world, rank)
         c0 = scene.camera(0)
@@ -1226,7 +1310,7 @@ def main() -> int:
         value = rays_step * args.steps / elapsed / 1e6
         threads, how = host_cores()
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 # fraction of one frame's work in one launch (one rt_render_device call)
                 share = rays_local / max(1.0, rays_step / n_cams) / max(1.0, launches / args.steps)
@@ -1247,7 +1331,7 @@ def main() -> int:
                 log(f"roofline accounting failed: {e!r}")
         single = cold = None
         probe = probe_c4 = None
-        if world == 1 and not use_pg:
+        if args.full and world == 1 and not use_pg:
             try:
                 single = one_frame_ms(scene, stream, max(10, args.steps // 2))
                 cold = cold_frame_ms(scene)
@@ -1274,19 +1358,19 @@ def main() -> int:
             except Exception as e:
                 log(f"one-frame / share probe failed: {e!r}")
         host_rate = None
-        if world == 1:
+        if args.full and world == 1:
             try:
                 host_rate = host_buffer_rate(scene, rays_step / n_cams)
             except Exception as e:
                 log(f"host-buffer rate failed: {e!r}")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and with_cpu:
             try:
                 cpu = cpu_baseline(xml, threads, how)
             except Exception as e:
                 log(f"cpu baseline failed: {e!r}")
         dropin = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and with_cpu:
             try:
                 dropin = dropin_ms(xml, threads)
             except Exception as e:
@@ -1296,7 +1380,7 @@ def main() -> int:
         comm = "rccl" if coll_dev == "cuda" else "gloo"
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(ms_step, 4), "higher_is_better": True,
             # N = 1 is the base of the default N > 1 run, the tile split of one frame (strong)
             "scaling": "strong" if (strong or world == 1) else "weak",
@@ -1354,10 +1438,12 @@ def main() -> int:
                                       "efficiency_t1_over_N_tN": round(t1_ms / (world * ms_step), 4)}
         if weak is not None:
             line["weak_scaling"] = weak
-        if world == 1 and not use_pg and not args.no_c5:
+        if dumped is not None:
+            line["dumped_outputs"] = {"elements_written_of": dumped, "dtype": "float32"}
+        if args.full and world == 1 and not use_pg and not args.no_c5:
             try:
                 import bench_ppm
-                c5 = bench_ppm.run(max(3, args.steps // 4), 1, not args.no_cpu_baseline)
+                c5 = bench_ppm.run(max(3, args.steps // 4), 1, with_cpu)
                 line["c5"] = {k: c5[k] for k in ("metric", "value", "unit", "ms_per_step",
                                                  "steps", "warmup", "config", "roofline")}
                 line["c5"]["cpu_baseline"] = c5.get("cpu_baseline")

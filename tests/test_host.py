@@ -398,3 +398,59 @@ def test_bench_efficiency_check_names_every_prediction_above_one():
     assert msg.startswith("above 1.0") and "band_locality.json" in msg
     assert os.path.exists(os.path.join(os.path.dirname(bench.__file__), "profiles", "r06",
                                        "band_locality.json"))
+
+
+def test_bench_scene_dir_falls_back_when_the_checkout_is_not_writable(tmp_path, monkeypatch):
+    """bench.py keeps its generated scenes in $CENG795_SCENE_DIR, else in scenes/ of the checkout,
+    else — when that cannot be created — in a per-user directory under the temporary directory;
+    scene_path writes the scene there."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import tempfile
+    import bench
+    monkeypatch.setenv("CENG795_SCENE_DIR", str(tmp_path / "given"))
+    assert bench.scene_dir() == str(tmp_path / "given") and os.path.isdir(tmp_path / "given")
+    monkeypatch.delenv("CENG795_SCENE_DIR")
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path / "checkout"))
+    os.makedirs(tmp_path / "checkout")
+    assert bench.scene_dir() == str(tmp_path / "checkout" / "scenes")
+    # a checkout in which scenes/ cannot be made (here: its place is taken by a file)
+    blocked = tmp_path / "blocked"
+    blocked.mkdir()
+    (blocked / "scenes").write_text("")
+    monkeypatch.setattr(bench, "ROOT", str(blocked))
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))
+    os.makedirs(tmp_path / "tmp")
+    d = bench.scene_dir()
+    assert d == str(tmp_path / "tmp" / f"ceng795_scenes_{os.getuid()}") and os.path.isdir(d)
+    xml = bench.scene_path("c2", 1)
+    assert os.path.dirname(xml) == d and os.path.getsize(xml) > 0
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py's dump_outputs: arrays within the budget are written whole as float32; beyond
+    it every array is cut to its share of the budget, the same elements in every run, in order."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    rng = np.random.default_rng(3)
+    a = rng.standard_normal((37, 53, 3))
+    b = rng.standard_normal((11, 7)).astype(np.float32)
+    n = bench.dump_outputs(str(tmp_path / "whole"), {"a": a, "b": b})
+    assert n == {"a": [a.size, a.size], "b": [b.size, b.size]}
+    got = np.load(tmp_path / "whole" / "a.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "whole" / "b.npy"), b)
+    # a budget of 8 KiB + headers for 24,000 B of data: a third of each array is kept
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8192 + 2 * 1024)
+    for d in ("s1", "s2"):
+        n = bench.dump_outputs(str(tmp_path / d), {"a": a, "b": b})
+    sa, sb = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s1" / "b.npy")
+    assert n == {"a": [sa.size, a.size], "b": [sb.size, b.size]}
+    assert 8192 - 16 <= sa.nbytes + sb.nbytes <= 8192 and sb.size > 0
+    assert np.array_equal(sa, np.load(tmp_path / "s2" / "a.npy"))
+    assert np.array_equal(sb, np.load(tmp_path / "s2" / "b.npy"))
+    flat = a.astype(np.float32).reshape(-1)  # a sample of a's elements, in their order
+    pos = np.searchsorted(np.sort(flat), sa)
+    assert np.array_equal(np.sort(flat)[pos], sa)
+    order = {v: i for i, v in enumerate(flat.tolist())}
+    idx = [order[v] for v in sa.tolist()]
+    assert idx == sorted(idx) and len(set(idx)) == len(idx)

@@ -27,9 +27,9 @@ METRIC = "Mphotons/s (PPM photon pass, Cornell box, 1e7 photons)"
 
 
 def scene_path() -> str:
+    import bench
     import gen_ppm_scene as GP
-    d = os.environ.get("CENG795_SCENE_DIR", os.path.join(ROOT, "scenes"))
-    os.makedirs(d, exist_ok=True)
+    d = bench.scene_dir()
     path = os.path.join(d, "bench_c5.xml")
     if not os.path.exists(path):
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -113,10 +113,11 @@ def update_roofline(st, launches_per_step: int, ms_per_launch: float):
             "traffic_source": "profiles/traffic_c5.json" if traffic is not None else None}
 
 
-def run(steps: int, warmup: int, with_cpu: bool, devices=None) -> dict:
+def run(steps: int, warmup: int, with_cpu: bool, devices=None, dump_dir=None) -> dict:
     """devices: None = one GPU (device 0); a list = one multi-device scene over those GPUs of
     this process (ppm_scene_load_xml_multi: every pass on each, the update pass sharded by hit
-    point, the state gathered on devices[0])."""
+    point, the state gathered on devices[0]).  dump_dir: the last timed step's frame
+    is written there as frame.npy (bench.dump_outputs)."""
     import torch  # noqa: F401  (shares the HIP runtime; see ceng795_amd/_lib.py)
     from ceng795_amd import ppm
 
@@ -160,6 +161,9 @@ def run(steps: int, warmup: int, with_cpu: bool, devices=None) -> dict:
         if len(set(devices)) < len(devices):
             line["config"]["rehearsal"] = "a device is listed more than once: replicas share a GPU"
     launches = max(1, st.update_launches)  # one per photon batch (one at this size)
+    if dump_dir:
+        import bench
+        bench.dump_outputs(dump_dir, {"frame": img})
     line["roofline"] = update_roofline(st, launches, sum(upd_ms) / len(upd_ms) / launches)
     if with_cpu:
         import bench
@@ -168,7 +172,8 @@ def run(steps: int, warmup: int, with_cpu: bool, devices=None) -> dict:
     return line
 
 
-def run_dist(steps: int, warmup: int, device: str = "cuda", verify: bool = True) -> dict:
+def run_dist(steps: int, warmup: int, device: str = "cuda", verify: bool = True,
+             dump_dir=None) -> dict:
     """C5 with one process per GPU (ceng795_amd.dist_ppm): every rank traces the whole photon
     sequence and updates its shard of the hit points; rank 0 gathers the state (RCCL) and runs
     the density estimation.  Timed: whole frames (eye pass, grid, photon pass, gather, density),
@@ -196,6 +201,9 @@ def run_dist(steps: int, warmup: int, device: str = "cuda", verify: bool = True)
     dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=device)
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     ms_step = 1e3 * float(dt.item()) / steps
+    if rank == 0 and dump_dir:
+        import bench
+        bench.dump_outputs(dump_dir, {"frame": np.asarray(img)})
     verified = None
     if rank == 0 and verify:
         scene.set_update_shard(0, 1)
@@ -223,6 +231,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also time the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     a = ap.parse_args()
-    print(json.dumps(run(a.steps, a.warmup, not a.no_cpu_baseline)))
+    print(json.dumps(run(a.steps, a.warmup, a.full and not a.no_cpu_baseline)))
