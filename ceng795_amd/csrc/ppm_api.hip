@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ceng795_ppm.h"
+#include "hip_host.h"
 #include "ppm_host.h"
 #include "ppm_internal.h"
 
@@ -69,74 +70,14 @@ namespace {
 
 thread_local std::string g_error;
 
-struct HipFailure {
-  hipError_t err;
-  const char* what;
-};
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw HipFailure{e, what};
-}
 int set_error(int code, const std::string& msg) {
   g_error = msg;
   return code;
 }
 template <typename F>
 int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const HipFailure& h) {
-    return set_error(RT_E_HIP, std::string(h.what) + ": " + hipGetErrorString(h.err));
-  } catch (const std::domain_error& e) {
-    return set_error(RT_E_UNSUPPORTED, e.what());
-  } catch (const std::invalid_argument& e) {
-    return set_error(RT_E_INVALID, e.what());
-  } catch (const std::ios_base::failure& e) {
-    return set_error(RT_E_IO, e.what());
-  } catch (const std::runtime_error& e) {
-    return set_error(RT_E_PARSE, e.what());
-  } catch (const std::exception& e) {
-    return set_error(RT_E_INVALID, e.what());
-  }
+  return guarded_with(set_error, std::forward<F>(f));
 }
-
-template <typename T>
-struct DevBuf {  // grow-only device array
-  T* p = nullptr;
-  size_t cap = 0;
-  void reserve(size_t n, const char* what) {
-    if (n <= cap) return;
-    (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hip_check(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)), what);
-    cap = n;
-  }
-  void release() {
-    (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-template <typename T>
-T* upload(const std::vector<T>& v, const char* what) {
-  T* p = nullptr;
-  hip_check(hipMalloc(&p, std::max<size_t>(v.size() * sizeof(T), 16)), what);
-  if (!v.empty()) hip_check(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
-  return p;
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) hip_check(hipSetDevice(dev), "hipSetDevice");
-  }
-  ~DeviceGuard() {
-    int cur;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 // Deposit slot rows per photon batch.  Default 16 GiB: C5's 1e7 photons x 19 slots x 48 B
 // (9.1 GB) run as one batch (one sort, one update launch).  The budget actually used is also
@@ -155,10 +96,10 @@ size_t default_slot_bytes() { return size_t(16) << 30; }
 struct ppm_scene {
   HostPPM host;
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   unsigned long long seed = 0;
   PScene S{};
-  std::vector<void*> owned;  // scene arrays
+  std::vector<DevBuf<char>> owned;  // scene arrays
   // eye pass / hash grid
   int eye_cam = -1;
   int n_hp = 0;
@@ -198,7 +139,7 @@ struct ppm_scene {
   DevBuf<float> image;
   // update-kernel launches since the last collection: event pairs (reused from upd_spare),
   // completed ones beyond kMaxUpdEvents folded into upd_ms_folded / upd_folded
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> upd_events, upd_spare;
+  std::vector<std::pair<Event, Event>> upd_events, upd_spare;
   double upd_ms_folded = 0;
   long long upd_folded = 0;
   long long photons = 0;
@@ -221,7 +162,7 @@ struct ppm_scene {
   bool shard_partial = false;
 
   void drop_update_events() {  // (back to the pool)
-    upd_spare.insert(upd_spare.end(), upd_events.begin(), upd_events.end());
+    for (auto& ev : upd_events) upd_spare.push_back(std::move(ev));
     upd_events.clear();
     upd_ms_folded = 0;
     upd_folded = 0;
@@ -238,43 +179,20 @@ struct ppm_scene {
           break;
         upd_ms_folded += ms;
         upd_folded++;
-        upd_spare.push_back(upd_events[k]);
+        upd_spare.push_back(std::move(upd_events[k]));
       }
       upd_events.erase(upd_events.begin(), upd_events.begin() + (long)k);
     }
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    std::pair<Event, Event> ev;
     if (!upd_spare.empty()) {
-      ev = upd_spare.back();
+      ev = std::move(upd_spare.back());
       upd_spare.pop_back();
     } else {
-      hip_check(hipEventCreate(&ev.first), "event");
-      hip_check(hipEventCreate(&ev.second), "event");
+      ev.first.create();
+      ev.second.create();
     }
-    upd_events.push_back(ev);
-    return ev;
-  }
-  void free_all() {
-    drop_update_events();
-    for (auto& ev : upd_spare) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-    upd_spare.clear();
-    for (void* p : owned) (void)hipFree(p);
-    owned.clear();
-    hp.release(), state.release(), nupd.release(), pix_cnt.release(), pix_off.release();
-    grid.release(), bstart.release(), bend.release(), slots.release(), ndep.release();
-    owner.release(), peer_state.release(), peer_nupd.release();
-    gkeys.release(), gkeys2.release(), gidx.release(), perm.release(), gflags.release();
-    gid.release(), gstart.release(), ntile.release(), tile_off.release(), tiles.release();
-    tiles_lpt.release(), tkey.release(), tkey2.release();
-    dep_off.release(), dbucket.release(), dense.release(), dpos.release(), pcount.release(), poff.release();
-    list_start.release(), list_end.release(), pkey.release(), pval.release(), pkey2.release();
-    pval2.release(), gb.release(), gm.release(), gnb.release(), goff.release();
-    bg_start.release(), bg_end.release(), bgkey.release(), bgval.release(), bgkey2.release();
-    bgval2.release(), gpos.release(), rrtab.release();
-    cneed.release(), cofs.release(), cbuf.release();
-    temp.release(), stats.release(), error.release(), image.release();
-    wide.release(), stats_keep.release();
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
+    upd_events.push_back(std::move(ev));
+    return {upd_events.back().first, upd_events.back().second};
   }
 };
 
@@ -294,15 +212,14 @@ long long default_compact_min() { return 65536LL; }
 
 template <typename T>
 const T* own(ppm_scene* s, const std::vector<T>& v, const char* what) {
-  T* p = upload(v, what);
-  s->owned.push_back(p);
-  return p;
+  s->owned.emplace_back(upload(v, what, 0));
+  return reinterpret_cast<const T*>(s->owned.back().p);
 }
 
 void create_device(ppm_scene* s, int device) {
   s->device = device;
   DeviceGuard g(device);
-  hip_check(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "stream");
+  s->stream.create();
   const HostPPM& h = s->host;
   PScene& S = s->S;
   S.top_nodes = own(s, h.top_nodes, "upload top nodes");
@@ -811,10 +728,7 @@ int ppm_scene_load_xml(const char* xml_path, int device, ppm_scene** out) {
     create_device(s.get(), device);
     return RT_OK;
   });
-  if (rc != RT_OK) {
-    s->free_all();
-    return rc;
-  }
+  if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
 }
@@ -850,11 +764,7 @@ int ppm_scene_load_xml_multi(const char* xml_path, int device_count, const int* 
 void ppm_scene_destroy(ppm_scene* s) {
   if (!s) return;
   for (auto& p : s->peers) ppm_scene_destroy(p.release());
-  s->peers.clear();
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) (void)hipSetDevice(s->device);
-  s->free_all();
-  if (cur >= 0 && cur != s->device) (void)hipSetDevice(cur);
+  DeviceGuard g(s->device, std::nothrow);  // the scene's buffers, events and stream go with it
   delete s;
 }
 
@@ -1113,14 +1023,8 @@ int ppm_render(ppm_scene* s, int cam, int threads, float* out, ppm_stats* stats)
                                   "passes and merge the shards' states");
     DeviceGuard g(s->device);
     const PCamera& C = s->host.cameras[cam].cam;
-    hipEvent_t ev[5];
-    for (auto& e : ev) hip_check(hipEventCreate(&e), "event");
-    struct Events {
-      hipEvent_t* e;
-      ~Events() {
-        for (int k = 0; k < 5; k++) (void)hipEventDestroy(e[k]);
-      }
-    } guard{ev};
+    Event ev[5];
+    for (auto& e : ev) e.create();
     // a multi-device scene runs each pass on every replica (update pass sharded), then
     // gathers the hit-point state onto replica 0 for the density estimation
     each_replica(s, [&](ppm_scene* r) {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/ceng795_rt.h"
+#include "hip_host.h"
 #include "host_scene.h"
 #include "rt_internal.h"
 
@@ -66,34 +67,26 @@ using namespace rt;
 constexpr int kRenderChunks = RT_RENDER_CHUNKS;
 
 struct RenderCtx {
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  float* d_out = nullptr;
-  size_t out_floats = 0;
-  unsigned long long* d_cnt = nullptr;
-  rt::int2_t* d_hits = nullptr;
-  size_t hits_records = 0;
-  unsigned* d_occ = nullptr;
-  size_t occ_words = 0;
-  unsigned* d_sched = nullptr;  // per tile: traversal cost, then the shadow dispatch order
-  size_t sched_words = 0;
-  float* d_frames = nullptr;
-  size_t frames_floats = 0;
-  float* d_samples = nullptr;
-  size_t samples_floats = 0;
-  float* d_recv = nullptr;  // multi-device frames, first device: the gathered tiles
-  size_t recv_floats = 0;
-  float* d_image = nullptr;  // multi-device rt_render, first device: the row-major frame
-  size_t image_floats = 0;
-  hipEvent_t ev_in = nullptr, ev_out = nullptr;  // multi-device frames: caller-stream ordering
+  Stream stream;
+  Event e0, e1;
+  DevBuf<float> d_out;
+  DevBuf<unsigned long long> d_cnt;
+  DevBuf<rt::int2_t> d_hits;
+  DevBuf<unsigned> d_occ;
+  DevBuf<unsigned> d_sched;  // per tile: traversal cost, then the shadow dispatch order
+  DevBuf<float> d_frames;
+  DevBuf<float> d_samples;
+  DevBuf<float> d_recv;   // multi-device frames, first device: the gathered tiles
+  DevBuf<float> d_image;  // multi-device rt_render, first device: the row-major frame
+  Event ev_in, ev_out;    // multi-device frames: caller-stream ordering
   // copy-gather frames (a device listed twice): recorded on the first device's stream after it
   // has copied the shares out of the other contexts' buffers; a context renders its next share
   // only after it (the copy reads d_out / d_image on another stream: write-after-read)
-  hipEvent_t ev_gathered = nullptr;
+  Event ev_gathered;
   // rt_render's chunked copy-out (render_to_host): a second stream for the device-to-host copies
   // and one event per row chunk (created on first use)
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_chunk[kRenderChunks] = {};
+  Stream copy_stream;
+  Event ev_chunk[kRenderChunks];
 };
 
 // rt_render_device scratch of one stream (hit records, occlusion bits, tile schedule, ray-tree
@@ -102,18 +95,14 @@ struct RenderCtx {
 struct StreamScratch {
   void* stream = nullptr;
   std::mutex mu;
-  int2_t* hits = nullptr;
-  unsigned* occ = nullptr;
-  unsigned* sched = nullptr;
-  float* frames = nullptr;
-  size_t frames_capacity = 0;
-  float* samples = nullptr;
-  size_t samples_capacity = 0;
+  DevBuf<int2_t> hits;
+  DevBuf<unsigned> occ, sched;
+  DevBuf<float> frames, samples;
   // warm order: the selection whose heavy-first unit order the last frame on this stream left
   // in `sched` (valid: that frame ran the order kernel)
   std::array<long long, 7> order_key{};
   bool order_valid = false;
-  hipEvent_t done = nullptr;  // after the last frame enqueued on the stream (eviction waits on it)
+  Event done;  // after the last frame enqueued on the stream (eviction waits on it)
   unsigned long long used = 0;  // Replica::tick of the last lookup (least recently used first)
 };
 
@@ -124,9 +113,11 @@ constexpr size_t kMaxStreamTables = 64;
 
 // Per-kernel HIP-event timing of render launches (rt_set_kernel_timing): one quad of events per
 // launch of the first device.  Completed quads beyond kTimingPending are folded into `sum` so
-// the list stays bounded while timing is on and nobody reads it.
+// the list stays bounded while timing is on and nobody reads it.  `events` owns every quad's
+// events; `pending` and `spare` hold their handles.
 struct KernelTiming {
   bool on = false;
+  std::vector<Event> events;
   std::vector<std::array<hipEvent_t, 4>> pending, spare;
   double sum[4] = {0, 0, 0, 0};
   long long folded = 0;
@@ -137,19 +128,20 @@ constexpr size_t kTimingPending = 256;
 // the calls that run there.
 struct Replica {
   int device = 0;
-  DevNode* d_nodes = nullptr;
-  DevPrim* d_prims = nullptr;
-  DevLeaf* d_leaves = nullptr;
-  float* d_normals = nullptr;
-  DevAncestry* d_anc = nullptr;
-  DevMaterial* d_mats = nullptr;
-  DevLight* d_lights = nullptr;
-  unsigned long long* d_counters = nullptr;
+  DevBuf<DevNode> d_nodes;
+  DevBuf<DevPrim> d_prims;
+  DevBuf<DevLeaf> d_leaves;
+  DevBuf<float> d_normals;
+  DevBuf<DevAncestry> d_anc;
+  DevBuf<DevMaterial> d_mats;
+  DevBuf<DevLight> d_lights;
+  DevBuf<unsigned long long> d_counters;
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
-  // laid out as a stream's `sched` (estimated costs, unit order, snapshot); nullptr: none
-  std::vector<unsigned*> d_cold;
+  // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
+  std::vector<DevBuf<unsigned>> d_cold;
   std::mutex mu;  // ctx pool and stream tables
-  std::vector<RenderCtx*> ctx_free, ctx_all;
+  std::vector<std::unique_ptr<RenderCtx>> ctx_all;  // every context; the two below point into it
+  std::vector<RenderCtx*> ctx_free;
   std::vector<std::unique_ptr<StreamScratch>> streams;
   // multi-device scenes: the context each caller stream renders its shares on (one per caller
   // stream and device, kept across calls), so frames on different caller streams have their
@@ -177,6 +169,19 @@ struct rt_scene {
   std::vector<ncclComm_t> comms;
   bool multi = false;  // made by rt_scene_*_multi: frames go through render_multi (any count)
   bool copy_gather = false;
+  // the communicators go first, then the timing events and each replica's buffers, events and
+  // streams with their device current
+  ~rt_scene() {
+    for (ncclComm_t c : comms) (void)ncclCommDestroy(c);
+    if (!rep.empty()) {
+      DeviceGuard g(rep[0]->device, std::nothrow);
+      timing.events.clear();
+    }
+    for (auto& r : rep) {
+      DeviceGuard g(r->device, std::nothrow);
+      r.reset();
+    }
+  }
 };
 
 namespace {
@@ -188,140 +193,25 @@ int set_error(int code, const std::string& msg) {
   return code;
 }
 
-struct HipFailure {
-  hipError_t err;
-  const char* what;
-};
-
 struct NcclFailure {
   ncclResult_t err;
   const char* what;
 };
-
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw HipFailure{e, what};
-}
 
 void nccl_check(ncclResult_t e, const char* what) {
   if (e != ncclSuccess) throw NcclFailure{e, what};
 }
 
 template <typename F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const HipFailure& h) {
-    return set_error(RT_E_HIP, std::string(h.what) + ": " + hipGetErrorString(h.err));
-  } catch (const NcclFailure& h) {
-    return set_error(RT_E_HIP, std::string(h.what) + ": " + ncclGetErrorString(h.err));
-  } catch (const std::domain_error& e) {
-    return set_error(RT_E_UNSUPPORTED, e.what());
-  } catch (const std::invalid_argument& e) {
-    return set_error(RT_E_INVALID, e.what());
-  } catch (const std::ios_base::failure& e) {
-    return set_error(RT_E_IO, e.what());
-  } catch (const std::runtime_error& e) {
-    return set_error(RT_E_PARSE, e.what());
-  } catch (const std::bad_alloc&) {
-    return set_error(RT_E_INVALID, "out of host memory");
-  } catch (const std::exception& e) {
-    return set_error(RT_E_INVALID, e.what());
-  }
+int guarded(F&& f) {  // (the RCCL failures are this library's alone)
+  return guarded_with(set_error, [&]() -> int {
+    try {
+      return f();
+    } catch (const NcclFailure& h) {
+      return set_error(RT_E_HIP, std::string(h.what) + ": " + ncclGetErrorString(h.err));
+    }
+  });
 }
-
-template <typename T>
-T* upload(const std::vector<T>& v, const char* what) {
-  T* p = nullptr;
-  // +64 B: the kernels may fetch a record with one 64-byte scalar load past its 48 bytes
-  const size_t bytes = v.size() * sizeof(T) + 64;
-  hip_check(hipMalloc(&p, bytes), what);
-  if (!v.empty()) hip_check(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), what);
-  return p;
-}
-
-void free_ctx(RenderCtx* c) {
-  (void)hipFree(c->d_out);
-  (void)hipFree(c->d_cnt);
-  (void)hipFree(c->d_hits);
-  (void)hipFree(c->d_occ);
-  (void)hipFree(c->d_sched);
-  (void)hipFree(c->d_frames);
-  (void)hipFree(c->d_samples);
-  (void)hipFree(c->d_recv);
-  (void)hipFree(c->d_image);
-  if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-  if (c->ev_out) (void)hipEventDestroy(c->ev_out);
-  if (c->ev_gathered) (void)hipEventDestroy(c->ev_gathered);
-  if (c->e0) (void)hipEventDestroy(c->e0);
-  if (c->e1) (void)hipEventDestroy(c->e1);
-  for (hipEvent_t e : c->ev_chunk)
-    if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
-
-void free_scratch(StreamScratch& x) {
-  (void)hipFree(x.hits);
-  (void)hipFree(x.occ);
-  (void)hipFree(x.sched);
-  (void)hipFree(x.frames);
-  (void)hipFree(x.samples);
-  if (x.done) (void)hipEventDestroy(x.done);
-  x.done = nullptr;
-}
-
-void free_replica(Replica& r) {
-  int cur = 0;
-  if (hipGetDevice(&cur) == hipSuccess && cur != r.device) (void)hipSetDevice(r.device);
-  for (RenderCtx* c : r.ctx_all) free_ctx(c);
-  r.ctx_all.clear();
-  r.ctx_free.clear();
-  r.stream_ctx.clear();
-  for (auto& x : r.streams) free_scratch(*x);
-  r.streams.clear();
-  (void)hipFree(r.d_nodes);
-  (void)hipFree(r.d_prims);
-  (void)hipFree(r.d_leaves);
-  (void)hipFree(r.d_normals);
-  (void)hipFree(r.d_anc);
-  (void)hipFree(r.d_mats);
-  (void)hipFree(r.d_lights);
-  (void)hipFree(r.d_counters);
-  for (unsigned* p : r.d_cold) (void)hipFree(p);
-  r.d_cold.clear();
-  if (cur != r.device) (void)hipSetDevice(cur);
-}
-
-void free_device(rt_scene* s) {
-  for (ncclComm_t c : s->comms) (void)ncclCommDestroy(c);
-  s->comms.clear();
-  if (!s->rep.empty()) {
-    int cur = 0;
-    const int d0 = s->rep[0]->device;
-    if (hipGetDevice(&cur) == hipSuccess && cur != d0) (void)hipSetDevice(d0);
-    for (auto* v : {&s->timing.pending, &s->timing.spare})
-      for (auto& q : *v)
-        for (hipEvent_t e : q) (void)hipEventDestroy(e);
-    if (cur != d0) (void)hipSetDevice(cur);
-  }
-  s->timing.pending.clear();
-  s->timing.spare.clear();
-  for (auto& r : s->rep) free_replica(*r);
-  s->rep.clear();
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    hip_check(hipGetDevice(&prev), "hipGetDevice");
-    if (prev != dev) hip_check(hipSetDevice(dev), "hipSetDevice");
-  }
-  ~DeviceGuard() {
-    int cur;
-    if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 constexpr int kFrameFloats = 28;  // rt_kernels.hip kFrFields
 constexpr size_t kTileFloats = (size_t)kTile * kTile * 3;
@@ -461,23 +351,19 @@ void seed_cold_orders(const rt_scene* s, Replica& r) {
 #ifndef RT_COLD_SEED  // (A/B builds: 0 = cold frames in block order)
 #define RT_COLD_SEED 1
 #endif
-  r.d_cold.assign(h.cameras.size(), nullptr);
+  r.d_cold = std::vector<DevBuf<unsigned>>(h.cameras.size());
   if (!RT_COLD_SEED || s->needs_recursion || h.lights.empty()) return;  // (no warm order either)
   for (size_t cam = 0; cam < h.cameras.size(); cam++) {
     const rt_camera& c = h.cameras[cam];
     if (c.num_samples > 1) continue;
     const std::vector<unsigned> est = cold_costs(h, c);
-    unsigned* buf = nullptr;
-    hip_check(hipMalloc(&buf, sched_words_for(est.size()) * sizeof(unsigned)), "alloc cold order");
-    hip_check(hipMemcpy(buf, est.data(), est.size() * sizeof(unsigned), hipMemcpyHostToDevice),
+    DevBuf<unsigned> buf;
+    buf.reserve(sched_words_for(est.size()), "alloc cold order");
+    hip_check(hipMemcpy(buf.p, est.data(), est.size() * sizeof(unsigned), hipMemcpyHostToDevice),
               "upload tile cost estimate");
     RenderParams P = make_params(s, r, (int)cam, 0, 1, 0, 1, 0, nullptr, nullptr);
-    set_schedule(P, buf);
-    if (launch_cold_order(P, nullptr)) {
-      r.d_cold[cam] = buf;
-    } else {
-      (void)hipFree(buf);
-    }
+    set_schedule(P, buf.p);
+    if (launch_cold_order(P, nullptr)) r.d_cold[cam] = std::move(buf);
   }
   hip_check(hipDeviceSynchronize(), "cold orders");
 }
@@ -485,15 +371,17 @@ void seed_cold_orders(const rt_scene* s, Replica& r) {
 void upload_replica(const rt_scene* s, Replica& r) {
   DeviceGuard g(r.device);
   const HostScene& h = s->host;
-  r.d_nodes = upload(h.nodes, "upload nodes");
-  r.d_prims = upload(h.prims, "upload prims");
-  r.d_leaves = upload(h.leaves, "upload culling leaves");
-  r.d_normals = upload(h.normals, "upload normals");
-  r.d_anc = upload(h.ancestry, "upload ancestry");
-  r.d_mats = upload(h.materials, "upload materials");
-  r.d_lights = upload(h.lights, "upload lights");
-  hip_check(hipMalloc(&r.d_counters, sizeof(unsigned long long) * kCounterAlloc), "alloc counters");
-  hip_check(hipMemset(r.d_counters, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
+  // +64 B: the kernels may fetch a record with one 64-byte scalar load past its 48 bytes
+  constexpr size_t kPad = 64;
+  r.d_nodes = upload(h.nodes, "upload nodes", kPad);
+  r.d_prims = upload(h.prims, "upload prims", kPad);
+  r.d_leaves = upload(h.leaves, "upload culling leaves", kPad);
+  r.d_normals = upload(h.normals, "upload normals", kPad);
+  r.d_anc = upload(h.ancestry, "upload ancestry", kPad);
+  r.d_mats = upload(h.materials, "upload materials", kPad);
+  r.d_lights = upload(h.lights, "upload lights", kPad);
+  r.d_counters.reserve(kCounterAlloc, "alloc counters");
+  hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
 }
 
@@ -572,12 +460,12 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
   const rt_camera& c = h.cameras[cam];
   RenderParams P;
   std::memset(&P, 0, sizeof P);
-  P.nodes = r.d_nodes;
-  P.leaves = r.d_leaves;
-  P.prims = r.d_prims;
-  P.normals = r.d_normals;
-  P.materials = r.d_mats;
-  P.lights = r.d_lights;
+  P.nodes = r.d_nodes.p;
+  P.leaves = r.d_leaves.p;
+  P.prims = r.d_prims.p;
+  P.normals = r.d_normals.p;
+  P.materials = r.d_mats.p;
+  P.lights = r.d_lights.p;
   P.num_lights = (int)h.lights.size();
   P.max_depth = h.max_depth;
   std::memcpy(P.background, h.background, sizeof P.background);
@@ -589,7 +477,7 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
   P.accel_root = h.accel_root;
   P.quot_ok = h.quot_ok;
   std::memcpy(P.accel_box, h.accel_box, sizeof P.accel_box);
-  P.anc = r.d_anc;
+  P.anc = r.d_anc.p;
   std::memcpy(P.cam_e, c.e, 12);
   std::memcpy(P.cam_tl, c.top_left, 12);
   std::memcpy(P.cam_su, c.s_u, 12);
@@ -614,8 +502,8 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
   P.occ_words = occ_words(h);
   P.counters = counters;
   if (row0 == 0 && row_stride == 1 && tile_begin == 0 && tile_step == 1 && !P.block_deal &&
-      cam < (int)r.d_cold.size() && r.d_cold[cam]) {  // the whole frame: its cold order
-    P.cold_order = reinterpret_cast<const int*>(r.d_cold[cam]) + P.num_sel_tiles;
+      cam < (int)r.d_cold.size() && r.d_cold[cam].p) {  // the whole frame: its cold order
+    P.cold_order = reinterpret_cast<const int*>(r.d_cold[cam].p) + P.num_sel_tiles;
     P.cold_tiles = P.num_sel_tiles;
   }
   return P;
@@ -688,7 +576,11 @@ const hipEvent_t* timing_marks(rt_scene* s, const RenderParams& P) {
   if (t.pending.size() >= kTimingPending) fold_timing(t);
   if (t.spare.empty()) {
     std::array<hipEvent_t, 4> q{};
-    for (hipEvent_t& e : q) hip_check(hipEventCreate(&e), "timing event");
+    for (hipEvent_t& e : q) {
+      t.events.emplace_back();
+      t.events.back().create(hipEventDefault, "timing event");
+      e = t.events.back();
+    }
     t.spare.push_back(q);
   }
   t.pending.push_back(t.spare.back());
@@ -711,7 +603,7 @@ void enqueue_samples(rt_scene* s, const Replica& r, const RenderParams& P, int s
     Q.msaa_seed = s->msaa_seed;
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
-    hip_check(launch_render(Q, r.d_nodes, r.d_prims, r.d_normals, r.d_mats, r.d_lights, fast,
+    hip_check(launch_render(Q, r.d_nodes.p, r.d_prims.p, r.d_normals.p, r.d_mats.p, r.d_lights.p, fast,
                             s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr, stream),
               "render launch");
   }
@@ -740,7 +632,7 @@ void enqueue_frame(rt_scene* s, const Replica& r, const RenderParams& P, int sam
                    float* d_samples, hipStream_t stream, bool timed) {
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
-    hip_check(launch_render(P, r.d_nodes, r.d_prims, r.d_normals, r.d_mats, r.d_lights, fast,
+    hip_check(launch_render(P, r.d_nodes.p, r.d_prims.p, r.d_normals.p, r.d_mats.p, r.d_lights.p, fast,
                             s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr, stream),
               "render launch");
     return;
@@ -753,18 +645,6 @@ size_t sample_floats(const rt_camera& c) {
   return c.num_samples > 1 ? (size_t)c.num_samples * c.num_samples * c.width * c.height * 3 : 0;
 }
 
-// Grow-only device buffer.
-template <typename T>
-void ensure(T*& p, size_t& cap, size_t need, const char* what) {
-  need = std::max<size_t>(need, 1);
-  if (need <= cap) return;
-  (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  hip_check(hipMalloc(&p, need * sizeof(T)), what);
-  cap = need;
-}
-
 RenderCtx* acquire_ctx(Replica& r) {
   {
     std::lock_guard<std::mutex> lk(r.mu);
@@ -775,23 +655,18 @@ RenderCtx* acquire_ctx(Replica& r) {
     }
   }
   DeviceGuard g(r.device);
-  std::unique_ptr<RenderCtx> c(new RenderCtx);
-  try {
-    hip_check(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "stream");
-    hip_check(hipEventCreate(&c->e0), "event");
-    hip_check(hipEventCreate(&c->e1), "event");
-    hip_check(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming), "event");
-    hip_check(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming), "event");
-    hip_check(hipEventCreateWithFlags(&c->ev_gathered, hipEventDisableTiming), "event");
-    hip_check(hipEventRecord(c->ev_gathered, c->stream), "event record");  // (complete)
-    hip_check(hipMalloc(&c->d_cnt, sizeof(unsigned long long) * kCounterAlloc), "alloc counters");
-  } catch (...) {
-    free_ctx(c.release());
-    throw;
-  }
+  auto c = std::make_unique<RenderCtx>();
+  c->stream.create();
+  c->e0.create();
+  c->e1.create();
+  c->ev_in.create(hipEventDisableTiming);
+  c->ev_out.create(hipEventDisableTiming);
+  c->ev_gathered.create(hipEventDisableTiming);
+  hip_check(hipEventRecord(c->ev_gathered, c->stream), "event record");  // (complete)
+  c->d_cnt.reserve(kCounterAlloc, "alloc counters");
   std::lock_guard<std::mutex> lk(r.mu);
-  r.ctx_all.push_back(c.get());
-  return c.release();
+  r.ctx_all.push_back(std::move(c));
+  return r.ctx_all.back().get();
 }
 
 void release_ctx(Replica& r, RenderCtx* c) {
@@ -852,19 +727,17 @@ struct CtxSet {
 // P at them.
 void bind_ctx(rt_scene* s, RenderCtx* x, RenderParams& P, const rt_camera& c) {
   const size_t lanes = (size_t)kTile * kTile * (size_t)std::max(1, P.num_sel_tiles);
-  ensure(x->d_hits, x->hits_records, lanes, "alloc hit records");
-  P.hits = x->d_hits;
-  ensure(x->d_occ, x->occ_words, (size_t)P.occ_words * lanes, "alloc occlusion bits");
-  P.occ = x->d_occ;
-  ensure(x->d_sched, x->sched_words, (size_t)sched_words_for(lanes / (kTile * kTile)),
-         "alloc tile schedule");
-  set_schedule(P, x->d_sched);
+  x->d_hits.reserve(lanes, "alloc hit records");
+  P.hits = x->d_hits.p;
+  x->d_occ.reserve((size_t)P.occ_words * lanes, "alloc occlusion bits");
+  P.occ = x->d_occ.p;
+  x->d_sched.reserve((size_t)sched_words_for(lanes / (kTile * kTile)), "alloc tile schedule");
+  set_schedule(P, x->d_sched.p);
   if (s->needs_recursion) {
-    ensure(x->d_frames, x->frames_floats, frame_floats(s->host, P.num_sel_tiles),
-           "alloc ray-tree frames");
-    P.frames = x->d_frames;
+    x->d_frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
+    P.frames = x->d_frames.p;
   }
-  if (c.num_samples > 1) ensure(x->d_samples, x->samples_floats, sample_floats(c), "alloc MSAA samples");
+  if (c.num_samples > 1) x->d_samples.reserve(sample_floats(c), "alloc MSAA samples");
 }
 
 void add_counters(const std::vector<unsigned long long>& cnt, rt_stats* stats) {
@@ -874,6 +747,93 @@ void add_counters(const std::vector<unsigned long long>& cnt, rt_stats* stats) {
     stats->secondary_rays += (long long)cnt[kCounterWidth * r + kCntSecondary];
     stats->primary_hits += (long long)cnt[kCounterWidth * r + kCntHits];
   }
+}
+
+// Device d's share of a multi-device frame on its way to the first device: `words` 4-B words
+// (floats or pixel records; 0: nothing to send) from src on device d to dst on the first.
+struct GatherPart {
+  const float* src;
+  float* dst;
+  size_t words;
+};
+
+// Lands part(d) of every device d > 0 on the first device, ordered after the work on device d's
+// context stream and on the first device's.  Copy gather: ev_out of context d, a wait and a peer
+// copy on the first device's stream, then ev_gathered there (the contexts' write-after-read
+// fence); else one RCCL group of send / receive pairs.  Caller holds s->multi_mu and has the
+// first device current.
+template <typename Part>
+void gather_parts(rt_scene* s, CtxSet& cx, Part&& part) {
+  const int D = (int)s->rep.size();
+  RenderCtx* x0 = cx.x[0];
+  if (D == 1) return;  // the one device rendered the frame in place
+  if (s->copy_gather) {
+    for (int d = 1; d < D; d++) {
+      const GatherPart g = part(d);
+      if (!g.words) continue;
+      {
+        DeviceGuard gd(s->rep[d]->device);
+        hip_check(hipEventRecord(cx.x[d]->ev_out, cx.x[d]->stream), "event record");
+      }
+      hip_check(hipStreamWaitEvent(x0->stream, cx.x[d]->ev_out, 0), "wait event");
+      hip_check(hipMemcpyPeerAsync(g.dst, s->rep[0]->device, g.src, s->rep[d]->device,
+                                   g.words * sizeof(float), x0->stream),
+                "gather copy");
+    }
+    hip_check(hipEventRecord(x0->ev_gathered, x0->stream), "event record");
+    return;
+  }
+  nccl_check(ncclGroupStart(), "ncclGroupStart");
+  for (int d = 1; d < D; d++) {
+    const GatherPart g = part(d);
+    if (!g.words) continue;
+    nccl_check(ncclSend(g.src, g.words, ncclFloat, 0, s->comms[d], cx.x[d]->stream), "ncclSend");
+    nccl_check(ncclRecv(g.dst, g.words, ncclFloat, d, s->comms[0], x0->stream), "ncclRecv");
+  }
+  nccl_check(ncclGroupEnd(), "ncclGroupEnd");
+}
+
+// The untile / resolve kernels' view of a frame whose deal units (tiles, or 2x2 blocks with
+// RT_UNTILE_BLOCKS) were dealt over `devices` slots of `slot` tiles; recv, out and vec are the
+// caller's.
+UntileParams untile_params(const rt_camera& c, const TilePlan& tp, int row0, int row_stride,
+                           int devices, int slot, int tile_offset, int flags) {
+  UntileParams U;
+  U.recv = nullptr;
+  U.out = nullptr;
+  U.width = c.width;
+  U.row0 = row0;
+  U.row_stride = row_stride;
+  U.rows = tp.rows;
+  U.tiles_x = tp.tiles_x;
+  U.tiles_total = tp.tiles_total;
+  U.devices = devices;
+  U.slot = slot;
+  U.tile_offset = tile_offset % devices;
+  U.blocks = (flags & RT_UNTILE_BLOCKS) ? 1 : 0;
+  U.skip_root = (flags & RT_UNTILE_SKIP_ROOT) ? 1 : 0;
+  U.vec = 0;
+  return U;
+}
+
+// The argument checks rt_untile_device and rt_resolve_device (`records`) share, under the
+// caller's name `fn`; returns the frame's UntileParams (recv, out and vec left to the caller).
+UntileParams checked_untile_params(const char* fn, bool records, const rt_scene* s, int cam,
+                                   int row0, int row_stride, int devices, int slot,
+                                   int tile_offset, int flags, const void* d_gathered,
+                                   const float* d_out) {
+  check_render_args(s, cam, row0, row_stride);
+  if (devices < 1 || slot < 0 || tile_offset < 0 || !d_gathered || !d_out ||
+      (flags & ~(RT_UNTILE_BLOCKS | RT_UNTILE_SKIP_ROOT)) || ((flags & RT_UNTILE_BLOCKS) && slot % 4))
+    throw std::invalid_argument(std::string(fn) + ": bad argument");
+  if (records && !records_ok(s, cam)) throw std::domain_error(std::string(fn) + ": no pixel records here");
+  const rt_camera& c = s->host.cameras[cam];
+  const TilePlan tp = plan(c, row0, row_stride);
+  const bool blocks = flags & RT_UNTILE_BLOCKS;
+  const long long units = blocks ? deal_blocks(tp.tiles_x, tp.tiles_total / tp.tiles_x) : tp.tiles_total;
+  if ((long long)devices * (blocks ? slot / 4 : slot) < units)
+    throw std::invalid_argument(std::string(fn) + ": devices * slot is smaller than the frame's share");
+  return untile_params(c, tp, row0, row_stride, devices, slot, tile_offset, flags);
 }
 
 // One frame of an MSAA camera over every device of a multi-device scene (the
@@ -907,13 +867,13 @@ void render_multi_msaa(rt_scene* s, CtxSet& cx, int cam, float* d_frame, hipStre
     // stream) has finished before this frame renders into it
     if (d > 0 && s->copy_gather) hip_check(hipStreamWaitEvent(x->stream, x0->ev_gathered, 0), "wait event");
     if (d > 0) {
-      ensure(x->d_image, x->image_floats, frame, "alloc band frame");
-      dst = x->d_image;
+      x->d_image.reserve(frame, "alloc band frame");
+      dst = x->d_image.p;
     }
-    RenderParams P = make_params(s, r, cam, lo, 1, 0, 1, 0, dst, per_call ? x->d_cnt : r.d_counters);
+    RenderParams P = make_params(s, r, cam, lo, 1, 0, 1, 0, dst, per_call ? x->d_cnt.p : r.d_counters.p);
     limit_rows(P, hi - lo);
     bind_ctx(s, x, P, c);
-    enqueue_samples(s, r, P, n, x->d_samples, x->stream, d == 0);
+    enqueue_samples(s, r, P, n, x->d_samples.p, x->stream, d == 0);
     for (const int row : {lo - 1, hi}) {  // the halo rows the splat of the band's edges reads
       if (row < 0 || row >= H) continue;
       RenderParams Q = make_params(s, r, cam, row, 1, 0, 1, 0, dst, nullptr);
@@ -921,45 +881,17 @@ void render_multi_msaa(rt_scene* s, CtxSet& cx, int cam, float* d_frame, hipStre
       Q.hits = P.hits;
       Q.occ = P.occ;
       Q.frames = P.frames;
-      set_schedule(Q, x->d_sched);
-      enqueue_samples(s, r, Q, n, x->d_samples, x->stream, false);
+      set_schedule(Q, x->d_sched.p);
+      enqueue_samples(s, r, Q, n, x->d_samples.p, x->stream, false);
     }
-    enqueue_resolve(s, W, H, n, x->d_samples, dst, lo, hi, x->stream);
+    enqueue_resolve(s, W, H, n, x->d_samples.p, dst, lo, hi, x->stream);
   }
   DeviceGuard g(s->rep[0]->device);
-  if (D > 1) {
-    auto band = [&](int d, float* base) {
-      const int lo = (int)((long long)H * d / D), hi = (int)((long long)H * (d + 1) / D);
-      return std::make_pair(base + (size_t)lo * W * 3, (size_t)(hi - lo) * W * 3);
-    };
-    if (s->copy_gather) {
-      for (int d = 1; d < D; d++) {
-        const auto src = band(d, cx.x[d]->d_image);
-        if (!src.second) continue;
-        {
-          DeviceGuard gd(s->rep[d]->device);
-          hip_check(hipEventRecord(cx.x[d]->ev_out, cx.x[d]->stream), "event record");
-        }
-        hip_check(hipStreamWaitEvent(x0->stream, cx.x[d]->ev_out, 0), "wait event");
-        hip_check(hipMemcpyPeerAsync(band(d, d_frame).first, s->rep[0]->device, src.first,
-                                     s->rep[d]->device, src.second * sizeof(float), x0->stream),
-                  "gather copy");
-      }
-      hip_check(hipEventRecord(x0->ev_gathered, x0->stream), "event record");
-    } else {
-      nccl_check(ncclGroupStart(), "ncclGroupStart");
-      for (int d = 1; d < D; d++) {
-        const auto src = band(d, cx.x[d]->d_image);
-        if (!src.second) continue;
-        nccl_check(ncclSend(src.first, src.second, ncclFloat, 0, s->comms[d], cx.x[d]->stream),
-                   "ncclSend");
-        nccl_check(ncclRecv(band(d, d_frame).first, src.second, ncclFloat, d, s->comms[0],
-                            x0->stream),
-                   "ncclRecv");
-      }
-      nccl_check(ncclGroupEnd(), "ncclGroupEnd");
-    }
-  }
+  gather_parts(s, cx, [&](int d) {  // device d's band (an empty one is skipped)
+    const int lo = (int)((long long)H * d / D), hi = (int)((long long)H * (d + 1) / D);
+    const size_t off = (size_t)lo * W * 3;
+    return GatherPart{cx.x[d]->d_image.p + off, d_frame + off, (size_t)(hi - lo) * W * 3};
+  });
   if (s0 != x0->stream) {
     hip_check(hipEventRecord(x0->ev_out, x0->stream), "event record");
     hip_check(hipStreamWaitEvent(s0, x0->ev_out, 0), "wait event");
@@ -1003,57 +935,25 @@ void render_multi(rt_scene* s, CtxSet& cx, int cam, int row0, int row_stride, fl
     // copy gather: the previous frame's peer copy out of d_out (on the first device's stream)
     // has finished before this frame renders into it
     if (d > 0 && s->copy_gather) hip_check(hipStreamWaitEvent(x->stream, x0->ev_gathered, 0), "wait event");
-    if (d > 0) ensure(x->d_out, x->out_floats, (size_t)slot * tile_words, "alloc tile slot");
+    if (d > 0) x->d_out.reserve((size_t)slot * tile_words, "alloc tile slot");
     RenderParams P = make_params(s, r, cam, row0, row_stride, d, D,
                                  d == 0 ? RT_TILE_BLOCKS
                                         : RT_TILE_MAJOR | RT_TILE_BLOCKS | (records ? RT_TILE_RECORDS : 0),
-                                 d == 0 ? d_frame : x->d_out, per_call ? x->d_cnt : r.d_counters);
+                                 d == 0 ? d_frame : x->d_out.p, per_call ? x->d_cnt.p : r.d_counters.p);
     bind_ctx(s, x, P, c);
     enqueue_frame(s, r, P, 1, nullptr, x->stream, d == 0);
   }
   DeviceGuard g(s->rep[0]->device);
-  ensure(x0->d_recv, x0->recv_floats, (size_t)D * slot * tile_words, "alloc gathered slots");
+  x0->d_recv.reserve((size_t)D * slot * tile_words, "alloc gathered slots");
   const size_t count = (size_t)slot * tile_words;  // 4-B words (floats or pixel records)
-  if (D == 1) {
-    // nothing to gather: the one device rendered the frame in place
-  } else if (s->copy_gather) {
-    for (int d = 1; d < D; d++) {
-      {
-        DeviceGuard gd(s->rep[d]->device);
-        hip_check(hipEventRecord(cx.x[d]->ev_out, cx.x[d]->stream), "event record");
-      }
-      hip_check(hipStreamWaitEvent(x0->stream, cx.x[d]->ev_out, 0), "wait event");
-      hip_check(hipMemcpyPeerAsync(x0->d_recv + (size_t)d * count, s->rep[0]->device,
-                                   cx.x[d]->d_out, s->rep[d]->device, count * sizeof(float),
-                                   x0->stream),
-                "gather copy");
-    }
-    hip_check(hipEventRecord(x0->ev_gathered, x0->stream), "event record");
-  } else {
-    nccl_check(ncclGroupStart(), "ncclGroupStart");
-    for (int d = 1; d < D; d++)
-      nccl_check(ncclSend(cx.x[d]->d_out, count, ncclFloat, 0, s->comms[d], cx.x[d]->stream),
-                 "ncclSend");
-    for (int d = 1; d < D; d++)
-      nccl_check(ncclRecv(x0->d_recv + (size_t)d * count, count, ncclFloat, d, s->comms[0],
-                          x0->stream),
-                 "ncclRecv");
-    nccl_check(ncclGroupEnd(), "ncclGroupEnd");
-  }
-  UntileParams U;
-  U.recv = x0->d_recv;
+  gather_parts(s, cx, [&](int d) {
+    return GatherPart{cx.x[d]->d_out.p, x0->d_recv.p + (size_t)d * count, count};
+  });
+  // (skip root: the first device's blocks are already in d_frame)
+  UntileParams U = untile_params(c, tp, row0, row_stride, D, slot, 0,
+                                 RT_UNTILE_BLOCKS | RT_UNTILE_SKIP_ROOT);
+  U.recv = x0->d_recv.p;
   U.out = d_frame;
-  U.width = c.width;
-  U.row0 = row0;
-  U.row_stride = row_stride;
-  U.rows = tp.rows;
-  U.tiles_x = tp.tiles_x;
-  U.tiles_total = tp.tiles_total;
-  U.devices = D;
-  U.slot = slot;
-  U.tile_offset = 0;
-  U.blocks = 1;
-  U.skip_root = 1;  // the first device's blocks are already in d_frame
   U.vec = untile_vec(U);
   if (D > 1 && records) {  // the others' pixel records shaded into the frame
     const RenderParams P0 = make_params(s, *s->rep[0], cam, row0, row_stride, 0, 1, 0, d_frame,
@@ -1082,7 +982,6 @@ void evict_scratch(Replica& r) {
   if (victim == r.streams.size()) return;  // every one in use: let the table grow
   StreamScratch& x = *r.streams[victim];
   if (x.done) hip_check(hipEventSynchronize(x.done), "synchronize evicted scratch");
-  free_scratch(x);
   r.streams.erase(r.streams.begin() + (long)victim);
 }
 
@@ -1102,17 +1001,10 @@ StreamScratch* scratch_for(rt_scene* s, Replica& r, void* stream, std::unique_lo
   x->stream = stream;
   x->used = ++r.tick;
   const size_t most = s->most;
-  try {
-    hip_check(hipEventCreateWithFlags(&x->done, hipEventDisableTiming), "event");
-    hip_check(hipMalloc(&x->hits, most * sizeof(int2_t)), "alloc hit records");
-    hip_check(hipMalloc(&x->occ, most * sizeof(unsigned) * occ_words(s->host)),
-              "alloc occlusion bits");
-    hip_check(hipMalloc(&x->sched, sched_words_for(most / (kTile * kTile)) * sizeof(unsigned)),
-              "alloc tile schedule");
-  } catch (...) {
-    free_scratch(*x);
-    throw;
-  }
+  x->done.create(hipEventDisableTiming);
+  x->hits.reserve(most, "alloc hit records");
+  x->occ.reserve(most * occ_words(s->host), "alloc occlusion bits");
+  x->sched.reserve(sched_words_for(most / (kTile * kTile)), "alloc tile schedule");
   r.streams.push_back(std::move(x));
   held = std::unique_lock<std::mutex>(r.streams.back()->mu);
   return r.streams.back().get();
@@ -1168,10 +1060,7 @@ int rt_scene_create_multi(const rt_scene_desc* desc, int device_count, const int
     build_host_scene(*desc, s->host);
     return create_from_host(s.get(), devs, true);
   });
-  if (rc != RT_OK) {
-    free_device(s.get());
-    return rc;
-  }
+  if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
 }
@@ -1185,10 +1074,7 @@ int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
     build_host_scene(*desc, s->host);
     return create_from_host(s.get(), devs, false);
   });
-  if (rc != RT_OK) {
-    free_device(s.get());
-    return rc;
-  }
+  if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
 }
@@ -1203,10 +1089,7 @@ int rt_scene_load_xml(const char* xml_path, int device, rt_scene** out) {
     return RT_OK;
   });
   if (rc == RT_OK) rc = load_xml_into(s.get(), xml_path, &devs, 0, nullptr);
-  if (rc != RT_OK) {
-    free_device(s.get());
-    return rc;
-  }
+  if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
 }
@@ -1217,17 +1100,12 @@ int rt_scene_load_xml_multi(const char* xml_path, int device_count, const int* d
   *out = nullptr;
   auto s = std::make_unique<rt_scene>();
   const int rc = load_xml_into(s.get(), xml_path, nullptr, device_count, devices);
-  if (rc != RT_OK) {
-    free_device(s.get());
-    return rc;
-  }
+  if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
 }
 
 void rt_scene_destroy(rt_scene* s) {
-  if (!s) return;
-  free_device(s);
   delete s;
 }
 
@@ -1372,24 +1250,23 @@ int rt_render_device_range(rt_scene* s, int cam, int row0, int row_stride, int t
     std::unique_lock<std::mutex> lk;
     StreamScratch* sc = scratch_for(s, r, stream, lk);
     RenderParams P = make_params(s, r, cam, row0, row_stride, tile_begin, tile_step, tile_major,
-                                 d_out, r.d_counters);
-    P.hits = sc->hits;
-    P.occ = sc->occ;
-    set_schedule(P, sc->sched);
+                                 d_out, r.d_counters.p);
+    P.hits = sc->hits.p;
+    P.occ = sc->occ.p;
+    set_schedule(P, sc->sched.p);
     const int unit_tiles = P.block_deal ? 4 : 1;  // tile_count counts deal units
     if (tile_count >= 0 && (long long)tile_count * unit_tiles < P.num_sel_tiles) {
       if (c.num_samples > 1) throw std::domain_error("NumSamples > 1 renders whole row-major frames only");
       P.num_sel_tiles = tile_count * unit_tiles;
     }
     if (s->needs_recursion) {
-      ensure(sc->frames, sc->frames_capacity, frame_floats(s->host, P.num_sel_tiles),
-             "alloc ray-tree frames");
-      P.frames = sc->frames;
+      sc->frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
+      P.frames = sc->frames.p;
     }
     if (c.num_samples > 1) {
       if (tile_begin != 0 || tile_step != 1 || tile_major)
         throw std::domain_error("NumSamples > 1 renders whole row-major frames only");
-      ensure(sc->samples, sc->samples_capacity, sample_floats(c), "alloc MSAA samples");
+      sc->samples.reserve(sample_floats(c), "alloc MSAA samples");
     }
     // warm order: a frame of the same selection as the stream's previous one
     // dispatches its primary kernel heaviest-first by that frame's measured tile costs
@@ -1397,7 +1274,7 @@ int rt_render_device_range(rt_scene* s, int cam, int row0, int row_stride, int t
                                        P.num_sel_tiles, P.block_deal};
     const bool orderable = c.num_samples <= 1 && !P.frames && P.num_lights > 0;
     P.primary_order = orderable && sc->order_valid && sc->order_key == key ? 1 : 0;
-    enqueue_frame(s, r, P, c.num_samples, sc->samples, (hipStream_t)stream, true);
+    enqueue_frame(s, r, P, c.num_samples, sc->samples.p, (hipStream_t)stream, true);
     hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
     sc->order_key = key;
     sc->order_valid = orderable;
@@ -1409,32 +1286,11 @@ int rt_untile_device(rt_scene* s, int cam, int row0, int row_stride, int devices
                      int tile_offset, int flags, const float* d_gathered, float* d_out,
                      void* stream) {
   return guarded([&] {
-    check_render_args(s, cam, row0, row_stride);
-    if (devices < 1 || slot < 0 || tile_offset < 0 || !d_gathered || !d_out ||
-        (flags & ~(RT_UNTILE_BLOCKS | RT_UNTILE_SKIP_ROOT)) ||
-        ((flags & RT_UNTILE_BLOCKS) && slot % 4))
-      throw std::invalid_argument("rt_untile_device: bad argument");
-    const rt_camera& c = s->host.cameras[cam];
-    const TilePlan tp = plan(c, row0, row_stride);
-    const int blocks = (flags & RT_UNTILE_BLOCKS) ? 1 : 0;
-    const long long units = blocks ? deal_blocks(tp.tiles_x, tp.tiles_total / tp.tiles_x) : tp.tiles_total;
-    if ((long long)devices * (blocks ? slot / 4 : slot) < units)
-      throw std::invalid_argument("rt_untile_device: devices * slot is smaller than the frame's share");
+    UntileParams U = checked_untile_params("rt_untile_device", false, s, cam, row0, row_stride,
+                                           devices, slot, tile_offset, flags, d_gathered, d_out);
     DeviceGuard g(s->rep[0]->device);
-    UntileParams U;
     U.recv = d_gathered;
     U.out = d_out;
-    U.width = c.width;
-    U.row0 = row0;
-    U.row_stride = row_stride;
-    U.rows = tp.rows;
-    U.tiles_x = tp.tiles_x;
-    U.tiles_total = tp.tiles_total;
-    U.devices = devices;
-    U.slot = slot;
-    U.tile_offset = tile_offset % devices;
-    U.blocks = blocks;
-    U.skip_root = (flags & RT_UNTILE_SKIP_ROOT) ? 1 : 0;
     U.vec = untile_vec(U);
     hip_check(launch_untile(U, (hipStream_t)stream), "untile launch");
     return RT_OK;
@@ -1460,7 +1316,7 @@ int rt_tile_costs(rt_scene* s, void* stream, unsigned* host_out, int capacity) {
     const long long n = x->order_key[5];  // the last selection's tiles
     if (n > capacity) throw std::invalid_argument("rt_tile_costs: capacity below the frame's tiles");
     hip_check(hipStreamSynchronize((hipStream_t)stream), "synchronize stream");
-    hip_check(hipMemcpy(host_out, x->sched + sched_snap_offset((unsigned long long)n),
+    hip_check(hipMemcpy(host_out, x->sched.p + sched_snap_offset((unsigned long long)n),
                         (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost),
               "read tile costs");
     return (int)n;
@@ -1477,36 +1333,13 @@ int rt_resolve_device(rt_scene* s, int cam, int row0, int row_stride, int device
                       int tile_offset, int flags, const unsigned* d_gathered, float* d_out,
                       void* stream) {
   return guarded([&] {
-    check_render_args(s, cam, row0, row_stride);
-    if (devices < 1 || slot < 0 || tile_offset < 0 || !d_gathered || !d_out ||
-        (flags & ~(RT_UNTILE_BLOCKS | RT_UNTILE_SKIP_ROOT)) ||
-        ((flags & RT_UNTILE_BLOCKS) && slot % 4))
-      throw std::invalid_argument("rt_resolve_device: bad argument");
-    if (!records_ok(s, cam)) throw std::domain_error("rt_resolve_device: no pixel records here");
-    const rt_camera& c = s->host.cameras[cam];
-    const TilePlan tp = plan(c, row0, row_stride);
-    const int blocks = (flags & RT_UNTILE_BLOCKS) ? 1 : 0;
-    const long long units = blocks ? deal_blocks(tp.tiles_x, tp.tiles_total / tp.tiles_x) : tp.tiles_total;
-    if ((long long)devices * (blocks ? slot / 4 : slot) < units)
-      throw std::invalid_argument("rt_resolve_device: devices * slot is smaller than the frame's share");
+    UntileParams U = checked_untile_params("rt_resolve_device", true, s, cam, row0, row_stride,
+                                           devices, slot, tile_offset, flags, d_gathered, d_out);
     Replica& r = *s->rep[0];
     DeviceGuard g(r.device);
     const RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, d_out, nullptr);
-    UntileParams U;
     U.recv = reinterpret_cast<const float*>(d_gathered);
     U.out = d_out;
-    U.width = c.width;
-    U.row0 = row0;
-    U.row_stride = row_stride;
-    U.rows = tp.rows;
-    U.tiles_x = tp.tiles_x;
-    U.tiles_total = tp.tiles_total;
-    U.devices = devices;
-    U.slot = slot;
-    U.tile_offset = tile_offset % devices;
-    U.blocks = blocks;
-    U.skip_root = (flags & RT_UNTILE_SKIP_ROOT) ? 1 : 0;
-    U.vec = 0;
     hip_check(launch_resolve(P, U, s->has_spheres, (hipStream_t)stream), "resolve launch");
     return RT_OK;
   });
@@ -1559,9 +1392,11 @@ int rt_release_stream_scratch(rt_scene* s, void* stream) {
       }
       if (!x) continue;
       DeviceGuard g(r.device);
-      std::lock_guard<std::mutex> lk(x->mu);  // no enqueue on it is in progress
-      hip_check(hipStreamSynchronize((hipStream_t)stream), "synchronize stream");
-      free_scratch(*x);
+      {
+        std::lock_guard<std::mutex> lk(x->mu);  // no enqueue on it is in progress
+        hip_check(hipStreamSynchronize((hipStream_t)stream), "synchronize stream");
+      }
+      x.reset();
     }
     return RT_OK;
   });
@@ -1574,9 +1409,9 @@ int rt_collect_stats(rt_scene* s, rt_stats* stats) {
     for (auto& rp : s->rep) {
       DeviceGuard g(rp->device);
       std::vector<unsigned long long> c(kCounterWidth * kCounterRows);
-      hip_check(hipMemcpy(c.data(), rp->d_counters, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
+      hip_check(hipMemcpy(c.data(), rp->d_counters.p, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
                 "read counters");
-      hip_check(hipMemset(rp->d_counters, 0, c.size() * sizeof c[0]), "reset counters");
+      hip_check(hipMemset(rp->d_counters.p, 0, c.size() * sizeof c[0]), "reset counters");
       add_counters(c, stats);
     }
     return RT_OK;
@@ -1590,9 +1425,9 @@ int rt_debug_counters(rt_scene* s, long long* out16) {
     for (auto& rp : s->rep) {
       DeviceGuard g(rp->device);
       std::vector<unsigned long long> c(kCounterWidth * kCounterRows);
-      hip_check(hipMemcpy(c.data(), rp->d_counters, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
+      hip_check(hipMemcpy(c.data(), rp->d_counters.p, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
                 "read counters");
-      hip_check(hipMemset(rp->d_counters, 0, c.size() * sizeof c[0]), "reset counters");
+      hip_check(hipMemset(rp->d_counters.p, 0, c.size() * sizeof c[0]), "reset counters");
       for (int k = 0; k < kCounterWidth; k++) {
         unsigned long long sum = 0;
         for (int r = 0; r < kCounterRows; r++) sum += c[kCounterWidth * r + k];
@@ -1623,10 +1458,9 @@ int rt_debug_quotient_check(int device, unsigned long long seed, long long count
   if (!out2 || count < 0) return set_error(RT_E_INVALID, "rt_debug_quotient_check: bad argument");
   return guarded([&] {
     DeviceGuard g(device);
-    unsigned long long* d = nullptr;
-    hip_check(hipMalloc(&d, 2 * sizeof *d), "alloc");
-    std::unique_ptr<unsigned long long, void (*)(unsigned long long*)> hold(
-        d, [](unsigned long long* p) { (void)hipFree(p); });
+    DevBuf<unsigned long long> buf;
+    buf.reserve(2, "alloc");
+    unsigned long long* d = buf.p;
     hip_check(hipMemset(d, 0, 2 * sizeof *d), "clear");
     hip_check(launch_quot_check(seed, count, d, nullptr), "quotient check launch");
     unsigned long long h[2];
@@ -1654,16 +1488,16 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
     const size_t frame = (size_t)c.width * c.height * 3;
     float* d_frame = nullptr;
     if (multi) {  // (d_out holds the first device's tile slot)
-      ensure(x->d_image, x->image_floats, frame, "alloc frame");
-      d_frame = x->d_image;
+      x->d_image.reserve(frame, "alloc frame");
+      d_frame = x->d_image.p;
     } else {
-      ensure(x->d_out, x->out_floats, frame, "alloc frame");
-      d_frame = x->d_out;
+      x->d_out.reserve(frame, "alloc frame");
+      d_frame = x->d_out.p;
     }
     // Counters are per scene; this call reports its own deltas via the contexts' buffers.
     for (size_t d = 0; d < cx.x.size(); d++) {
       DeviceGuard gd(s->rep[d]->device);
-      hip_check(hipMemsetAsync(cx.x[d]->d_cnt, 0,
+      hip_check(hipMemsetAsync(cx.x[d]->d_cnt.p, 0,
                                sizeof(unsigned long long) * kCounterWidth * kCounterRows,
                                cx.x[d]->stream),
                 "zero counters");
@@ -1692,7 +1526,7 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
         (void)hipGetLastError();  // pageable memory: not an error here
     }
     if (direct) {
-      RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, direct, x->d_cnt);
+      RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, direct, x->d_cnt.p);
       bind_ctx(s, x, P, c);
       // block order: the frame is bound by its writes over PCIe, which the heavy-first (cold)
       // order scatters (0.674 -> 0.742 ms per C3 frame, profiles/r06/ab_dropin_cold.jsonl)
@@ -1701,34 +1535,41 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
 #define RT_PAIR_ROWS 1
 #endif
       P.pair_rows = RT_PAIR_ROWS;
-      enqueue_frame(s, r, P, c.num_samples, x->d_samples, x->stream, true);
+      enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
       hip_check(hipEventRecord(x->e1, x->stream), "event record");
     } else if (!multi && c.num_samples <= 1 && chunks > 1) {
       // the drop-in seam: the frame as `chunks` bands of tile rows, one
       // launch each on the context's stream; each band goes to the caller's buffer on the copy
       // stream as soon as its launch is done, while the next bands render
-      if (!x->copy_stream)
-        hip_check(hipStreamCreateWithFlags(&x->copy_stream, hipStreamNonBlocking), "copy stream");
+      x->copy_stream.create("copy stream");
       for (int k = 0; k < chunks; k++) {
         const int ty0 = (int)((long long)tiles_y * k / chunks);
         const int ty1 = (int)((long long)tiles_y * (k + 1) / chunks);
         RenderParams P = make_params(s, r, cam, row0, row_stride, ty0 * tp.tiles_x, 1, 0, d_frame,
-                                     x->d_cnt);
+                                     x->d_cnt.p);
         P.num_sel_tiles = (ty1 - ty0) * tp.tiles_x;
         bind_ctx(s, x, P, c);
         P.tile_cost = nullptr;  // no dispatch order for a next frame (nothing reuses it here)
-        enqueue_frame(s, r, P, c.num_samples, x->d_samples, x->stream, true);
-        if (!x->ev_chunk[k])
-          hip_check(hipEventCreateWithFlags(&x->ev_chunk[k], hipEventDisableTiming), "event");
+        enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
+        x->ev_chunk[k].create(hipEventDisableTiming);
         hip_check(hipEventRecord(x->ev_chunk[k], x->stream), "event record");
       }
       hip_check(hipEventRecord(x->e1, x->stream), "event record");
+      // no copy into out_rgb is pending when a failure below leaves this call
+      struct Drain {
+        hipStream_t st;
+        bool armed = true;
+        ~Drain() {
+          if (armed) (void)hipStreamSynchronize(st);
+        }
+      } drain{x->copy_stream};
       for (int k = 0; k < chunks; k++) {
         const int ty0 = (int)((long long)tiles_y * k / chunks);
         const int ty1 = (int)((long long)tiles_y * (k + 1) / chunks);
         hip_check(hipStreamWaitEvent(x->copy_stream, x->ev_chunk[k], 0), "wait band");
         copy_rows(kTile * ty0, std::min(tp.rows, kTile * ty1), x->copy_stream);
       }
+      drain.armed = false;
       hip_check(hipStreamSynchronize(x->copy_stream), "synchronize copies");
     } else {
       if (multi && c.num_samples > 1) {
@@ -1736,9 +1577,9 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
       } else if (multi) {
         render_multi(s, cx, cam, row0, row_stride, d_frame, x->stream, true);
       } else {
-        RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, d_frame, x->d_cnt);
+        RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, d_frame, x->d_cnt.p);
         bind_ctx(s, x, P, c);
-        enqueue_frame(s, r, P, c.num_samples, x->d_samples, x->stream, true);
+        enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
       }
       hip_check(hipEventRecord(x->e1, x->stream), "event record");
       copy_rows(0, tp.rows, x->stream);
@@ -1747,7 +1588,7 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
                                                      std::vector<unsigned long long>(kCounterAlloc));
     for (size_t d = 0; d < cx.x.size(); d++) {
       DeviceGuard gd(s->rep[d]->device);
-      hip_check(hipMemcpyAsync(cnt[d].data(), cx.x[d]->d_cnt, kCounterAlloc * sizeof(unsigned long long),
+      hip_check(hipMemcpyAsync(cnt[d].data(), cx.x[d]->d_cnt.p, kCounterAlloc * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, cx.x[d]->stream),
                 "copy counters");
     }

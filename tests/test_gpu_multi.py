@@ -319,3 +319,38 @@ def test_many_caller_streams_stay_bounded(scene_dir, devices):
         torch.cuda.synchronize()
         for k, b in enumerate(bufs):
             assert same(b.cpu().numpy(), ref), k
+
+
+@pytest.mark.parametrize("devices", [[0], [0, 0, 0]])
+def test_scene_churn(tmp_path, devices):
+    """Scenes made and destroyed over and over, each used the ways that make the library
+    allocate (a pooled context with its frame and copy stream, the pinned path, per-stream
+    scratch or per-stream contexts, one stream released early, the rest left to the scene's
+    destruction): every frame of every cycle is the oracle's bit for bit."""
+    import torch
+    import gen_scene as G
+    import ceng795_amd
+    xml = str(tmp_path / "soup1_64x48.xml")
+    with open(xml, "w") as f:
+        f.write(G.soup_scene(1, 64, 48).to_xml())
+    ref, _ = oracle_frame(xml, 0)
+    pinned = torch.empty(ref.shape, dtype=torch.float32, pin_memory=True)
+    streams = [torch.cuda.Stream() for _ in range(3 if len(devices) == 1 else 2)]
+    for cycle in range(12):
+        kw = {"device": 0} if len(devices) == 1 else {"devices": devices}
+        with ceng795_amd.Scene(xml, **kw) as s:
+            got, _ = s.render_image(0, np.full(ref.shape, -1.0, np.float32))
+            assert same(got, ref), (devices, cycle, "pageable")
+            pinned.fill_(-1.0)
+            got, _ = s.render_image(0, pinned.numpy())
+            assert same(got, ref), (devices, cycle, "pinned")
+            bufs = []
+            for st in streams:
+                b = torch.full(ref.shape, -1.0, dtype=torch.float32, device="cuda")
+                st.wait_stream(torch.cuda.current_stream())
+                s.render_device(0, b.data_ptr(), stream=st.cuda_stream)
+                bufs.append(b)
+            torch.cuda.synchronize()
+            for k, b in enumerate(bufs):
+                assert same(b.cpu().numpy(), ref), (devices, cycle, k)
+            s.release_stream(streams[cycle % len(streams)].cuda_stream)

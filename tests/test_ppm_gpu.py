@@ -204,6 +204,23 @@ def test_multi_device_render_matches_oracle(ppm, scene_dir, replicas):
         assert np.array_equal(bits(img2), bits(want))
 
 
+def test_ppm_scene_churn(ppm, tmp_path):
+    """Scenes made, rendered and destroyed over and over, single-device and two replicas in
+    turn (the smoke run's Cornell box): every frame is the oracle's bit for bit."""
+    import gen_ppm_scene
+    xml = str(tmp_path / "cornell32.xml")
+    with open(xml, "w") as f:
+        f.write(gen_ppm_scene.cornell(32, 32, photons=2000, iterations=10))
+    want, ost = OraclePPM(xml).render(0, seed=1, threads=8)
+    for cycle in range(8):
+        kw = {"devices": [0, 0]} if cycle % 2 else {"device": 0}
+        with ppm.PhotonScene(xml, seed=1, **kw) as g:
+            img, st = g.render(0, reference_threads=8)
+            assert np.array_equal(bits(img), bits(want)), cycle
+            assert st.photons == ost.photons
+            g.collect_stats()
+
+
 @pytest.mark.parametrize("shards", [2, 4])
 def test_update_shards_merge_to_oracle(ppm, scene_dir, shards):
     """One process per GPU: S scenes, each applying update shard s of S, merged by hit-point
