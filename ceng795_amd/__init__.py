@@ -6,11 +6,14 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
     pixels = scene.new_image(camera_index)           # Pixel[w*h]  (fp32 RGB radiance)
     scene.render_image(camera_index, pixels, starting_row, height_increase)
     write_png(name, pixels)                          # HW2/main.cpp:43-57
+    hits = scene.trace_rays(origins, directions)     # closest hit of the caller's own rays
+    occ = scene.occluded(origins, directions, tmax)  # is the segment blocked?
 
 Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 """
-from .scene import Scene, CameraInfo, write_png  # noqa: F401
+from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, pack_rays,  # noqa: F401
+                    host_leaf_objects)
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
 __all__ = ["Scene", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_FAST",
-           "RT_TRAVERSAL_REFERENCE"]
+           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "pack_rays", "host_leaf_objects"]

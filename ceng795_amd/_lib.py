@@ -25,6 +25,8 @@ RT_E_UNSUPPORTED = -5
 RT_TRAVERSAL_FAST = 0
 RT_TRAVERSAL_REFERENCE = 1
 
+RT_QUERY_REORDER = 1  # flags of the ray queries
+
 F3 = C.c_float * 3
 
 
@@ -71,6 +73,15 @@ class rt_stats(C.Structure):
 
     def rays(self) -> int:
         return self.primary_rays + self.shadow_rays + self.secondary_rays
+
+
+class rt_ray(C.Structure):
+    _fields_ = [("o", F3), ("tmax", C.c_float), ("d", F3), ("pad", C.c_float)]
+
+
+class rt_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("object", C.c_int), ("material", C.c_int), ("leaf", C.c_int),
+                ("normal", F3), ("pad", C.c_int)]
 
 
 # name -> (restype, argtypes); mirrors include/ceng795_rt.h one to one
@@ -127,6 +138,14 @@ SIGNATURES = {
     "rt_debug_phases": (C.c_longlong, [C.POINTER(C.c_ulonglong), C.c_longlong]),
     "rt_debug_quotient_check": (C.c_int, [C.c_int, C.c_ulonglong, C.c_longlong,
                                           C.POINTER(C.c_longlong)]),
+    "rt_ray_query_version": (C.c_int, []),
+    "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
+                                       C.c_void_p]),
+    "rt_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
+                                     C.c_void_p]),
+    "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]),
+    "rt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]),
+    "rt_host_leaf_objects_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_int), C.c_int]),
 }
 
 _lib = None

@@ -16,6 +16,8 @@ struct LeafSource {  // what the leaf was in the reference object list (for BVH 
   int i0, i1, i2;    // triangle vertex ids (0-based)
   float center[3], radius;
   int material;
+  int object;        // index in the object lists: triangles (mesh faces in mesh order, then loose
+                     // triangles), then spheres — rt_scene_desc::bvh_leaf_object's numbering
 };
 
 struct HostScene {
@@ -33,6 +35,7 @@ struct HostScene {
   std::vector<DevPrim> prims;
   std::vector<float> normals;  // 4 per leaf
   std::vector<LeafSource> leaf_src;
+  std::vector<int> leaf_object;  // per DFS leaf: leaf_src[leaf].object (uploaded for ray queries)
   int root_kind = kRootNode;
   int root_ref = 0;
   float root_box[6] = {0, 0, 0, 0, 0, 0};

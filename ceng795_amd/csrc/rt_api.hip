@@ -41,6 +41,8 @@ bool diag_build();
 long long read_reset_timeline(unsigned long long* out, long long max_values);
 long long read_reset_phases(unsigned long long* out, long long max_values);
 int launch_cold_order(RenderParams P, hipStream_t stream);
+hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
+                        bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream);
 void write_png(const std::string& path, const float* rgb, int w, int h);
 }  // namespace rt
 
@@ -87,6 +89,10 @@ struct RenderCtx {
   // and one event per row chunk (created on first use)
   Stream copy_stream;
   Event ev_chunk[kRenderChunks];
+  // rt_trace_rays / rt_occluded: the uploaded rays, the results, the reorder stage's scratch
+  DevBuf<rt_ray> d_rays;
+  DevBuf<rt_ray_hit> d_ray_out;  // (or n bytes of occlusion flags)
+  DevBuf<unsigned> d_query;
 };
 
 // rt_render_device scratch of one stream (hit records, occlusion bits, tile schedule, ray-tree
@@ -98,6 +104,7 @@ struct StreamScratch {
   DevBuf<int2_t> hits;
   DevBuf<unsigned> occ, sched;
   DevBuf<float> frames, samples;
+  DevBuf<unsigned> query;  // ray queries with RT_QUERY_REORDER: permutation, histogram, totals
   // warm order: the selection whose heavy-first unit order the last frame on this stream left
   // in `sched` (valid: that frame ran the order kernel)
   std::array<long long, 7> order_key{};
@@ -135,6 +142,7 @@ struct Replica {
   DevBuf<DevAncestry> d_anc;
   DevBuf<DevMaterial> d_mats;
   DevBuf<DevLight> d_lights;
+  DevBuf<int> d_leaf_object;  // per DFS leaf: its object index (rt_ray_hit::object)
   DevBuf<unsigned long long> d_counters;
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
   // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
@@ -380,6 +388,7 @@ void upload_replica(const rt_scene* s, Replica& r) {
   r.d_anc = upload(h.ancestry, "upload ancestry", kPad);
   r.d_mats = upload(h.materials, "upload materials", kPad);
   r.d_lights = upload(h.lights, "upload lights", kPad);
+  r.d_leaf_object = upload(h.leaf_object, "upload leaf objects", 0);
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
@@ -453,11 +462,9 @@ TilePlan plan(const rt_camera& c, int row0, int row_stride) {
   return p;
 }
 
-RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0, int row_stride,
-                         int tile_begin, int tile_step, int tile_major, float* out,
-                         unsigned long long* counters) {
+// The scene's part of the kernel parameters (no camera, no outputs): what a ray query needs.
+RenderParams scene_params(const rt_scene* s, const Replica& r) {
   const HostScene& h = s->host;
-  const rt_camera& c = h.cameras[cam];
   RenderParams P;
   std::memset(&P, 0, sizeof P);
   P.nodes = r.d_nodes.p;
@@ -478,6 +485,15 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
   P.quot_ok = h.quot_ok;
   std::memcpy(P.accel_box, h.accel_box, sizeof P.accel_box);
   P.anc = r.d_anc.p;
+  P.occ_words = occ_words(h);
+  return P;
+}
+
+RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0, int row_stride,
+                         int tile_begin, int tile_step, int tile_major, float* out,
+                         unsigned long long* counters) {
+  const rt_camera& c = s->host.cameras[cam];
+  RenderParams P = scene_params(s, r);
   std::memcpy(P.cam_e, c.e, 12);
   std::memcpy(P.cam_tl, c.top_left, 12);
   std::memcpy(P.cam_su, c.s_u, 12);
@@ -499,7 +515,6 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
   P.tile_major = tile_major & RT_TILE_MAJOR;
   P.records = (tile_major & RT_TILE_RECORDS) ? 1 : 0;
   P.out = out;
-  P.occ_words = occ_words(h);
   P.counters = counters;
   if (row0 == 0 && row_stride == 1 && tile_begin == 0 && tile_step == 1 && !P.block_deal &&
       cam < (int)r.d_cold.size() && r.d_cold[cam].p) {  // the whole frame: its cold order
@@ -1033,6 +1048,96 @@ std::vector<int> single_device(int device) {
   return {device};
 }
 
+// Argument rules shared by the four ray-query entries; they need no GPU.
+void check_query_args(const char* fn, const rt_scene* s, const void* rays, long long n,
+                      const void* out, bool out_aligned, int flags) {
+  const std::string f(fn);
+  if (n < 0) throw std::invalid_argument(f + ": n < 0");
+  if (flags & ~RT_QUERY_REORDER) throw std::invalid_argument(f + ": unknown flag bit");
+  if (n > 0 && (!rays || !out)) throw std::invalid_argument(f + ": NULL pointer");
+  if ((uintptr_t)rays % 16 != 0 || (out_aligned && (uintptr_t)out % 16 != 0))
+    throw std::invalid_argument(f + ": rays and hits must be 16-byte aligned");
+  if (!s) throw std::invalid_argument(f + ": scene is NULL");
+  if (s->multi) throw std::domain_error(f + ": ray queries on multi-device scenes are not supported");
+}
+
+// Enqueues the query over d_rays[0, n) on `stream`, at most kQueryMaxLaunch rays per launch;
+// `scratch` (the stream's or the context's) holds the reorder stage's buffers.
+void enqueue_query(rt_scene* s, const Replica& r, const rt_ray* d_rays, long long n, void* d_out,
+                   bool occlusion, int flags, DevBuf<unsigned>& scratch, hipStream_t stream) {
+  const HostScene& h = s->host;
+  const RenderParams P = scene_params(s, r);
+  const bool reorder = (flags & RT_QUERY_REORDER) != 0;
+  QueryParams Q;
+  std::memset(&Q, 0, sizeof Q);
+  Q.leaf_object = r.d_leaf_object.p;
+  if (h.root_kind == kRootNode)  // (a root primitive: one origin cell)
+    for (int a = 0; a < 3; a++) {
+      const float ext = h.root_box[a + 3] - h.root_box[a];
+      Q.box_lo[a] = h.root_box[a];
+      Q.box_scale[a] = ext > 0.0f && std::isfinite(ext) ? 1.0f / ext : 0.0f;  // cells: kernel
+    }
+  if (reorder) scratch.reserve(query_scratch_words(std::min(n, kQueryMaxLaunch)), "alloc query scratch");
+  const size_t out_stride = occlusion ? 1 : sizeof(rt_ray_hit);
+  for (long long done = 0; done < n; done += kQueryMaxLaunch) {
+    Q.rays = d_rays + done;
+    Q.out = static_cast<char*>(d_out) + (size_t)done * out_stride;
+    Q.n = std::min(n - done, kQueryMaxLaunch);
+    if (reorder) {
+      Q.perm_out = reinterpret_cast<int*>(scratch.p);
+      Q.hist = scratch.p + Q.n;
+      Q.totals = Q.hist + (size_t(1) << query_bin_bits(Q.n));
+    }
+    hip_check(launch_query(P, Q, r.d_nodes.p, occlusion, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
+                           s->deep, s->has_spheres, stream),
+              "query launch");
+  }
+}
+
+int query_device(const char* fn, rt_scene* s, const rt_ray* d_rays, long long n, void* d_out,
+                 bool occlusion, int flags, void* stream) {
+  return guarded([&] {
+    check_query_args(fn, s, d_rays, n, d_out, !occlusion, flags);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    std::unique_lock<std::mutex> lk;
+    StreamScratch* sc = scratch_for(s, r, stream, lk);
+    enqueue_query(s, r, d_rays, n, d_out, occlusion, flags, sc->query, (hipStream_t)stream);
+    hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
+    return RT_OK;
+  });
+}
+
+int query_host(const char* fn, rt_scene* s, const rt_ray* rays, long long n, void* out,
+               bool occlusion, int flags) {
+  return guarded([&] {
+    check_query_args(fn, s, rays, n, out, !occlusion, flags);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    struct Lease {  // a pooled context, handed back on every path
+      Replica& r;
+      RenderCtx* x;
+      ~Lease() {
+        (void)hipStreamSynchronize(x->stream);
+        release_ctx(r, x);
+      }
+    } lease{r, acquire_ctx(r)};
+    RenderCtx* x = lease.x;
+    const size_t out_bytes = occlusion ? (size_t)n : (size_t)n * sizeof(rt_ray_hit);
+    x->d_rays.reserve((size_t)n, "alloc rays");
+    x->d_ray_out.reserve((out_bytes + sizeof(rt_ray_hit) - 1) / sizeof(rt_ray_hit), "alloc results");
+    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
+                             x->stream), "upload rays");
+    enqueue_query(s, r, x->d_rays.p, n, x->d_ray_out.p, occlusion, flags, x->d_query, x->stream);
+    hip_check(hipMemcpyAsync(out, x->d_ray_out.p, out_bytes, hipMemcpyDeviceToHost, x->stream),
+              "download results");
+    hip_check(hipStreamSynchronize(x->stream), "synchronize query");
+    return RT_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1360,6 +1465,38 @@ int rt_resolve_rows(rt_scene* s, int cam, int row_begin, int row_end, const unsi
     hip_check(launch_resolve_rows(P, d_records, row_begin, row_end, s->has_spheres,
                                   (hipStream_t)stream), "resolve launch");
     return RT_OK;
+  });
+}
+
+int rt_ray_query_version(void) { return 1; }
+
+int rt_trace_rays_device(rt_scene* s, const rt_ray* d_rays, long long n, rt_ray_hit* d_hits,
+                         int flags, void* stream) {
+  return query_device("rt_trace_rays_device", s, d_rays, n, d_hits, false, flags, stream);
+}
+
+int rt_occluded_device(rt_scene* s, const rt_ray* d_rays, long long n, unsigned char* d_occ,
+                       int flags, void* stream) {
+  return query_device("rt_occluded_device", s, d_rays, n, d_occ, true, flags, stream);
+}
+
+int rt_trace_rays(rt_scene* s, const rt_ray* rays, long long n, rt_ray_hit* hits, int flags) {
+  return query_host("rt_trace_rays", s, rays, n, hits, false, flags);
+}
+
+int rt_occluded(rt_scene* s, const rt_ray* rays, long long n, unsigned char* occ, int flags) {
+  return query_host("rt_occluded", s, rays, n, occ, true, flags);
+}
+
+int rt_host_leaf_objects_desc(const rt_scene_desc* desc, int* out, int capacity) {
+  if (!desc || capacity < 0 || (capacity > 0 && !out))
+    return set_error(RT_E_INVALID, "rt_host_leaf_objects_desc: bad argument");
+  return guarded([&] {
+    HostScene h;
+    build_host_scene(*desc, h);
+    const int leaves = (int)h.leaf_object.size();
+    std::copy_n(h.leaf_object.begin(), std::min(leaves, capacity), out);
+    return leaves;
   });
 }
 

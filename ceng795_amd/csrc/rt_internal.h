@@ -311,6 +311,48 @@ struct RenderParams {
   unsigned long long* counters;
 };
 
+// Ray queries (rt_trace_rays_device / rt_occluded_device): one launch over rays
+// [0, n) of `rays` (rt_ray, two 16-B words each).  Wave w traces rays perm[64 w .. 64 w + 63]
+// (perm == nullptr: the identity) and writes result slot perm[i]: an rt_ray_hit (closest hit) or
+// one byte (occlusion).
+// The reorder key (rt_kernels.hip query_key): 3 bits of cube face, kQueryOriginBits per axis of
+// origin cell, kQueryDirBits per face axis of direction — 20 bits, at most 2^20 bins.
+#ifndef RT_QUERY_ORIGIN_BITS  // (A/B builds: 2 = a 4x4x4 origin grid and 64x64 direction cells)
+#define RT_QUERY_ORIGIN_BITS 1
+#endif
+constexpr int kQueryOriginBits = RT_QUERY_ORIGIN_BITS;
+constexpr int kQueryDirBits = (18 - 3 * kQueryOriginBits) / 2;
+constexpr int kQueryKeyBits = 3 + 3 * kQueryOriginBits + 2 * kQueryDirBits;
+static_assert(kQueryOriginBits >= 1 && kQueryDirBits >= 1 && kQueryDirBits <= 8 &&
+              kQueryKeyBits <= 21, "reorder key layout");
+constexpr int kQueryMinBinBits = 11;  // ... and at least one scan chunk
+constexpr int kQueryScanChunk = 1 << kQueryMinBinBits;  // bins one scan workgroup takes
+constexpr long long kQueryMaxLaunch = 1ll << 28;        // rays per launch (32-bit perm entries)
+struct QueryParams {
+  const void* rays;
+  void* out;
+  const int* perm;
+  const int* leaf_object;  // per DFS leaf: its index in the object lists
+  long long n;
+  // RT_QUERY_REORDER: the key's origin cell = (o - box_lo) * box_scale (0..1 across the scene
+  // box) times the cells per axis, clamped; `bins` = 2^(kQueryKeyBits - shift) counters in
+  // hist, one total per scan chunk in totals
+  float box_lo[3], box_scale[3];
+  int shift, bins;
+  unsigned* hist;
+  unsigned* totals;
+  int* perm_out;
+};
+// words of reorder scratch for a launch of n rays: perm, then hist, then totals
+constexpr int query_bin_bits(long long n) {
+  int b = kQueryMinBinBits;
+  while (b < kQueryKeyBits && (1ll << b) < n) b++;
+  return b;
+}
+constexpr size_t query_scratch_words(long long n) {
+  return (size_t)n + (size_t(1) << query_bin_bits(n)) + (size_t(1) << (kQueryKeyBits - kQueryMinBinBits));
+}
+
 }  // namespace rt
 
 #endif

@@ -2197,6 +2197,327 @@ hipError_t launch_resolve(const RenderParams& P, const UntileParams& U, bool sph
 
 int max_supported_depth() { return kDeepStack; }
 
+// ------------------------------------------------------------------ ray queries
+// Caller-supplied rays (rt_trace_rays_device / rt_occluded_device): one lane per
+// ray, 64 consecutive rays of the order in use per wave, through the same closest_hit / occluded
+// as the frame kernels.  A ray with a non-finite component, or with every |d_i| < 1e-6 (the
+// reference's rule would skip all three axes and test every leaf), is INVALID: its lane stays
+// inactive and reports a miss / not occluded.
+struct QueryRay {
+  V3 o, d;
+  float tmax;
+  bool in;     // i < n: the lane has a result slot
+  bool valid;  // ... and a ray to trace
+};
+
+__device__ __forceinline__ bool finite3(V3 a) {  // (a NaN fails the compares)
+  return (__builtin_fabsf(a.x) < RT_INF) & (__builtin_fabsf(a.y) < RT_INF) &
+         (__builtin_fabsf(a.z) < RT_INF);
+}
+__device__ __forceinline__ bool query_ray_ok(V3 o, V3 d) {
+  const bool tiny = (__builtin_fabsf(d.x) < kEps) & (__builtin_fabsf(d.y) < kEps) &
+                    (__builtin_fabsf(d.z) < kEps);
+  return finite3(o) && finite3(d) && !tiny;
+}
+
+// Ray index of this lane, and its result slot (perm[i], or i).
+__device__ __forceinline__ long long query_index() {
+  return (long long)blockIdx.x * (kWavesPerBlock * 64) + threadIdx.x;
+}
+__device__ __forceinline__ long long query_slot(const QueryParams& Q, long long i) {
+  return Q.perm ? (long long)Q.perm[i] : i;
+}
+
+__device__ __forceinline__ QueryRay load_query_ray(const QueryParams& Q, long long i) {
+  QueryRay q;
+  q.in = i < Q.n;
+  f4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 1.0f, 0.0f};
+  if (q.in) {
+    const f4* p = reinterpret_cast<const f4*>(Q.rays) + 2 * query_slot(Q, i);
+    a = p[0];
+    b = p[1];
+  }
+  q.o = v3(a.x, a.y, a.z);
+  q.d = v3(b.x, b.y, b.z);
+  q.tmax = a.w;
+  q.valid = q.in && query_ray_ok(q.o, q.d);
+  if (!q.valid) {  // an idle lane still takes part in the wave-wide steps: a harmless ray
+    q.o = v3(0.0f, 0.0f, 0.0f);
+    q.d = v3(0.0f, 0.0f, 1.0f);
+  }
+  return q;
+}
+
+template <bool FAST, bool DEEP, bool SPHERES>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void query_closest_kernel(
+    RenderParams P, QueryParams Q, const DevNode* __restrict__ nodes) {
+  extern __shared__ __attribute__((aligned(16))) int deep_stack[];
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, P.quot_ok);
+  const bool any_skip = q.valid && (ray.skip0 || ray.skip1 || ray.skip2);
+  Diag dg;
+  float t;
+  int leaf;
+  if (ballot(any_skip))
+    closest_hit<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+  else
+    closest_hit<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+  f4 h0 = {RT_INF, __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)};
+  f4 h1 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (q.valid && leaf >= 0) {
+    const DevPrim& pr = P.prims[leaf];
+    // Hit_data::normal: the flat normal (Triangle.cpp:14), or Sphere.h:42,50's
+    // (ray.point_at(t) - center).normalize()
+    const V3 n = !SPHERES || pr.kind == kPrimTriangle
+                     ? ld3(P.normals + 4 * leaf)
+                     : normalize((ray.o + ray.d * t) - ld3(pr.v0));
+    h0 = (f4){t, __int_as_float(Q.leaf_object[leaf]), __int_as_float(pr.material),
+              __int_as_float(leaf)};
+    h1 = (f4){n.x, n.y, n.z, 0.0f};
+  }
+  const long long i = query_index();
+  if (i < Q.n) {
+    f4* out = reinterpret_cast<f4*>(Q.out) + 2 * query_slot(Q, i);
+    out[0] = h0;
+    out[1] = h1;
+  }
+}
+
+template <bool FAST, bool DEEP, bool SPHERES>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void query_occluded_kernel(
+    RenderParams P, QueryParams Q, const DevNode* __restrict__ nodes) {
+  extern __shared__ __attribute__((aligned(16))) int deep_stack[];
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;
+  int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, P.quot_ok);
+  const bool any_skip = q.valid && (ray.skip0 || ray.skip1 || ray.skip2);
+  Diag dg;
+  // 0 < t < tmax; tmax <= 0 or NaN: never (occluded's own `thr > 0` test)
+  const bool occ =
+      ballot(any_skip)
+          ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, q.tmax, dg)
+          : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, q.tmax, dg);
+  const long long i = query_index();
+  if (i < Q.n)
+    reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
+}
+
+// RT_QUERY_REORDER: a permutation that brings similar rays into the same wave (64 unrelated rays
+// walk the union of 64 paths).  Key, most significant first: the dominant axis and sign of d (6
+// cube faces), the origin's cell in a 2x2x2 grid over the clamped scene box, and the direction's
+// position on its cube face, 128 x 128 cells in Morton order (kQueryOriginBits / kQueryDirBits
+// bits per axis, rt_internal.h; measured against 4x4x4 and 64 x 64 in DESIGN.md §4.11); small
+// batches drop the low bits
+// (Q.shift).  Invalid rays share the last bin (face 7, which no direction has).  One counting
+// sort: histogram by atomics, exclusive scan (per chunk of kQueryScanChunk bins, then over the
+// chunk totals), scatter through the bins' counters as atomic cursors.  Not stable: results do
+// not depend on the order.
+__device__ __forceinline__ unsigned spread8(unsigned x) {  // bits 0..7 -> the even bits 0..14
+  x = (x | (x << 4)) & 0x0f0fu;
+  x = (x | (x << 2)) & 0x3333u;
+  x = (x | (x << 1)) & 0x5555u;
+  return x;
+}
+
+__device__ __forceinline__ int cell_of(float x, float cells) {  // clamped, NaN -> 0
+  return (int)__builtin_fminf(__builtin_fmaxf(x, 0.0f), cells - 1.0f);
+}
+
+__device__ __forceinline__ unsigned query_key(const QueryParams& Q, long long i) {
+  const f4* p = reinterpret_cast<const f4*>(Q.rays) + 2 * i;
+  const f4 a = p[0], b = p[1];
+  const V3 o = v3(a.x, a.y, a.z), d = v3(b.x, b.y, b.z);
+  if (!query_ray_ok(o, d)) return (unsigned)Q.bins - 1u;
+  const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+  int axis = 0;
+  float dm = d.x, du = d.y, dv = d.z;
+  if (ay > ax && ay >= az) {
+    axis = 1;
+    dm = d.y, du = d.z, dv = d.x;
+  } else if (az > ax && az > ay) {
+    axis = 2;
+    dm = d.z, du = d.x, dv = d.y;
+  }
+  const unsigned face = 2u * (unsigned)axis + (dm < 0.0f ? 1u : 0u);
+  constexpr float kDirCells = (float)(1 << kQueryDirBits), kCells = (float)(1 << kQueryOriginBits);
+  const float inv = 0.5f * kDirCells / __builtin_fabsf(dm);  // |du|, |dv| <= |dm|
+  const unsigned u = (unsigned)cell_of(du * inv + 0.5f * kDirCells, kDirCells);
+  const unsigned v = (unsigned)cell_of(dv * inv + 0.5f * kDirCells, kDirCells);
+  const unsigned cx = (unsigned)cell_of((o.x - Q.box_lo[0]) * Q.box_scale[0] * kCells, kCells);
+  const unsigned cy = (unsigned)cell_of((o.y - Q.box_lo[1]) * Q.box_scale[1] * kCells, kCells);
+  const unsigned cz = (unsigned)cell_of((o.z - Q.box_lo[2]) * Q.box_scale[2] * kCells, kCells);
+  const unsigned cell = (cz << (2 * kQueryOriginBits)) | (cy << kQueryOriginBits) | cx;
+  const unsigned key = (face << (kQueryKeyBits - 3)) | (cell << (2 * kQueryDirBits)) |
+                       (spread8(v) << 1) | spread8(u);
+  return key >> Q.shift;
+}
+
+constexpr int kQueryThreads = 256;
+
+// counter[key] += 1 for every active lane; returns what the lane's own atomicAdd(&counter[key], 1)
+// would have (POS; its position in the bin when the counters are cursors).  Neighbouring rays
+// of an ordered batch share a bin, and 64 atomics on one address serialise (first measurement:
+// sorting an ordered C3 batch took twice as long as a shuffled one), so the lanes holding one of
+// the wave's first kQueryAggregate distinct keys go through one atomic per key, ranked in lane
+// order; the others (a shuffled batch: 64 different bins) add for themselves.  Every lane of
+// the wave takes part.
+constexpr int kQueryAggregate = 4;
+template <bool POS>
+__device__ __forceinline__ unsigned wave_count(unsigned* counter, unsigned key, bool active) {
+  const int lane = lane_id();
+  uint64_t todo = ballot(active);
+  int head = lane;          // the lane whose atomic covers this one (itself: on its own)
+  unsigned rank = 0, count = 1;
+  for (int it = 0; it < kQueryAggregate && todo; it++) {
+    const int leader = __builtin_ctzll(todo);
+    const unsigned k = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
+    const uint64_t same = ballot(active && key == k) & todo;
+    if ((same >> lane) & 1) {
+      head = leader;
+      rank = __builtin_amdgcn_mbcnt_hi((unsigned)(same >> 32),
+                                       __builtin_amdgcn_mbcnt_lo((unsigned)same, 0u));
+      count = (unsigned)__builtin_popcountll(same);
+    }
+    todo &= ~same;
+  }
+  // one atomic per lane at most, all in flight together
+  unsigned base = 0;
+  if (active && head == lane) {
+    if (POS)
+      base = atomicAdd(&counter[key], count);
+    else
+      atomicAdd(&counter[key], count);
+  }
+  if (!POS) return 0;
+  return (unsigned)__builtin_amdgcn_ds_bpermute(head << 2, (int)base) + rank;
+}
+
+__global__ __launch_bounds__(kQueryThreads) void query_hist_kernel(QueryParams Q) {
+  const long long i = (long long)blockIdx.x * kQueryThreads + threadIdx.x;
+  const bool active = i < Q.n;
+  wave_count<false>(Q.hist, active ? query_key(Q, i) : 0u, active);
+}
+
+// Exclusive scan of v over the workgroup's T threads (T a power of two); total = the sum.
+template <int T>
+__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* lds, unsigned& total) {
+  const int tid = (int)threadIdx.x;
+  lds[tid] = v;
+  __syncthreads();
+  for (int off = 1; off < T; off <<= 1) {
+    const unsigned x = tid >= off ? lds[tid - off] : 0u;
+    __syncthreads();
+    lds[tid] += x;
+    __syncthreads();
+  }
+  total = lds[T - 1];
+  return lds[tid] - v;
+}
+
+// Each workgroup turns its chunk of kQueryScanChunk counters into exclusive prefix sums within
+// the chunk and writes the chunk's total.
+__global__ __launch_bounds__(kQueryThreads) void query_scan_chunks_kernel(QueryParams Q) {
+  constexpr int kPer = kQueryScanChunk / kQueryThreads;
+  __shared__ unsigned lds[kQueryThreads];
+  unsigned* h = Q.hist + (size_t)blockIdx.x * kQueryScanChunk + threadIdx.x * kPer;
+  unsigned c[kPer], sum = 0;
+#pragma unroll
+  for (int k = 0; k < kPer; k++) {
+    c[k] = h[k];
+    sum += c[k];
+  }
+  unsigned total;
+  unsigned run = block_scan<kQueryThreads>(sum, lds, total);
+#pragma unroll
+  for (int k = 0; k < kPer; k++) {
+    h[k] = run;
+    run += c[k];
+  }
+  if (threadIdx.x == 0) Q.totals[blockIdx.x] = total;
+}
+
+// The chunk totals (at most 2^(kQueryKeyBits - kQueryMinBinBits) <= 1024) into exclusive sums.
+constexpr int kQueryMaxChunks = 1 << (kQueryKeyBits - kQueryMinBinBits);
+__global__ __launch_bounds__(kQueryMaxChunks) void query_scan_totals_kernel(QueryParams Q) {
+  __shared__ unsigned lds[kQueryMaxChunks];
+  const int chunks = Q.bins / kQueryScanChunk;
+  const unsigned v = (int)threadIdx.x < chunks ? Q.totals[threadIdx.x] : 0u;
+  unsigned total;
+  const unsigned e = block_scan<kQueryMaxChunks>(v, lds, total);
+  if ((int)threadIdx.x < chunks) Q.totals[threadIdx.x] = e;
+}
+
+__global__ __launch_bounds__(kQueryThreads) void query_scatter_kernel(QueryParams Q) {
+  const long long i = (long long)blockIdx.x * kQueryThreads + threadIdx.x;
+  const bool active = i < Q.n;
+  const unsigned key = active ? query_key(Q, i) : 0u;
+  // the bin's counter holds its start within the chunk and serves as its cursor; the counts sum
+  // to n, so every position is below n
+  const unsigned at = wave_count<true>(Q.hist, key, active);
+  if (active) Q.perm_out[at + Q.totals[key >> kQueryMinBinBits]] = (int)i;
+}
+
+template <bool FAST, bool DEEP, bool SPHERES>
+static void launch_query_variant(const RenderParams& P, const QueryParams& Q, const DevNode* nodes,
+                                 bool occlusion, hipStream_t stream) {
+  const size_t lds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kWavesPerBlock : 0;
+  const dim3 grid((unsigned)((Q.n + kWavesPerBlock * 64 - 1) / (kWavesPerBlock * 64)));
+  if (occlusion)
+    hipLaunchKernelGGL((query_occluded_kernel<FAST, DEEP, SPHERES>), grid,
+                       dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes);
+  else
+    hipLaunchKernelGGL((query_closest_kernel<FAST, DEEP, SPHERES>), grid,
+                       dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes);
+}
+
+// One query launch over Q.n rays (0 < n <= kQueryMaxLaunch); reorder: Q's hist / totals /
+// perm_out point at query_scratch_words(n) words of scratch.  The variant is picked as
+// launch_render picks the frame kernels'.
+hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
+                        bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream) {
+  if (Q.n <= 0) return hipSuccess;
+  Q.perm = nullptr;
+  if (reorder) {
+    const int bits = query_bin_bits(Q.n);
+    Q.shift = kQueryKeyBits - bits;
+    Q.bins = 1 << bits;
+    const hipError_t e = hipMemsetAsync(Q.hist, 0, sizeof(unsigned) * (size_t)Q.bins, stream);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((Q.n + kQueryThreads - 1) / kQueryThreads));
+    hipLaunchKernelGGL(query_hist_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
+    hipLaunchKernelGGL(query_scan_chunks_kernel, dim3(Q.bins / kQueryScanChunk),
+                       dim3(kQueryThreads), 0, stream, Q);
+    hipLaunchKernelGGL(query_scan_totals_kernel, dim3(1), dim3(kQueryMaxChunks), 0, stream, Q);
+    hipLaunchKernelGGL(query_scatter_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
+    Q.perm = Q.perm_out;
+  }
+  fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
+  const int v = (fast ? 4 : 0) | (deep ? 2 : 0) | (spheres ? 1 : 0);
+  switch (v) {
+#define RT_CASE(F, D, S)                                              \
+  case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                       \
+    launch_query_variant<F, D, S>(P, Q, nodes, occlusion, stream);    \
+    break;
+    RT_CASE(true, false, false)
+    RT_CASE(true, false, true)
+    RT_CASE(true, true, false)
+    RT_CASE(true, true, true)
+    RT_CASE(false, false, false)
+    RT_CASE(false, false, true)
+    RT_CASE(false, true, false)
+    RT_CASE(false, true, true)
+#undef RT_CASE
+  }
+  return hipGetLastError();
+}
+
 // Self-check of tri_quotients against `/` on random operands spanning the whole fast range:
 // |det| in [2^-40, 2^40] (a quarter with all-ones mantissas, where a reciprocal is hardest),
 // numerators 0 or in [2^-49, 2^49], a quarter of them chosen so the quotient sits next to a

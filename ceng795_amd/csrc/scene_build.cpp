@@ -264,6 +264,7 @@ int append_leaf(HostScene& s, const LeafSource& ls, F3 n, Vtx vtx) {
   std::memcpy(&mat_f, &mat_bits, 4);
   s.normals.insert(s.normals.end(), {n.x, n.y, n.z, mat_f});
   s.leaf_src.push_back(ls);
+  s.leaf_object.push_back(ls.object);
   return index;
 }
 
@@ -290,7 +291,7 @@ void adopt_tree(const rt_scene_desc& d, HostScene& s, const std::vector<LeafSour
     F3 n = normals[o];
     if (d.bvh_leaf_normals && objects[o].kind == kPrimTriangle)
       n = {d.bvh_leaf_normals[3 * k], d.bvh_leaf_normals[3 * k + 1], d.bvh_leaf_normals[3 * k + 2]};
-    append_leaf(s, objects[o], n, vtx);
+    append_leaf(s, objects[o], n, vtx);  // (objects[o].object == o)
   }
   if (nn == 0) {  // the root is the one primitive (BVH::create_bvh, .h:13-14)
     s.root_kind = s.prims[0].kind == kPrimTriangle ? kRootTriangle : kRootSphere;
@@ -400,6 +401,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
       ls.i1 = i1;
       ls.i2 = i2;
       ls.material = mat;
+      ls.object = (int)objects.size();
       objects.push_back(ls);
       normals.push_back(unit(cross(v1 - v0, v2 - v0)));  // Triangle.cpp:14
     };
@@ -427,6 +429,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
       ls.center[2] = c.z;
       ls.radius = d.sphere_radius[k];
       ls.material = d.sphere_material[k];
+      ls.object = (int)objects.size();
       objects.push_back(ls);
       normals.push_back({0, 0, 0});
     }
@@ -434,6 +437,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
     s.prims.clear();
     s.normals.clear();
     s.leaf_src.clear();
+    s.leaf_object.clear();
     s.quot_ok = 1;
     adopt_tree(d, s, objects, normals, vtx);
     return;
@@ -453,6 +457,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
     ls.i1 = i1;
     ls.i2 = i2;
     ls.material = mat;
+    ls.object = (int)B.leaves.size();  // B.leaves is in object-list order
     B.leaves.push_back(ls);
     B.normals.push_back(unit(cross(v1 - v0, v2 - v0)));
     B.objs.push_back(o);
@@ -499,6 +504,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
     ls.center[2] = c.z;
     ls.radius = r;
     ls.material = d.sphere_material[k];
+    ls.object = (int)B.leaves.size();
     B.leaves.push_back(ls);
     B.normals.push_back({0, 0, 0});
     B.objs.push_back(o);
@@ -513,6 +519,7 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
   s.prims.clear();
   s.normals.clear();
   s.leaf_src.clear();
+  s.leaf_object.clear();
   s.quot_ok = 1;
   auto resolve = [&](int id) {
     while (B.objs[id].kind == kObjMesh) id = B.objs[id].a;

@@ -14,6 +14,33 @@ from ._lib import check, lib
 RT_TILE_MAJOR, RT_TILE_BLOCKS, RT_TILE_RECORDS = 1, 2, 4
 RT_UNTILE_BLOCKS, RT_UNTILE_SKIP_ROOT = 1, 2  # rt_untile_device flags
 
+# rt_ray / rt_ray_hit (include/ceng795_rt.h), 32 bytes each
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3),
+                      ("pad", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("material", np.int32),
+                      ("leaf", np.int32), ("normal", np.float32, 3), ("pad", np.int32)])
+
+
+def _aligned(n: int, dtype) -> np.ndarray:
+    """n zeroed records of `dtype` at a 16-byte aligned address (the queries' pointer rule)."""
+    dtype = np.dtype(dtype)
+    raw = np.zeros(n * dtype.itemsize + 16, np.uint8)
+    off = -raw.ctypes.data % 16
+    return raw[off:off + n * dtype.itemsize].view(dtype)
+
+
+def pack_rays(origins, directions, tmax=None) -> np.ndarray:
+    """(n, 3) origins and directions (and per-ray tmax) as a 16-byte aligned RAY_DTYPE array."""
+    o = np.asarray(origins, np.float32)
+    d = np.asarray(directions, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be (n, 3) arrays")
+    rays = _aligned(len(o), RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    if tmax is not None:
+        rays["tmax"] = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
+    return rays
+
 
 @dataclass
 class CameraInfo:
@@ -197,6 +224,42 @@ class Scene:
                                       flags, C.c_void_p(gathered_ptr), C.c_void_p(out_ptr),
                                       C.c_void_p(stream)))
 
+    # ------------------------------------------------------------------ ray queries
+    def trace_rays(self, origins, directions, *, reorder: bool = False) -> np.ndarray:
+        """Closest hit of each ray o + t d (rt_trace_rays): a HIT_DTYPE array with the
+        reference's Hit_data::t and normal, the object / material / DFS leaf hit; a miss has
+        t = +inf and object = material = leaf = -1.  ``reorder``: group similar rays before
+        tracing (RT_QUERY_REORDER; same results)."""
+        rays = pack_rays(origins, directions)
+        hits = _aligned(len(rays), HIT_DTYPE)
+        check(lib().rt_trace_rays(self._h, rays.ctypes.data, len(rays), hits.ctypes.data,
+                                  _lib.RT_QUERY_REORDER if reorder else 0))
+        return hits
+
+    def occluded(self, origins, directions, tmax, *, reorder: bool = False) -> np.ndarray:
+        """uint8[n]: 1 where something lies at 0 < t < tmax along the ray (rt_occluded)."""
+        rays = pack_rays(origins, directions, tmax)
+        occ = np.zeros(len(rays), np.uint8)
+        check(lib().rt_occluded(self._h, rays.ctypes.data, len(rays), occ.ctypes.data,
+                                _lib.RT_QUERY_REORDER if reorder else 0))
+        return occ
+
+    def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, *, reorder: bool = False,
+                          stream: int = 0) -> None:
+        """rt_trace_rays_device: n rt_ray records in device memory at ``rays_ptr`` (e.g. a torch
+        tensor's ``data_ptr()``) to n rt_ray_hit records at ``hits_ptr``, asynchronously on HIP
+        stream ``stream``."""
+        check(lib().rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), n, C.c_void_p(hits_ptr),
+                                         _lib.RT_QUERY_REORDER if reorder else 0,
+                                         C.c_void_p(stream)))
+
+    def occluded_device(self, rays_ptr: int, n: int, occ_ptr: int, *, reorder: bool = False,
+                        stream: int = 0) -> None:
+        """rt_occluded_device: one byte (0 / 1) per ray at ``occ_ptr``."""
+        check(lib().rt_occluded_device(self._h, C.c_void_p(rays_ptr), n, C.c_void_p(occ_ptr),
+                                       _lib.RT_QUERY_REORDER if reorder else 0,
+                                       C.c_void_p(stream)))
+
     def release_stream(self, stream: int) -> None:
         """Frees the scratch the library keeps for HIP stream ``stream`` (after waiting for it)."""
         check(lib().rt_release_stream_scratch(self._h, C.c_void_p(stream)))
@@ -242,3 +305,12 @@ def write_png(path: str, rgb: np.ndarray) -> None:
 def host_dump_bvh(xml_path: str, out_path: str) -> None:
     """Host-only: parse + build + flatten the BVH and dump it (no GPU needed)."""
     check(lib().rt_host_dump_bvh_xml(str(xml_path).encode(), str(out_path).encode()))
+
+
+def host_leaf_objects(desc) -> np.ndarray:
+    """Host-only (rt_host_leaf_objects_desc): for each DFS leaf of the tree of ``desc`` (an
+    ``rt_scene_desc``) its index in the object lists, the ``object`` a ray query reports."""
+    n = check(lib().rt_host_leaf_objects_desc(C.byref(desc), None, 0))
+    out = np.zeros(n, np.int32)
+    check(lib().rt_host_leaf_objects_desc(C.byref(desc), out.ctypes.data_as(C.POINTER(C.c_int)), n))
+    return out

@@ -355,6 +355,72 @@ long long rt_debug_phases(unsigned long long* out, long long max_values);
 int rt_debug_quotient_check(int device, unsigned long long seed, long long count,
                             long long* out2);
 
+/* ---- Ray queries: closest hit and occlusion for the caller's own rays -------------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_RAY_QUERY / rt_ray_query_version).
+ * The frame calls answer "what colour is pixel (x, y) of camera c"; these trace any ray the
+ * caller generates — area-light, lens, glossy or path-tracing rays of the later homeworks, or
+ * a caller's own shading — through the same intersection rule (HW2/Bounding_volume_hierarchy.cpp,
+ * Triangle.cpp, Sphere.h):
+ *
+ *   closest hit  ray i's result is what Scene::trace_ray's bvh->intersect(ray, hit) yields: the
+ *                minimum of (t, DFS leaf) over the leaves the ray may reach with 0 < t < inf, or,
+ *                when the scene's root is one primitive, that primitive's own rule (a lone sphere
+ *                reports its negative root).  tmax is ignored.
+ *   occlusion    1 iff some leaf the ray may reach has 0 < t < tmax (the shadow-ray test of
+ *                HW2/Scene.cpp:123-127 with tmax = dist - eps); tmax <= 0 or NaN gives 0.
+ *
+ * Both honour rt_set_traversal (both modes give the same bits) and are independent per ray: a
+ * ray's result does not depend on n, its position in the batch, its neighbours or `flags`.
+ * d need not be normalised (t is in units of d).  A ray is INVALID when a component of o or d is
+ * not finite, or when all three |d_i| < 1e-6; it reports a miss / 0 and does not disturb other
+ * rays.  The all-zero direction is the one deliberate departure from the reference, whose slab
+ * test would skip every axis and test every leaf for such a ray (it never builds one); with one
+ * or two |d_i| < 1e-6 the ray is valid and those axes are skipped as in HW2/bounding_box.cpp:21.
+ *
+ * RT_QUERY_REORDER: the library first groups similar rays (by origin cell and quantised
+ * direction, one counting sort on the device) so the 64 rays of a wave walk similar paths; the
+ * results are bit-identical with and without it, and land in the caller's order either way.
+ *
+ * rays, hits: 16-byte aligned.  n == 0 succeeds and launches nothing; n < 0, an unknown flag
+ * bit, a NULL pointer with n > 0 or a misaligned pointer is RT_E_INVALID.  Multi-device scenes:
+ * RT_E_UNSUPPORTED.  The ray counters of rt_stats are not touched. */
+#define CENG795_RT_HAS_RAY_QUERY 1
+int rt_ray_query_version(void); /* 1 */
+
+typedef struct rt_ray {      /* 32 B */
+  float o[3];  float tmax;   /* tmax: occlusion queries only */
+  float d[3];  float pad;    /* d need not be normalised     */
+} rt_ray;
+typedef struct rt_ray_hit {  /* 32 B */
+  float t;        /* the reference's Hit_data::t; +inf on a miss                     */
+  int   object;   /* index in the object lists, bvh_leaf_object's numbering; -1 miss */
+  int   material; /* -1 miss                                                         */
+  int   leaf;     /* DFS leaf index = the closest-hit tie-break key; -1 miss         */
+  float normal[3];/* Hit_data::normal: flat triangle normal, or
+                     (o + d*t - center).normalize() for a sphere; 0 0 0 on a miss    */
+  int   pad;
+} rt_ray_hit;
+enum { RT_QUERY_REORDER = 1 };
+
+/* Device-resident variants: d_rays / d_hits / d_occ are device memory of the scene's device.
+ * Asynchronous on `hip_stream`; they use that stream's scratch like rt_render_device (the
+ * reorder stage's buffers live there), so calls on one stream run in order and may interleave
+ * with frames, different streams may be in flight together, and rt_release_stream_scratch
+ * frees the scratch.  d_occ: one byte per ray, 0 or 1. */
+int rt_trace_rays_device(rt_scene* scene, const rt_ray* d_rays, long long n, rt_ray_hit* d_hits,
+                         int flags, void* hip_stream);
+int rt_occluded_device(rt_scene* scene, const rt_ray* d_rays, long long n, unsigned char* d_occ,
+                       int flags, void* hip_stream);
+/* Host variants, synchronous: upload, run, download. */
+int rt_trace_rays(rt_scene* scene, const rt_ray* rays, long long n, rt_ray_hit* hits, int flags);
+int rt_occluded(rt_scene* scene, const rt_ray* rays, long long n, unsigned char* occ, int flags);
+/* Host-only, touches no HIP API: for each DFS leaf of the description's tree (built by the
+ * library, or the caller's own bvh_*: then it is bvh_leaf_object) its index in the object lists
+ * — what rt_ray_hit::object reports for rt_ray_hit::leaf.  Writes min(leaves, capacity) values
+ * (out may be NULL with capacity 0) and returns the leaf count, or a negative RT_E_* code. */
+int rt_host_leaf_objects_desc(const rt_scene_desc* desc, int* out, int capacity);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 

@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""Ray-query throughput on the C3 scene (not bench.py): camera 0's 1920x1080 primary rays put
+to rt_trace_rays_device / rt_occluded_device in three orders — row-major, the frame kernel's
+8x8-tile order, a seeded shuffle — each with and without RT_QUERY_REORDER.
+
+Per case: device-event time of every call over --calls rounds after --warmup rounds, the
+cases alternated within each round (one process), median and quartiles, Mrays/s from the
+median.  For scale, the frame kernel's own time on the same scene in the same rounds
+(rt_set_kernel_timing): it traces the same primary rays in tile order, plus shadow rays and
+shading.  Writes profiles/ray_query.json, keyed to the sha256 of the library that ran.
+
+usage: ray_query_bench.py [--calls 50] [--warmup 3] [--n 708] [--out PATH] [--check]
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import gen_scene  # noqa: E402
+
+
+def file_sha256(path: str) -> str:
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for b in iter(lambda: f.read(1 << 20), b""):
+            h.update(b)
+    return h.hexdigest()
+
+
+def primary_rays(cam):
+    """o = e, d = normalize((top_left + (x + 0.5) s_u) - (y + 0.5) s_v - e) in fp32 (the
+    camera's rays, Camera.h:30-35), row-major."""
+    f = np.float32
+    e, tl = np.array(cam.e, f), np.array(cam.top_left, f)
+    su, sv = np.array(cam.s_u, f), np.array(cam.s_v, f)
+    x = (np.arange(cam.width, dtype=f) + f(0.5))[None, :, None]
+    y = (np.arange(cam.height, dtype=f) + f(0.5))[:, None, None]
+    s = (tl + x * su) - y * sv
+    d = s - e
+    d = d / np.sqrt((d * d).sum(-1, dtype=f))[..., None]
+    d = np.ascontiguousarray(d.reshape(-1, 3), f)
+    return np.broadcast_to(e, d.shape), d
+
+
+def orders(width: int, height: int, seed: int):
+    n = width * height
+    idx = np.arange(n, dtype=np.int64).reshape(height, width)
+    th, tw = -(-height // 8), -(-width // 8)
+    padded = np.full((th * 8, tw * 8), -1, np.int64)
+    padded[:height, :width] = idx
+    tiles = padded.reshape(th, 8, tw, 8).transpose(0, 2, 1, 3).reshape(-1)
+    return {"row_major": idx.reshape(-1), "tile_8x8": tiles[tiles >= 0],
+            "shuffled": np.random.default_rng(seed).permutation(n)}
+
+
+def quartiles(ms):
+    q = np.percentile(np.array(ms), [25, 50, 75])
+    return {"ms_q1": float(q[0]), "ms_median": float(q[1]), "ms_q3": float(q[2])}
+
+
+def main(argv=None) -> int:
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--calls", type=int, default=50)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--n", type=int, default=708, help="height-field grid (708: the C3 mesh)")
+    p.add_argument("--width", type=int, default=1920)
+    p.add_argument("--height", type=int, default=1080)
+    p.add_argument("--seed", type=int, default=795)
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query.json"))
+    p.add_argument("--check", action="store_true",
+                   help="also compare every case's results with the row-major ones, bit for bit")
+    a = p.parse_args(argv)
+
+    import torch
+    import ceng795_amd
+    from ceng795_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU")
+
+    with tempfile.TemporaryDirectory() as d:
+        xml = os.path.join(d, "c3.xml")
+        with open(xml, "w") as f:
+            f.write(gen_scene.heightfield_scene(a.n, a.width, a.height, name="c3.png").to_xml())
+        scene = ceng795_amd.Scene(xml, device=0)
+    cam = scene.camera(0)
+    o, dirs = primary_rays(cam)
+    n = len(dirs)
+    order = orders(cam.width, cam.height, a.seed)
+    rays = {}
+    for name, idx in order.items():
+        r = ceng795_amd.pack_rays(o[idx], dirs[idx], np.inf)
+        rays[name] = torch.from_numpy(r.view(np.uint8).reshape(-1)).cuda()
+    hits = torch.zeros(n * 32, dtype=torch.uint8, device="cuda")
+    occ = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    frame = torch.zeros((cam.height, cam.width, 3), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    cases = [(kind, name, flag) for kind in ("closest", "occluded") for name in order
+             for flag in (False, True)]
+
+    def run(kind, name, flag):
+        if kind == "closest":
+            scene.trace_rays_device(rays[name].data_ptr(), n, hits.data_ptr(), reorder=flag,
+                                    stream=stream)
+        else:
+            scene.occluded_device(rays[name].data_ptr(), n, occ.data_ptr(), reorder=flag,
+                                  stream=stream)
+
+    checks = {}
+    if a.check:
+        want = {}
+        for kind, name, flag in cases:
+            run(kind, name, flag)
+            torch.cuda.synchronize()
+            out = (hits if kind == "closest" else occ).cpu().numpy()
+            out = out.reshape(n, -1)
+            back = np.empty_like(out)
+            back[order[name]] = out  # to row-major positions
+            if (kind, "row_major", False) == (kind, name, flag):
+                want[kind] = back
+            checks[f"{kind}/{name}/{'reorder' if flag else 'plain'}"] = bool(
+                np.array_equal(back, want[kind]))
+        hit_share = float((want["closest"].view(np.int32)[:, 1] >= 0).mean())
+    else:
+        hit_share = None
+
+    times = {c: [] for c in cases}
+    scene.set_kernel_timing(False)
+    for rnd in range(a.warmup + a.calls):
+        timed = rnd >= a.warmup
+        if rnd == a.warmup:
+            torch.cuda.synchronize()
+            scene.set_kernel_timing(True)
+        marks = []
+        for c in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(*c)
+            e1.record()
+            marks.append((c, e0, e1))
+        scene.render_device(0, frame.data_ptr(), stream=stream)  # the frame kernel, same rounds
+        torch.cuda.synchronize()
+        if timed:
+            for c, e0, e1 in marks:
+                times[c].append(e0.elapsed_time(e1))
+    kt, launches = scene.read_kernel_times()
+    frame_ms = kt["frame"] / max(1, launches)
+
+    result = {"lib_sha256": file_sha256(_lib.LIB_PATH), "device": torch.cuda.get_device_name(0),
+              "scene": f"C3: height field {a.n}, camera 0 {cam.width}x{cam.height}",
+              "rays": n, "calls": a.calls, "warmup": a.warmup,
+              "timing": "device events around each call; cases alternated within every round",
+              "frame_kernel_ms": frame_ms, "frame_kernel_launches": launches,
+              "frame_kernel_note": "rt_set_kernel_timing mean over the same rounds: primary + "
+                                   "shadow rays + shading of the same pixels in tile order",
+              "hit_share": hit_share, "cases": {}}
+    for (kind, name, flag), ms in times.items():
+        q = quartiles(ms)
+        q["mrays_per_s"] = n / q["ms_median"] / 1e3
+        result["cases"][f"{kind}/{name}/{'reorder' if flag else 'plain'}"] = q
+    c = result["cases"]
+    result["ratios"] = {
+        "closest_tile_plain_over_frame_kernel": c["closest/tile_8x8/plain"]["ms_median"] / frame_ms,
+        "closest_shuffled_reorder_over_plain":
+            c["closest/shuffled/reorder"]["ms_median"] / c["closest/shuffled/plain"]["ms_median"],
+        "closest_tile_reorder_over_plain":
+            c["closest/tile_8x8/reorder"]["ms_median"] / c["closest/tile_8x8/plain"]["ms_median"],
+        "occluded_shuffled_reorder_over_plain":
+            c["occluded/shuffled/reorder"]["ms_median"] / c["occluded/shuffled/plain"]["ms_median"],
+    }
+    if a.check:
+        result["bit_identical_to_row_major"] = checks
+    scene.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+    return 0 if all(checks.values()) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
