@@ -650,4 +650,23 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
   return "";
 }
 
+void accel_slot_histogram(const HostScene& s, long long hist[kWideSlots + 1]) {
+  for (int i = 0; i <= kWideSlots; i++) hist[i] = 0;
+  if (s.accel_root < 0) return;
+  std::vector<int> todo{s.accel_root & ~kWideTag};
+  while (!todo.empty()) {
+    const int idx = todo.back();
+    todo.pop_back();
+    DevNode8 W;
+    std::memcpy(&W, &s.nodes[idx], sizeof W);
+    int valid = 0, r = 0;
+    for (int c = 0; c < kWideSlots; c++) {
+      if (!(W.kinds & (kSlotValid << c))) continue;
+      valid++;
+      if (!(W.kinds & (kSlotLeafy << c))) todo.push_back(W.inner_base + 2 * r++);
+    }
+    hist[valid]++;
+  }
+}
+
 }  // namespace rt

@@ -62,6 +62,8 @@ void build_accel(HostScene& s, int K);
 // margin, child layout, ancestry); "" if they hold.  stats: treelets, culling nodes, culling
 // depth, lone-leaf treelets.
 std::string check_accel(const HostScene& s, int K, long long stats[4]);
+// hist[v] = culling nodes with v valid slots (a tree that passed check_accel).
+void accel_slot_histogram(const HostScene& s, long long hist[kWideSlots + 1]);
 
 // Builds `out` from `desc`; throws std::invalid_argument on a bad description.
 void build_host_scene(const rt_scene_desc& desc, HostScene& out);

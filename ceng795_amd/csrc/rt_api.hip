@@ -1301,6 +1301,24 @@ int rt_host_check_accel_xml(const char* xml_path, int treelet_leaves, long long*
   });
 }
 
+int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long long* hist9) {
+  if (!xml_path || !hist9)
+    return set_error(RT_E_INVALID, "rt_host_accel_slot_hist_xml: NULL argument");
+  return guarded([&] {
+    XmlSceneStorage st;
+    rt_scene_desc d;
+    load_scene_xml(xml_path, st, d);
+    HostScene h;
+    build_host_scene(d, h);
+    build_accel(h, treelet_leaves);
+    long long stats[4];
+    const std::string err = check_accel(h, treelet_leaves, stats);
+    if (!err.empty()) throw std::invalid_argument("culling tree: " + err);
+    accel_slot_histogram(h, hist9);
+    return RT_OK;
+  });
+}
+
 int rt_set_traversal(rt_scene* s, int mode) {
   if (!s || (mode != RT_TRAVERSAL_FAST && mode != RT_TRAVERSAL_REFERENCE))
     return set_error(RT_E_INVALID, "rt_set_traversal: bad argument");

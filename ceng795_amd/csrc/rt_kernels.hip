@@ -134,6 +134,9 @@ __device__ __forceinline__ uint64_t lanes_lt(float a, float b) { return __builti
 // !(a >= b): true for a NaN operand too
 __device__ __forceinline__ uint64_t lanes_nge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpULT); }
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+// v_writelane_b32 (the LLVM intrinsic; clang has no builtin for it): `old` with lane `lane`
+// (wave-uniform) replaced by the wave-uniform `v`.  Ignores EXEC.
+__device__ int writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
 // ------------------------------------------------------------------ slab test
 // Literal HW2/bounding_box.cpp:15-35 + the caller's reject rule (BVH.cpp:32-35).  Used when
@@ -307,7 +310,7 @@ __device__ __forceinline__ bool leaf_test(const DevPrim* __restrict__ prims, int
 
 // ------------------------------------------------------------------ traversal stack
 // Wave-uniform (node, lane-mask) entries.  DEEP == false: entry i lives in VGPR lane i
-// (select-on-lane push / v_readlane pop, no memory traffic, 64 deep).  DEEP == true: a
+// (v_writelane push / v_readlane pop, no memory traffic, 64 deep).  DEEP == true: a
 // per-wave LDS array of kDeepStack entries for trees deeper than 64 levels (lane 0 writes,
 // all lanes read the broadcast word; LDS ops of one wave complete in order).
 constexpr int kDeepStack = 1024;
@@ -323,10 +326,12 @@ struct WaveStack {
 
   __device__ __forceinline__ void push(int n, uint64_t m) {
     if (!DEEP) {
-      const bool mine = lane_id() == sp;  // v_cmp + v_cndmask: lane sp takes the entry
-      node = mine ? n : node;
-      mlo = mine ? (unsigned)m : mlo;
-      mhi = mine ? (unsigned)(m >> 32) : mhi;
+      // Lane sp takes the entry: three v_writelane_b32, the values in SGPRs and the lane select
+      // in M0 (gfx9 allows a v_writelane one SGPR besides M0).  (Round 7: was a v_cmp and three
+      // v_mov + v_cndmask, seven VALU)
+      node = writelane(n, sp, node);
+      mlo = (unsigned)writelane((int)(unsigned)m, sp, (int)mlo);
+      mhi = (unsigned)writelane((int)(unsigned)(m >> 32), sp, (int)mhi);
     } else if (lane_id() == 0) {
       lds[kDeepWords * sp] = n;
       lds[kDeepWords * sp + 1] = (int)(unsigned)m;
@@ -506,23 +511,33 @@ __device__ __forceinline__ void batch_push(WaveLeafLds& L, int& n, int leaf, uin
   n += __builtin_popcountll(m);
 }
 
-// Queue leaves `leaf` and `leaf + 1` (a pair) for the lanes of `m`: each lane's two entries are
-// adjacent (one ds_write2_b32), the queue order does not matter.
+// A wide slot's lone leaf (p = 0) or leaf pair (p = 1, wave-uniform) in one branch-free push: a
+// lane's rank among the lanes of `m` is shifted by p, the first word goes to its entry and the
+// word `leaf + p` to entry + p — the pair's second entry, or for a lone leaf the same word to
+// the same place again (LDS writes of one wave complete in order).  ALL: the junk / queue
+// select is one v_cndmask on the mask itself (written `lane_in(m) ? :` the compiler wraps the
+// rank in an s_and_saveexec / s_or exec pair).  (Round 7, DESIGN.md §5.1: against a branch on
+// the pair bit around batch_push / batch_push_pair, 5 scalar-side instructions fewer per leafy
+// hit and 1.8 KB less code.)
 template <bool ALL = false>
-__device__ __forceinline__ void batch_push_pair(WaveLeafLds& L, int& n, int leaf, uint64_t m) {
+__device__ __forceinline__ void batch_push_n(WaveLeafLds& L, int& n, int leaf, uint64_t m,
+                                             unsigned p) {
   const int lane = lane_id();
   const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
                                                    __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
   const unsigned e = ((unsigned)lane << kQueueLeafBits) | (unsigned)leaf;
-  if (ALL) {  // (n may be odd: two 4-B writes, ds_write2_b32)
-    const int at = lane_in(m) ? n + 2 * below : kBatchCap + 2 * lane;
+  if (ALL) {
+    int at;
+    asm("v_cndmask_b32 %0, %1, %2, %3"
+        : "=v"(at) : "v"(kBatchCap + 2 * lane), "v"(n + (below << p)), "s"(m));
     L.q[at] = e;
-    L.q[at + 1] = e + 1u;
+    L.q[at + (int)p] = e + p;
   } else if (lane_in(m)) {
-    L.q[n + 2 * below] = e;
-    L.q[n + 2 * below + 1] = e + 1u;
+    const int at = n + (below << p);
+    L.q[at] = e;
+    L.q[at + (int)p] = e + p;
   }
-  n += 2 * __builtin_popcountll(m);
+  n += __builtin_popcountll(m) << p;
 }
 
 __device__ __forceinline__ float lane_f(int src, float v) {
@@ -667,9 +682,10 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
 #pragma unroll
   for (int x = 0; x < 3; x++) {
     S[x] = __builtin_amdgcn_ldexpf(rc[x], (int)(signed char)(scale >> (8 * x)));
-    const float A = (__int_as_float(a[x]) - o[x]) * rc[x];
-    Alo[x] = A - __builtin_fabsf(mg[x]);  // entry plane earlier
-    Ahi[x] = A + __builtin_fabsf(mg[x]);  // exit plane later
+    // (fma: three VALU per axis, and one rounding fewer than a product and a sum — DESIGN.md §4.2)
+    const float A = __int_as_float(a[x]) - o[x];
+    Alo[x] = __builtin_fmaf(A, rc[x], -__builtin_fabsf(mg[x]));  // entry plane earlier
+    Ahi[x] = __builtin_fmaf(A, rc[x], __builtin_fabsf(mg[x]));   // exit plane later
     if (SKIP) {  // a skipped axis: every plane at -inf / +inf (fma(h, 0, -+inf), h finite)
       const bool sk = x == 0 ? r.skip0 : (x == 1 ? r.skip1 : r.skip2);
       S[x] = sk ? 0.0f : S[x];
@@ -699,22 +715,21 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
     const float tf = __builtin_fminf(__builtin_fminf(f3[0], f3[1]), f3[2]);
     // out: !(tf >= max(tn, 0)) — one compare (tn and tf are never NaN on a valid slot: finite
     // fp16 planes, finite scales, skipped axes at -inf / +inf)
-    const uint64_t hm = m & alive & ~lanes_nge(tf, __builtin_fmaxf(tn, 0.0f));
+    // (m holds no lane outside `alive` wherever a visit starts — occluded() folds it in after
+    // every flush and pop_live at every pop — so the slots do not mask with it again)
+    const uint64_t hm = m & ~lanes_nge(tf, __builtin_fmaxf(tn, 0.0f));
     if (!hm) continue;
     DIAG(dg.ev[kPhSlotHits]++);
     if (kinds & (kSlotLeafy << c)) {
       DIAG(dg.ev[kPhLeafyHits]++);
       const int leaf = leaf_base + (int)((offs >> (4 * c)) & 15u);
-      const bool pair = (kinds & (kSlotPair << c)) != 0;
+      [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
       DIAG(dg.ev[kPhPairHits] += pair);
       // (the shadow kernel keeps the exec-mask pushes: junk writes cost it VGPR spills)
 #ifdef RT_PRIO_PUSH  // (A/B builds: the leaf pushes at another priority; +0.3 %, in the noise)
       __builtin_amdgcn_s_setprio(RT_PRIO_PUSH);
 #endif
-      if (pair)
-        batch_push_pair<!SHADOW>(L, pending, leaf, hm);
-      else
-        batch_push<!SHADOW>(L, pending, leaf, hm);
+      batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
 #ifdef RT_PRIO_PUSH
       __builtin_amdgcn_s_setprio(3);  // (RT_PRIO_V)
 #endif

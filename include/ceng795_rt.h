@@ -193,6 +193,9 @@ int rt_host_dump_bvh_desc(const rt_scene_desc* desc, const char* out_path);
  * stats4: treelets, culling nodes, culling-tree depth, lone-leaf treelets (zeros when the
  * tree is a single treelet).  RT_E_INVALID with the violation in rt_last_error(). */
 int rt_host_check_accel_xml(const char* xml_path, int treelet_leaves, long long* stats4);
+/* Host-only: builds and checks the culling tree as above, then hist9[v] = its 8-wide nodes with
+ * v valid slots (v = 0..8; all zero when the tree is a single treelet). */
+int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long long* hist9);
 /* Height of the flattened BVH (levels of internal nodes). */
 int rt_scene_bvh_depth(const rt_scene* scene);
 
