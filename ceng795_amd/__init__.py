@@ -8,12 +8,14 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
     write_png(name, pixels)                          # HW2/main.cpp:43-57
     hits = scene.trace_rays(origins, directions)     # closest hit of the caller's own rays
     occ = scene.occluded(origins, directions, tmax)  # is the segment blocked?
+    rad = scene.shade_rays(origins, directions)      # Scene::trace_ray of the caller's own rays
 
 Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 """
-from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, pack_rays,  # noqa: F401
-                    host_leaf_objects)
+from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, RADIANCE_DTYPE,  # noqa: F401
+                    pack_rays, host_leaf_objects)
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
 __all__ = ["Scene", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_FAST",
-           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "pack_rays", "host_leaf_objects"]
+           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "pack_rays",
+           "host_leaf_objects"]

@@ -26,6 +26,7 @@ RT_TRAVERSAL_FAST = 0
 RT_TRAVERSAL_REFERENCE = 1
 
 RT_QUERY_REORDER = 1  # flags of the ray queries
+RT_QUERY_IN_MEDIUM = 2  # radiance queries only: every ray starts inside a dielectric
 
 F3 = C.c_float * 3
 
@@ -82,6 +83,10 @@ class rt_ray(C.Structure):
 class rt_ray_hit(C.Structure):
     _fields_ = [("t", C.c_float), ("object", C.c_int), ("material", C.c_int), ("leaf", C.c_int),
                 ("normal", F3), ("pad", C.c_int)]
+
+
+class rt_radiance(C.Structure):
+    _fields_ = [("rgb", F3), ("t", C.c_float)]
 
 
 # name -> (restype, argtypes); mirrors include/ceng795_rt.h one to one
@@ -147,6 +152,13 @@ SIGNATURES = {
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]),
     "rt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]),
     "rt_host_leaf_objects_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_int), C.c_int]),
+    "rt_radiance_query_version": (C.c_int, []),
+    "rt_shade_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_void_p]),
+    "rt_shade_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
+                                C.POINTER(rt_stats)]),
+    "rt_set_radiance_scratch_limit": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "rt_stream_frame_scratch_bytes": (C.c_longlong, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

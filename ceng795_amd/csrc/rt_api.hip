@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <array>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,6 +44,10 @@ long long read_reset_phases(unsigned long long* out, long long max_values);
 int launch_cold_order(RenderParams P, hipStream_t stream);
 hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
                         bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream);
+hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
+hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
+                           const DevNode* nodes, bool fast, bool deep, bool spheres,
+                           hipStream_t stream);
 void write_png(const std::string& path, const float* rgb, int w, int h);
 }  // namespace rt
 
@@ -67,6 +72,11 @@ using namespace rt;
 #define RT_RENDER_CHUNKS 2
 #endif
 constexpr int kRenderChunks = RT_RENDER_CHUNKS;
+
+// Frame scratch of one chunk of a recursing radiance query: 256 MiB hold the
+// frames of 342k rays at depth 6 (784 B each) — more waves than the device keeps resident, so a
+// chunk still fills it — and of 1.2 M rays at depth 1.
+constexpr size_t kRadianceDefaultLimit = size_t(256) << 20;
 
 struct RenderCtx {
   Stream stream;
@@ -166,6 +176,8 @@ struct rt_scene {
   bool has_spheres = false;
   size_t most = 1;         // pixel records of the largest camera frame (whole tiles)
   unsigned long long msaa_seed = 0;
+  // bytes of ray-tree frames one chunk of a radiance query may hold (rt_set_radiance_scratch_limit)
+  std::atomic<size_t> radiance_limit{kRadianceDefaultLimit};
   std::vector<std::unique_ptr<Replica>> rep;  // rep[0]: the first (output) device
   std::mutex timing_mu;
   KernelTiming timing;
@@ -1048,12 +1060,13 @@ std::vector<int> single_device(int device) {
   return {device};
 }
 
-// Argument rules shared by the four ray-query entries; they need no GPU.
+// Argument rules shared by the ray-query and radiance-query entries; they need no GPU.
 void check_query_args(const char* fn, const rt_scene* s, const void* rays, long long n,
-                      const void* out, bool out_aligned, int flags) {
+                      const void* out, bool out_aligned, int flags,
+                      int known_flags = RT_QUERY_REORDER) {
   const std::string f(fn);
   if (n < 0) throw std::invalid_argument(f + ": n < 0");
-  if (flags & ~RT_QUERY_REORDER) throw std::invalid_argument(f + ": unknown flag bit");
+  if (flags & ~known_flags) throw std::invalid_argument(f + ": unknown flag bit");
   if (n > 0 && (!rays || !out)) throw std::invalid_argument(f + ": NULL pointer");
   if ((uintptr_t)rays % 16 != 0 || (out_aligned && (uintptr_t)out % 16 != 0))
     throw std::invalid_argument(f + ": rays and hits must be 16-byte aligned");
@@ -1091,6 +1104,74 @@ void enqueue_query(rt_scene* s, const Replica& r, const rt_ray* d_rays, long lon
     hip_check(launch_query(P, Q, r.d_nodes.p, occlusion, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
                            s->deep, s->has_spheres, stream),
               "query launch");
+  }
+}
+
+// The depth a radiance query runs at: -1 = the scene's maximum.
+int radiance_depth(const char* fn, const rt_scene* s, int depth) {
+  if (depth < -1 || depth > s->host.max_depth)
+    throw std::invalid_argument(std::string(fn) + ": depth must be -1 or 0 .. MaxRecursionDepth");
+  return depth < 0 ? s->host.max_depth : depth;
+}
+
+size_t round_up_wave(long long n) { return (size_t)((n + 63) / 64 * 64); }
+
+// Enqueues the radiance query over d_rays[0, n) at `depth` on `stream`.  `scratch` holds the
+// reorder stage's buffers and `frames` the ray-tree frames of one chunk (the stream's or the
+// context's); a query that cannot recurse touches neither `frames` nor the limit.
+void enqueue_radiance(rt_scene* s, const Replica& r, const rt_ray* d_rays, long long n, int depth,
+                      rt_radiance* d_out, int flags, DevBuf<unsigned>& scratch,
+                      DevBuf<float>& frames, unsigned long long* counters, hipStream_t stream) {
+  const HostScene& h = s->host;
+  RenderParams P = scene_params(s, r);
+  P.counters = counters;
+  const bool reorder = (flags & RT_QUERY_REORDER) != 0;
+  const bool recurse = depth > 0 && s->needs_recursion;
+  QueryParams Q;
+  std::memset(&Q, 0, sizeof Q);
+  if (h.root_kind == kRootNode)
+    for (int a = 0; a < 3; a++) {
+      const float ext = h.root_box[a + 3] - h.root_box[a];
+      Q.box_lo[a] = h.root_box[a];
+      Q.box_scale[a] = ext > 0.0f && std::isfinite(ext) ? 1.0f / ext : 0.0f;
+    }
+  long long chunk = kQueryMaxLaunch;  // rays per launch
+  if (recurse) {
+    const long long fit = (long long)(s->radiance_limit.load() / radiance_frame_bytes(depth)) /
+                          kRadianceChunkUnit * kRadianceChunkUnit;
+    if (fit < kRadianceChunkUnit)
+      throw std::invalid_argument("radiance scratch limit below one wave's ray-tree frames");
+    chunk = std::min(chunk, fit);
+    frames.reserve(std::min((size_t)chunk, round_up_wave(n)) * kRadianceFrameFloats * (size_t)(depth + 1),
+                   "alloc ray-tree frames");
+  }
+  if (reorder) scratch.reserve(query_scratch_words(std::min(n, kQueryMaxLaunch)), "alloc query scratch");
+  RadianceParams R;
+  R.frames = recurse ? frames.p : nullptr;
+  R.lanes = (long long)std::min((size_t)chunk, round_up_wave(n));
+  R.depth = depth;
+  R.in_medium = (flags & RT_QUERY_IN_MEDIUM) ? 1 : 0;
+  // one permutation per kQueryMaxLaunch rays (32-bit entries), then that part chunk by chunk
+  for (long long done = 0; done < n; done += kQueryMaxLaunch) {
+    const long long part = std::min(n - done, kQueryMaxLaunch);
+    Q.rays = d_rays + done;
+    Q.out = d_out + done;
+    Q.n = part;
+    Q.perm = nullptr;
+    if (reorder) {
+      Q.perm_out = reinterpret_cast<int*>(scratch.p);
+      Q.hist = scratch.p + part;
+      Q.totals = Q.hist + (size_t(1) << query_bin_bits(part));
+      hip_check(launch_query_sort(Q, stream), "query sort launch");
+      Q.perm = Q.perm_out;
+    }
+    for (R.first = 0; R.first < part; R.first += chunk) {
+      QueryParams C = Q;
+      C.n = std::min(part, R.first + chunk);
+      hip_check(launch_radiance(P, C, R, r.d_nodes.p, s->mode != RT_TRAVERSAL_REFERENCE, s->deep,
+                                s->has_spheres, stream),
+                "radiance query launch");
+    }
   }
 }
 
@@ -1504,6 +1585,96 @@ int rt_trace_rays(rt_scene* s, const rt_ray* rays, long long n, rt_ray_hit* hits
 
 int rt_occluded(rt_scene* s, const rt_ray* rays, long long n, unsigned char* occ, int flags) {
   return query_host("rt_occluded", s, rays, n, occ, true, flags);
+}
+
+int rt_radiance_query_version(void) { return 1; }
+
+int rt_shade_rays_device(rt_scene* s, const rt_ray* d_rays, long long n, int depth,
+                         rt_radiance* d_out, int flags, void* stream) {
+  const char* fn = "rt_shade_rays_device";
+  return guarded([&] {
+    check_query_args(fn, s, d_rays, n, d_out, true, flags, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM);
+    depth = radiance_depth(fn, s, depth);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    std::unique_lock<std::mutex> lk;
+    StreamScratch* sc = scratch_for(s, r, stream, lk);
+    enqueue_radiance(s, r, d_rays, n, depth, d_out, flags, sc->query, sc->frames, r.d_counters.p,
+                     (hipStream_t)stream);
+    hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
+    return RT_OK;
+  });
+}
+
+int rt_shade_rays(rt_scene* s, const rt_ray* rays, long long n, int depth, rt_radiance* out,
+                  int flags, rt_stats* stats) {
+  const char* fn = "rt_shade_rays";
+  return guarded([&] {
+    check_query_args(fn, s, rays, n, out, true, flags, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM);
+    depth = radiance_depth(fn, s, depth);
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    struct Lease {  // a pooled context, handed back on every path
+      Replica& r;
+      RenderCtx* x;
+      ~Lease() {
+        (void)hipStreamSynchronize(x->stream);
+        release_ctx(r, x);
+      }
+    } lease{r, acquire_ctx(r)};
+    RenderCtx* x = lease.x;
+    static_assert(sizeof(rt_ray_hit) == 2 * sizeof(rt_radiance), "result buffer sizing");
+    x->d_rays.reserve((size_t)n, "alloc rays");
+    x->d_ray_out.reserve(((size_t)n + 1) / 2, "alloc results");
+    rt_radiance* d_out = reinterpret_cast<rt_radiance*>(x->d_ray_out.p);
+    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
+                             x->stream), "upload rays");
+    // this call's own counts, through the context's counter buffer (as rt_render)
+    hip_check(hipMemsetAsync(x->d_cnt.p, 0, sizeof(unsigned long long) * kCounterAlloc, x->stream),
+              "zero counters");
+    hip_check(hipEventRecord(x->e0, x->stream), "event record");
+    enqueue_radiance(s, r, x->d_rays.p, n, depth, d_out, flags, x->d_query, x->d_frames, x->d_cnt.p,
+                     x->stream);
+    hip_check(hipEventRecord(x->e1, x->stream), "event record");
+    hip_check(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_radiance), hipMemcpyDeviceToHost,
+                             x->stream), "download results");
+    std::vector<unsigned long long> cnt(kCounterAlloc);
+    hip_check(hipMemcpyAsync(cnt.data(), x->d_cnt.p, kCounterAlloc * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, x->stream), "copy counters");
+    hip_check(hipStreamSynchronize(x->stream), "synchronize query");
+    if (stats) {
+      add_counters(cnt, stats);
+      float ms = 0;
+      hip_check(hipEventElapsedTime(&ms, x->e0, x->e1), "elapsed");
+      stats->kernel_ms = ms;
+    }
+    return RT_OK;
+  });
+}
+
+int rt_set_radiance_scratch_limit(rt_scene* s, size_t bytes) {
+  if (!s) return set_error(RT_E_INVALID, "rt_set_radiance_scratch_limit: NULL scene");
+  // one wave of rays at the scene's maximum depth must fit (scenes that can recurse)
+  if (bytes != 0 && s->needs_recursion &&
+      bytes < (size_t)kRadianceChunkUnit * radiance_frame_bytes(s->host.max_depth))
+    return set_error(RT_E_INVALID, "rt_set_radiance_scratch_limit: below one wave's ray-tree "
+                                   "frames at the scene's MaxRecursionDepth");
+  s->radiance_limit.store(bytes ? bytes : kRadianceDefaultLimit);
+  return RT_OK;
+}
+
+long long rt_stream_frame_scratch_bytes(rt_scene* s, void* stream) {
+  if (!s) return set_error(RT_E_INVALID, "rt_stream_frame_scratch_bytes: NULL scene");
+  long long bytes = 0;
+  for (auto& rp : s->rep) {
+    std::lock_guard<std::mutex> lk(rp->mu);
+    for (auto& x : rp->streams)
+      if (x->stream == stream) bytes += (long long)(x->frames.cap * sizeof(float));
+  }
+  return bytes;
 }
 
 int rt_host_leaf_objects_desc(const rt_scene_desc* desc, int* out, int capacity) {

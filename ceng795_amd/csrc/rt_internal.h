@@ -353,6 +353,25 @@ constexpr size_t query_scratch_words(long long n) {
   return (size_t)n + (size_t(1) << query_bin_bits(n)) + (size_t(1) << (kQueryKeyBits - kQueryMinBinBits));
 }
 
+
+// Radiance queries (rt_shade_rays_device): one launch traces the rays
+// [first, Q.n) of the order in use — one chunk of the batch — from (o, d, in_medium, depth).
+// A recursing launch keeps its ray-tree frames in `frames`: (depth + 1) levels of
+// kRadianceFrameFloats fields of `lanes` floats, a lane's slot being its index within the chunk.
+constexpr int kRadianceFrameFloats = 28;         // rt_kernels.hip kFrFields
+constexpr long long kRadianceChunkUnit = 64;     // chunks are whole waves
+struct RadianceParams {
+  float* frames;  // nullptr: the launch cannot recurse (depth 0, or no mirror / glass material)
+  long long first;
+  long long lanes;
+  int depth;      // the reference's current_recursion_depth of every ray
+  int in_medium;  // RT_QUERY_IN_MEDIUM
+};
+// bytes of frame scratch one ray needs at `depth`
+constexpr size_t radiance_frame_bytes(int depth) {
+  return sizeof(float) * kRadianceFrameFloats * (size_t)(depth + 1);
+}
+
 }  // namespace rt
 
 #endif

@@ -1384,31 +1384,37 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
   return color;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES>
-__device__ __forceinline__ void recursive_packet(const RenderParams& P,
-                                                 const DevNode* __restrict__ nodes,
-                                                 const DevPrim* __restrict__ prims,
-                                                 const float* __restrict__ normals,
-                                                 const DevMaterial* __restrict__ mats,
-                                                 const DevLight* __restrict__ lights, int sel,
-                                                 int* spill, WaveLeafLds& L) {
-  const PacketPixel q = packet_pixel(P, sel);
-  const size_t lanes_total = (size_t)P.num_sel_tiles * (kTile * kTile);
-  const size_t g = (size_t)sel * (kTile * kTile) + q.lane;
+// Ray counts of one wave's ray trees (trace_tree): hits and shadow are wave totals, secondary is
+// this lane's own.
+struct TreeCounts {
+  unsigned long long hits = 0, shadow = 0, secondary = 0;
+};
+
+// Scene::trace_ray(Ray(ro, rd, medium), depth) of every `active` lane: the lane's ray tree in the
+// reference's post order.  Both callers run it: recursive_packet for a camera's pixel rays and
+// query_radiance_kernel for the caller's own.  The lane's frames are
+// frames[(level * kFrFields + field) * stride], `frames` already pointing at the lane's slot.
+// t_first: Hit_data::t of the lane's first ray, +inf on a miss or an inactive lane.
+// RECURSE = false (depth 0, or a scene without mirror or glass: no material can spawn a ray):
+// closest hit, local shading or the miss rule, and no frame is read or written.
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true>
+__device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* __restrict__ nodes,
+                                         const DevPrim* __restrict__ prims,
+                                         const float* __restrict__ normals,
+                                         const DevMaterial* __restrict__ mats,
+                                         const DevLight* __restrict__ lights, int* spill,
+                                         WaveLeafLds& L, float* frames, size_t stride, V3 ro, V3 rd,
+                                         bool medium, int depth, bool active, float& t_first,
+                                         TreeCounts& cnt) {
   auto frame = [&](int level) {
-    return FrameRef{P.frames + (size_t)level * kFrFields * lanes_total + g, lanes_total};
+    return FrameRef{frames + (size_t)level * kFrFields * stride, stride};
   };
-  // current ray of this lane
-  V3 ro = ld3(P.cam_e), rd = primary_dir(P, q.px, q.py);
-  bool medium = false;
-  int depth = P.max_depth;
-  bool active = q.valid;  // has a ray to trace
-  int sp = 0;             // frames on this lane's stack
+  int sp = 0;  // frames on this lane's stack
   V3 res = v3(0, 0, 0), out = v3(0, 0, 0);
   Diag dg;
-  unsigned long long n_primary = __builtin_popcountll(ballot(q.valid)), n_hits = 0;
-  unsigned long long n_shadow = 0, n_secondary = 0;
+  unsigned long long n_hits = 0, n_shadow = 0, n_secondary = 0;
   bool first = true;
+  t_first = RT_INF;
   while (ballot(active)) {
     const LaneRay ray = make_ray(ro, rd, P.quot_ok);
     const bool skip = ballot(active && (ray.skip0 || ray.skip1 || ray.skip2)) != 0;
@@ -1419,7 +1425,10 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
     else
       closest_hit<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, active, t, leaf, dg);
     const bool hit = active && leaf >= 0;
-    if (first) n_hits = __builtin_popcountll(ballot(hit));
+    if (first) {
+      n_hits = __builtin_popcountll(ballot(hit));
+      if (hit) t_first = t;
+    }
     first = false;
     V3 p = v3(0, 0, 0), n = v3(0, 0, 0);
     int mat = 0;
@@ -1432,6 +1441,13 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
     const V3 local = local_color<FAST, DEEP, SPHERES>(P, nodes, prims, mats, lights, spill, L,
                                                       hit && !medium, ray.o, p, n, mat, dg,
                                                       n_shadow);
+    if constexpr (!RECURSE) {  // the one ray of the tree (a miss: Scene.cpp:96-99)
+      if (hit)
+        out = local;
+      else if (active && depth == P.max_depth)
+        out = ld3(P.background);
+      break;
+    }
     if (active) {
       bool spawned = false;
       if (hit) {  // open a frame for this hit
@@ -1545,12 +1561,38 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
           n_secondary++;
         }
       }
-      if (!spawned) {  // the whole tree of this pixel is done
+      if (!spawned) {  // the whole tree of this lane is done
         out = res;
         active = false;
       }
     }
   }
+  cnt.hits = n_hits;
+  cnt.shadow = n_shadow;
+  cnt.secondary = n_secondary;
+  return out;
+}
+
+template <bool FAST, bool DEEP, bool SPHERES>
+__device__ __forceinline__ void recursive_packet(const RenderParams& P,
+                                                 const DevNode* __restrict__ nodes,
+                                                 const DevPrim* __restrict__ prims,
+                                                 const float* __restrict__ normals,
+                                                 const DevMaterial* __restrict__ mats,
+                                                 const DevLight* __restrict__ lights, int sel,
+                                                 int* spill, WaveLeafLds& L) {
+  const PacketPixel q = packet_pixel(P, sel);
+  const size_t lanes_total = (size_t)P.num_sel_tiles * (kTile * kTile);
+  const size_t g = (size_t)sel * (kTile * kTile) + q.lane;
+  const unsigned long long n_primary = __builtin_popcountll(ballot(q.valid));
+  float t_first;
+  TreeCounts cnt;
+  // the camera's pixel ray at the scene's maximum depth
+  const V3 out = trace_tree<FAST, DEEP, SPHERES>(P, nodes, prims, normals, mats, lights, spill, L,
+                                                 P.frames + g, lanes_total, ld3(P.cam_e),
+                                                 primary_dir(P, q.px, q.py), false, P.max_depth,
+                                                 q.valid, t_first, cnt);
+  const unsigned long long n_hits = cnt.hits, n_shadow = cnt.shadow, n_secondary = cnt.secondary;
   if (q.valid) {
     float* o;
     if (P.tile_major)
@@ -2324,6 +2366,59 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void query_occluded_kernel(
     reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
 }
 
+// Radiance of caller-supplied rays (rt_shade_rays_device): the layout of
+// query_closest_kernel, and between the lane's two 16-B loads and its one 16-B store the ray tree
+// of trace_tree from (o, d, R.in_medium, R.depth).  One launch covers the rays
+// [R.first, Q.n) of the order in use (a chunk: R.first is a multiple of 64, so waves stay whole);
+// a lane's frames sit at its slot within the chunk.  RECURSE = false touches no frame.
+static_assert(kFrFields == kRadianceFrameFloats, "frame size the host sizes the scratch by");
+#ifndef RT_RADIANCE_WAVES  // (A/B builds: waves per workgroup; measured in DESIGN.md §4.12)
+#define RT_RADIANCE_WAVES kWavesPerBlock
+#endif
+#ifndef RT_RADIANCE_MIN_WAVES  // (A/B builds: an occupancy request, as RT_FRAME_MIN_WAVES; 0 = none)
+#define RT_RADIANCE_MIN_WAVES 0
+#endif
+#if RT_RADIANCE_MIN_WAVES
+#define RT_RADIANCE_OCCUPANCY __attribute__((amdgpu_waves_per_eu(RT_RADIANCE_MIN_WAVES, 8)))
+#else
+#define RT_RADIANCE_OCCUPANCY
+#endif
+constexpr int kRadianceWaves = RT_RADIANCE_WAVES;
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE>
+__global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void query_radiance_kernel(
+    RenderParams P, QueryParams Q, RadianceParams R, const DevNode* __restrict__ nodes,
+    const DevPrim* __restrict__ prims, const float* __restrict__ normals,
+    const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights) {
+  extern __shared__ __attribute__((aligned(16))) int deep_stack[];
+  __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
+  const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;  // in the chunk
+  const long long i = R.first + slot;
+  if ((i & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, i);
+  const unsigned long long n_primary = __builtin_popcountll(ballot(q.valid));
+  float t;
+  TreeCounts cnt;
+  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE>(
+      P, nodes, prims, normals, mats, lights, spill, L, RECURSE ? R.frames + slot : nullptr,
+      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt);
+  if (i < Q.n) {
+    // Pixel::add_color(color, 1) onto a zeroed pixel; an invalid ray: (0, 0, 0, +inf)
+    const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
+    reinterpret_cast<f4*>(Q.out)[query_slot(Q, i)] = out;
+  }
+  if (P.counters) {
+    unsigned long long* row = counter_row(P, (int)((i >> 6) % kCounterSlots));
+    if (cnt.secondary) atomicAdd(&row[kCntSecondary], cnt.secondary);
+    if (lane_id() == 0) {
+      atomicAdd(&row[kCntPrimary], n_primary);
+      atomicAdd(&row[kCntHits], cnt.hits);
+      atomicAdd(&row[kCntShadow], cnt.shadow);
+    }
+  }
+}
+
 // RT_QUERY_REORDER: a permutation that brings similar rays into the same wave (64 unrelated rays
 // walk the union of 64 paths).  Key, most significant first: the dominant axis and sign of d (6
 // cube faces), the origin's cell in a 2x2x2 grid over the clamped scene box, and the direction's
@@ -2492,6 +2587,8 @@ static void launch_query_variant(const RenderParams& P, const QueryParams& Q, co
                        dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes);
 }
 
+hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
+
 // One query launch over Q.n rays (0 < n <= kQueryMaxLaunch); reorder: Q's hist / totals /
 // perm_out point at query_scratch_words(n) words of scratch.  The variant is picked as
 // launch_render picks the frame kernels'.
@@ -2500,17 +2597,8 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
   if (Q.n <= 0) return hipSuccess;
   Q.perm = nullptr;
   if (reorder) {
-    const int bits = query_bin_bits(Q.n);
-    Q.shift = kQueryKeyBits - bits;
-    Q.bins = 1 << bits;
-    const hipError_t e = hipMemsetAsync(Q.hist, 0, sizeof(unsigned) * (size_t)Q.bins, stream);
+    const hipError_t e = launch_query_sort(Q, stream);
     if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((Q.n + kQueryThreads - 1) / kQueryThreads));
-    hipLaunchKernelGGL(query_hist_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
-    hipLaunchKernelGGL(query_scan_chunks_kernel, dim3(Q.bins / kQueryScanChunk),
-                       dim3(kQueryThreads), 0, stream, Q);
-    hipLaunchKernelGGL(query_scan_totals_kernel, dim3(1), dim3(kQueryMaxChunks), 0, stream, Q);
-    hipLaunchKernelGGL(query_scatter_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
     Q.perm = Q.perm_out;
   }
   fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
@@ -2519,6 +2607,67 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
 #define RT_CASE(F, D, S)                                              \
   case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                       \
     launch_query_variant<F, D, S>(P, Q, nodes, occlusion, stream);    \
+    break;
+    RT_CASE(true, false, false)
+    RT_CASE(true, false, true)
+    RT_CASE(true, true, false)
+    RT_CASE(true, true, true)
+    RT_CASE(false, false, false)
+    RT_CASE(false, false, true)
+    RT_CASE(false, true, false)
+    RT_CASE(false, true, true)
+#undef RT_CASE
+  }
+  return hipGetLastError();
+}
+
+// The permutation of Q's rays [0, Q.n) into Q.perm_out (RT_QUERY_REORDER), for launches that
+// trace the batch in chunks afterwards (launch_radiance).
+hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
+  if (Q.n <= 0) return hipSuccess;
+  const int bits = query_bin_bits(Q.n);
+  Q.shift = kQueryKeyBits - bits;
+  Q.bins = 1 << bits;
+  const hipError_t e = hipMemsetAsync(Q.hist, 0, sizeof(unsigned) * (size_t)Q.bins, stream);
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)((Q.n + kQueryThreads - 1) / kQueryThreads));
+  hipLaunchKernelGGL(query_hist_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
+  hipLaunchKernelGGL(query_scan_chunks_kernel, dim3(Q.bins / kQueryScanChunk),
+                     dim3(kQueryThreads), 0, stream, Q);
+  hipLaunchKernelGGL(query_scan_totals_kernel, dim3(1), dim3(kQueryMaxChunks), 0, stream, Q);
+  hipLaunchKernelGGL(query_scatter_kernel, grid, dim3(kQueryThreads), 0, stream, Q);
+  return hipGetLastError();
+}
+
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE>
+static void launch_radiance_variant(const RenderParams& P, const QueryParams& Q,
+                                    const RadianceParams& R, const DevNode* nodes,
+                                    hipStream_t stream) {
+  const size_t lds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kRadianceWaves : 0;
+  const long long rays = Q.n - R.first;
+  const dim3 grid((unsigned)((rays + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
+  hipLaunchKernelGGL((query_radiance_kernel<FAST, DEEP, SPHERES, RECURSE>), grid,
+                     dim3(kRadianceWaves * 64), lds, stream, P, Q, R, nodes, P.prims, P.normals,
+                     P.materials, P.lights);
+}
+
+// One chunk of a radiance query: the rays [R.first, Q.n) of Q's order (Q.perm: the whole batch's
+// permutation, or null), at most R.lanes of them.  R.frames == nullptr picks the variant that
+// cannot recurse.
+hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
+                           const DevNode* nodes, bool fast, bool deep, bool spheres,
+                           hipStream_t stream) {
+  if (Q.n <= R.first) return hipSuccess;
+  fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
+  const bool recurse = R.frames != nullptr;
+  const int v = (recurse ? 8 : 0) | (fast ? 4 : 0) | (deep ? 2 : 0) | (spheres ? 1 : 0);
+  switch (v) {
+#define RT_CASE(F, D, S)                                                  \
+  case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                           \
+    launch_radiance_variant<F, D, S, false>(P, Q, R, nodes, stream);      \
+    break;                                                                \
+  case 8 | (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                       \
+    launch_radiance_variant<F, D, S, true>(P, Q, R, nodes, stream);       \
     break;
     RT_CASE(true, false, false)
     RT_CASE(true, false, true)

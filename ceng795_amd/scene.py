@@ -19,6 +19,8 @@ RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float
                       ("pad", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("material", np.int32),
                       ("leaf", np.int32), ("normal", np.float32, 3), ("pad", np.int32)])
+# rt_radiance, 16 bytes
+RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
 
 
 def _aligned(n: int, dtype) -> np.ndarray:
@@ -259,6 +261,48 @@ class Scene:
         check(lib().rt_occluded_device(self._h, C.c_void_p(rays_ptr), n, C.c_void_p(occ_ptr),
                                        _lib.RT_QUERY_REORDER if reorder else 0,
                                        C.c_void_p(stream)))
+
+    # ------------------------------------------------------------------ radiance queries
+    @staticmethod
+    def _radiance_flags(in_medium: bool, reorder: bool) -> int:
+        return ((_lib.RT_QUERY_IN_MEDIUM if in_medium else 0) |
+                (_lib.RT_QUERY_REORDER if reorder else 0))
+
+    def shade_rays(self, origins, directions, *, depth: Optional[int] = None,
+                   in_medium: bool = False, reorder: bool = False, stats: bool = False):
+        """Scene::trace_ray of each ray o + t d (rt_shade_rays): a RADIANCE_DTYPE array with the
+        colour ``rgb`` a frame would hold for that ray and the first hit's ``t`` (+inf on a
+        miss).  ``depth``: the reference's current_recursion_depth, None = the scene's
+        MaxRecursionDepth; a miss returns the background only at that maximum.  ``in_medium``:
+        every ray starts inside a dielectric (no local shading at its first hit).  With
+        ``stats`` returns (array, rt_stats of this call)."""
+        rays = pack_rays(origins, directions)
+        out = _aligned(len(rays), RADIANCE_DTYPE)
+        st = _lib.rt_stats()
+        check(lib().rt_shade_rays(self._h, rays.ctypes.data, len(rays),
+                                  -1 if depth is None else int(depth), out.ctypes.data,
+                                  self._radiance_flags(in_medium, reorder), C.byref(st)))
+        return (out, st) if stats else out
+
+    def shade_rays_device(self, rays_ptr: int, n: int, out_ptr: int, *,
+                          depth: Optional[int] = None, in_medium: bool = False,
+                          reorder: bool = False, stream: int = 0) -> None:
+        """rt_shade_rays_device: n rt_ray records in device memory at ``rays_ptr`` to n
+        rt_radiance records at ``out_ptr``, asynchronously on HIP stream ``stream``; the ray
+        counts go to collect_stats()."""
+        check(lib().rt_shade_rays_device(self._h, C.c_void_p(rays_ptr), n,
+                                         -1 if depth is None else int(depth), C.c_void_p(out_ptr),
+                                         self._radiance_flags(in_medium, reorder),
+                                         C.c_void_p(stream)))
+
+    def set_radiance_scratch_limit(self, nbytes: int) -> None:
+        """Bytes of ray-tree frames one chunk of a recursing radiance query may hold (0: the
+        default, 256 MiB)."""
+        check(lib().rt_set_radiance_scratch_limit(self._h, int(nbytes)))
+
+    def stream_frame_scratch_bytes(self, stream: int) -> int:
+        """Bytes of ray-tree frames the scene keeps for HIP stream ``stream`` (0: none)."""
+        return check(lib().rt_stream_frame_scratch_bytes(self._h, C.c_void_p(stream)))
 
     def release_stream(self, stream: int) -> None:
         """Frees the scratch the library keeps for HIP stream ``stream`` (after waiting for it)."""

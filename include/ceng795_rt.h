@@ -424,6 +424,63 @@ int rt_occluded(rt_scene* scene, const rt_ray* rays, long long n, unsigned char*
  * (out may be NULL with capacity 0) and returns the leaf count, or a negative RT_E_* code. */
 int rt_host_leaf_objects_desc(const rt_scene_desc* desc, int* out, int capacity);
 
+/* ---- Radiance queries: Scene::trace_ray for the caller's own rays -----------------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_RADIANCE_QUERY /
+ * rt_radiance_query_version).  The ray queries above return (t, normal, material) and leave the
+ * shading to the caller; these run the library's own — ambient and the point lights with their
+ * shadow rays, the mirror and dielectric recursion, the fp64 pow / exp / log, the background rule
+ * — for any ray: a thin-lens or fisheye camera, an anti-aliasing pattern, or the continuation
+ * ray of a caller-side bounce.
+ *
+ *   value     ray i's rgb is 0.0f + Scene::trace_ray(Ray(o, d, in_medium), depth)
+ *             (HW2/Scene.cpp:88-196): Pixel::color after add_color(c, 1) onto a zeroed pixel, so a
+ *             camera's pixel rays give that camera's frame bit for bit.  t is the first hit's
+ *             Hit_data::t, +inf on a miss — the bits of rt_ray_hit::t, a lone root sphere's
+ *             negative root included.  rt_ray::tmax and rt_ray::pad are ignored; d is used as
+ *             given (the reference normalises only where trace_ray does).
+ *   depth     -1: the scene's MaxRecursionDepth; 0 .. MaxRecursionDepth: the reference's
+ *             current_recursion_depth; anything else is RT_E_INVALID.  A first-ray miss returns
+ *             the background only when depth equals the scene's maximum (Scene.cpp:96-99), else
+ *             black.  A continuation ray goes back in at depth - 1.
+ *   flags     RT_QUERY_IN_MEDIUM: every ray of the batch starts with in_medium = true, so local
+ *             shading is skipped at its first hit (Scene.cpp:107) — per call, not per ray: split
+ *             the batch.  rt_trace_rays* / rt_occluded* refuse this bit like any unknown one.
+ *             RT_QUERY_REORDER: as above; results are bit-identical with and without it and land
+ *             in the caller's order.
+ *
+ * A ray's result does not depend on n, its position, its neighbours, the flags other than
+ * RT_QUERY_IN_MEDIUM, the traversal mode or the scratch limit.  Invalid rays (defined above) stay
+ * inactive, report (0, 0, 0, +inf) and disturb no other ray.  rays, out: 16-byte aligned; n == 0
+ * launches nothing; n < 0, an unknown flag bit, a NULL pointer with n > 0 or a misaligned pointer
+ * is RT_E_INVALID before any HIP call.  Multi-device scenes: RT_E_UNSUPPORTED.
+ *
+ * Counters: the device variant adds to the scene's device counters (rt_collect_stats): primary
+ * rays = the valid rays traced; primary hits, shadow rays and secondary rays as for
+ * rt_render_device.  The host variant fills *stats (nullable) with the call's own counts and the
+ * HIP-event time of its kernels.
+ *
+ * Streams and scratch: the rules of rt_trace_rays_device.  A query that can recurse (depth > 0 and
+ * a material with a non-zero mirror or transparency) keeps (depth + 1) x 28 floats of ray-tree
+ * frames per ray in the stream's scratch and runs in chunks of whole waves whose frames stay under
+ * the scratch limit: 256 MiB unless rt_set_radiance_scratch_limit sets another (0: the default
+ * again; a limit below one wave's frames at the scene's MaxRecursionDepth is RT_E_INVALID).  A
+ * query that cannot recurse allocates and touches no ray-tree scratch. */
+#define CENG795_RT_HAS_RADIANCE_QUERY 1
+int rt_radiance_query_version(void); /* 1 */
+
+typedef struct rt_radiance { float rgb[3]; float t; } rt_radiance; /* 16 B */
+enum { RT_QUERY_IN_MEDIUM = 2 };
+
+int rt_shade_rays_device(rt_scene* scene, const rt_ray* d_rays, long long n, int depth,
+                         rt_radiance* d_out, int flags, void* hip_stream);
+int rt_shade_rays(rt_scene* scene, const rt_ray* rays, long long n, int depth, rt_radiance* out,
+                  int flags, rt_stats* stats);
+int rt_set_radiance_scratch_limit(rt_scene* scene, size_t bytes);
+/* Bytes of ray-tree frames the scene keeps for `hip_stream`'s radiance queries and frames (0: none,
+ * or a stream the scene holds no scratch for).  For tests of the no-scratch rule above. */
+long long rt_stream_frame_scratch_bytes(rt_scene* scene, void* hip_stream);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 

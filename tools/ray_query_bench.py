@@ -9,7 +9,11 @@ median.  For scale, the frame kernel's own time on the same scene in the same ro
 (rt_set_kernel_timing): it traces the same primary rays in tile order, plus shadow rays and
 shading.  Writes profiles/ray_query.json, keyed to the sha256 of the library that ran.
 
-usage: ray_query_bench.py [--calls 50] [--warmup 3] [--n 708] [--out PATH] [--check]
+--radiance: the same three orders put to rt_shade_rays_device instead (the radiance query does
+the frame kernel's whole work for the caller's rays), every case checked bit for bit against the
+tile-order result and the frame in the same run; writes profiles/radiance_query.json.
+
+usage: ray_query_bench.py [--calls 50] [--warmup 3] [--n 708] [--out PATH] [--check] [--radiance]
 """
 from __future__ import annotations
 
@@ -76,10 +80,18 @@ def main(argv=None) -> int:
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--height", type=int, default=1080)
     p.add_argument("--seed", type=int, default=795)
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query.json"))
+    p.add_argument("--out", default=None,
+                   help="default: profiles/ray_query.json (profiles/radiance_query.json)")
+    p.add_argument("--radiance", action="store_true",
+                   help="radiance queries (rt_shade_rays_device) instead of hits and occlusion")
     p.add_argument("--check", action="store_true",
                    help="also compare every case's results with the row-major ones, bit for bit")
     a = p.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles",
+                             "radiance_query.json" if a.radiance else "ray_query.json")
+    if a.radiance:
+        return radiance_main(a)
 
     import torch
     import ceng795_amd
@@ -180,6 +192,112 @@ def main(argv=None) -> int:
     }
     if a.check:
         result["bit_identical_to_row_major"] = checks
+    scene.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+    return 0 if all(checks.values()) else 1
+
+
+def radiance_main(a) -> int:
+    """The radiance cases: orders x flag, alternated with a frame in every round."""
+    import torch
+    import ceng795_amd
+    from ceng795_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU")
+
+    with tempfile.TemporaryDirectory() as d:
+        xml = os.path.join(d, "c3.xml")
+        with open(xml, "w") as f:
+            f.write(gen_scene.heightfield_scene(a.n, a.width, a.height, name="c3.png").to_xml())
+        scene = ceng795_amd.Scene(xml, device=0)
+    cam = scene.camera(0)
+    o, dirs = primary_rays(cam)
+    n = len(dirs)
+    order = orders(cam.width, cam.height, a.seed)
+    rays = {}
+    for name, idx in order.items():
+        r = ceng795_amd.pack_rays(o[idx], dirs[idx])
+        rays[name] = torch.from_numpy(r.view(np.uint8).reshape(-1)).cuda()
+    rad = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    frame = torch.zeros((cam.height, cam.width, 3), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    cases = [(name, flag) for name in ("tile_8x8", "row_major", "shuffled")
+             for flag in (False, True)]
+
+    def run(name, flag):
+        scene.shade_rays_device(rays[name].data_ptr(), n, rad.data_ptr(), reorder=flag,
+                                stream=stream)
+
+    # every case against the tile-order result, and that against the frame, bit for bit
+    scene.render_device(0, frame.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    frame_rgb = frame.cpu().numpy().reshape(n, 3)
+    checks, want = {}, None
+    for name, flag in cases:
+        rad.zero_()
+        run(name, flag)
+        torch.cuda.synchronize()
+        out = rad.cpu().numpy().reshape(n, 16)
+        back = np.empty_like(out)
+        back[order[name]] = out  # to row-major positions
+        if want is None:
+            want = back
+        checks[f"radiance/{name}/{'reorder' if flag else 'plain'}"] = bool(
+            np.array_equal(back, want))
+    got = want.view(ceng795_amd.RADIANCE_DTYPE).reshape(n)
+    checks["tile_order_equals_frame"] = bool(
+        np.array_equal(got["rgb"].view(np.uint32), frame_rgb.view(np.uint32)))
+    hit_share = float(np.isfinite(got["t"]).mean())
+
+    times = {c: [] for c in cases}
+    scene.set_kernel_timing(False)
+    for rnd in range(a.warmup + a.calls):
+        timed = rnd >= a.warmup
+        if rnd == a.warmup:
+            torch.cuda.synchronize()
+            scene.set_kernel_timing(True)
+        marks = []
+        for c in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(*c)
+            e1.record()
+            marks.append((c, e0, e1))
+        scene.render_device(0, frame.data_ptr(), stream=stream)  # the frame kernel, same rounds
+        torch.cuda.synchronize()
+        if timed:
+            for c, e0, e1 in marks:
+                times[c].append(e0.elapsed_time(e1))
+    kt, launches = scene.read_kernel_times()
+    frame_ms = kt["frame"] / max(1, launches)
+
+    result = {"lib_sha256": file_sha256(_lib.LIB_PATH), "device": torch.cuda.get_device_name(0),
+              "scene": f"C3: height field {a.n}, camera 0 {cam.width}x{cam.height}",
+              "rays": n, "calls": a.calls, "warmup": a.warmup,
+              "timing": "device events around each call; cases alternated within every round",
+              "frame_kernel_ms": frame_ms, "frame_kernel_launches": launches,
+              "frame_kernel_note": "rt_set_kernel_timing mean over the same rounds: the same rays "
+                                   "in tile order, heavy-first dispatch, 12 B out per pixel",
+              "hit_share": hit_share, "cases": {}}
+    for (name, flag), ms in times.items():
+        q = quartiles(ms)
+        q["mrays_per_s"] = n / q["ms_median"] / 1e3
+        result["cases"][f"radiance/{name}/{'reorder' if flag else 'plain'}"] = q
+    c = result["cases"]
+    result["ratios"] = {
+        "tile_plain_over_frame_kernel": c["radiance/tile_8x8/plain"]["ms_median"] / frame_ms,
+        "row_major_plain_over_tile_plain":
+            c["radiance/row_major/plain"]["ms_median"] / c["radiance/tile_8x8/plain"]["ms_median"],
+        "shuffled_reorder_over_plain":
+            c["radiance/shuffled/reorder"]["ms_median"] / c["radiance/shuffled/plain"]["ms_median"],
+        "tile_reorder_over_plain":
+            c["radiance/tile_8x8/reorder"]["ms_median"] / c["radiance/tile_8x8/plain"]["ms_median"],
+    }
+    result["bit_identical_to_tile_order"] = checks
     scene.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
