@@ -14,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -24,10 +25,8 @@
 #include "rt_internal.h"
 
 namespace rt {
-hipError_t launch_render(const RenderParams& P, const DevNode* nodes, const DevPrim* prims,
-                         const float* normals, const DevMaterial* mats, const DevLight* lights,
-                         bool fast, bool deep, bool spheres, const hipEvent_t* marks,
-                         hipStream_t stream);
+hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
+                         const hipEvent_t* marks, hipStream_t stream);
 int max_supported_depth();
 hipError_t launch_msaa_resolve(const MsaaResolveParams& M, hipStream_t stream);
 hipError_t launch_untile(const UntileParams& U, hipStream_t stream);
@@ -71,6 +70,9 @@ using namespace rt;
 #ifndef RT_RENDER_CHUNKS  // (A/B builds)
 #define RT_RENDER_CHUNKS 2
 #endif
+#ifndef RT_PAIR_ROWS  // (A/B builds: 0 = each wave of a directly written frame writes its own tile)
+#define RT_PAIR_ROWS 1
+#endif
 constexpr int kRenderChunks = RT_RENDER_CHUNKS;
 
 // Frame scratch of one chunk of a recursing radiance query: 256 MiB hold the
@@ -78,16 +80,26 @@ constexpr int kRenderChunks = RT_RENDER_CHUNKS;
 // chunk still fills it — and of 1.2 M rays at depth 1.
 constexpr size_t kRadianceDefaultLimit = size_t(256) << 20;
 
+// What the launches on one stream (a pooled context's or a caller's) need besides their inputs
+// and outputs; they run one after the other, so they share it.  The buffers only grow.
+struct WorkSet {
+  DevBuf<rt::int2_t> hits;  // per pixel of the selected tiles: the primary hit
+  DevBuf<unsigned> occ;     // per pixel: the lights' occlusion bits
+  DevBuf<unsigned> sched;   // tile costs, unit order lists, cost snapshot (rt_internal.h)
+  DevBuf<float> frames;     // ray-tree frames: recursive scenes' frames and radiance queries
+  DevBuf<float> samples;    // MSAA cameras: the sample passes
+  DevBuf<unsigned> query;   // queries with RT_QUERY_REORDER: permutation, histogram, totals
+  void reserve_tiles(const HostScene& h, size_t tiles);  // hits, occ and sched
+  // Sizes the set for launch P of camera c, whose num_sel_tiles is final, and points P at it.
+  void bind(const rt_scene* s, const rt_camera& c, RenderParams& P);
+};
+
 struct RenderCtx {
   Stream stream;
   Event e0, e1;
   DevBuf<float> d_out;
   DevBuf<unsigned long long> d_cnt;
-  DevBuf<rt::int2_t> d_hits;
-  DevBuf<unsigned> d_occ;
-  DevBuf<unsigned> d_sched;  // per tile: traversal cost, then the shadow dispatch order
-  DevBuf<float> d_frames;
-  DevBuf<float> d_samples;
+  WorkSet work;
   DevBuf<float> d_recv;   // multi-device frames, first device: the gathered tiles
   DevBuf<float> d_image;  // multi-device rt_render, first device: the row-major frame
   Event ev_in, ev_out;    // multi-device frames: caller-stream ordering
@@ -95,28 +107,25 @@ struct RenderCtx {
   // has copied the shares out of the other contexts' buffers; a context renders its next share
   // only after it (the copy reads d_out / d_image on another stream: write-after-read)
   Event ev_gathered;
-  // rt_render's chunked copy-out (render_to_host): a second stream for the device-to-host copies
+  // rt_render's chunked copy-out (render_banded): a second stream for the device-to-host copies
   // and one event per row chunk (created on first use)
   Stream copy_stream;
   Event ev_chunk[kRenderChunks];
-  // rt_trace_rays / rt_occluded: the uploaded rays, the results, the reorder stage's scratch
+  // the host query entries: the uploaded rays and the results (rt_ray_hit or rt_radiance
+  // records, or n bytes of occlusion flags)
   DevBuf<rt_ray> d_rays;
-  DevBuf<rt_ray_hit> d_ray_out;  // (or n bytes of occlusion flags)
-  DevBuf<unsigned> d_query;
+  DevBuf<rt_ray_hit> d_ray_out;
 };
 
-// rt_render_device scratch of one stream (hit records, occlusion bits, tile schedule, ray-tree
-// frames, MSAA samples).  Owned through a unique_ptr, so its address is stable while the table
-// grows; `mu` serialises host threads that enqueue on the same stream.
+// What the `_device` entries keep for one caller stream.  Owned through a unique_ptr, so its
+// address is stable while the table grows; `mu` serialises host threads that enqueue on the
+// same stream.
 struct StreamScratch {
   void* stream = nullptr;
   std::mutex mu;
-  DevBuf<int2_t> hits;
-  DevBuf<unsigned> occ, sched;
-  DevBuf<float> frames, samples;
-  DevBuf<unsigned> query;  // ray queries with RT_QUERY_REORDER: permutation, histogram, totals
+  WorkSet work;
   // warm order: the selection whose heavy-first unit order the last frame on this stream left
-  // in `sched` (valid: that frame ran the order kernel)
+  // in `work.sched` (valid: that frame ran the order kernel)
   std::array<long long, 7> order_key{};
   bool order_valid = false;
   Event done;  // after the last frame enqueued on the stream (eviction waits on it)
@@ -259,19 +268,20 @@ constexpr size_t kCounterAlloc = (size_t)kCounterWidth * kCounterRows;
 #ifndef RT_ORDER_CHUNKS
 #define RT_ORDER_CHUNKS 2
 #endif
-// sched: sched_words_for(num_sel_tiles) words — tile costs, then the unit order lists
-// The untile kernel copies 16-B chunks when every frame row and both buffers are 16-B aligned.
-int untile_vec(const UntileParams& U) {
-  return (U.width % 4 == 0) && ((uintptr_t)U.out % 16 == 0) && ((uintptr_t)U.recv % 16 == 0);
-}
-
-
+// Points P's schedule at `sched`, sched_words_for(P.num_sel_tiles) words (layout: rt_internal.h);
+// P.num_sel_tiles is final.  (WorkSet::bind; beside it only the MSAA halo rows, which share
+// their band's buffer, and a camera's cold order, which has its own.)
 void set_schedule(RenderParams& P, unsigned* sched) {
   const int regions = RT_ORDER_REGIONS;
   P.tile_cost = regions ? sched : nullptr;
   P.unit_order = regions ? reinterpret_cast<int*>(sched) + P.num_sel_tiles : nullptr;
   P.order_regions = regions;
   P.order_chunk = RT_ORDER_CHUNKS;
+}
+
+// The untile kernel copies 16-B chunks when every frame row and both buffers are 16-B aligned.
+int untile_vec(const UntileParams& U) {
+  return (U.width % 4 == 0) && ((uintptr_t)U.out % 16 == 0) && ((uintptr_t)U.recv % 16 == 0);
 }
 
 // Estimated cost of every tile of camera c's whole frame, for the dispatch order of a frame
@@ -617,8 +627,8 @@ const hipEvent_t* timing_marks(rt_scene* s, const RenderParams& P) {
 
 // The sample passes of an MSAA camera (HW2/Scene.cpp:32-69) over P's rows: pass k renders
 // sample k of every selected pixel into d_samples[k] (row-major, full-frame positions).
-void enqueue_samples(rt_scene* s, const Replica& r, const RenderParams& P, int samples,
-                     float* d_samples, hipStream_t stream, bool timed) {
+void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_samples,
+                     hipStream_t stream, bool timed) {
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   const size_t frame = (size_t)P.width * P.height * 3;
   for (int k = 0; k < samples * samples; k++) {
@@ -630,9 +640,8 @@ void enqueue_samples(rt_scene* s, const Replica& r, const RenderParams& P, int s
     Q.msaa_seed = s->msaa_seed;
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
-    hip_check(launch_render(Q, r.d_nodes.p, r.d_prims.p, r.d_normals.p, r.d_mats.p, r.d_lights.p, fast,
-                            s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr, stream),
-              "render launch");
+    hip_check(launch_render(Q, fast, s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr,
+                            stream), "render launch");
   }
 }
 
@@ -655,16 +664,15 @@ void enqueue_resolve(rt_scene* s, int width, int height, int samples, const floa
 // render kernels write P.out directly.  MSAA cameras (HW2/Scene.cpp:32-69): one render pass per
 // sample index into d_samples[s], then the resolve kernel's splat + colour / weight into P.out
 // (row-major).  `timed`: this launch may take kernel-timing events (the first device only).
-void enqueue_frame(rt_scene* s, const Replica& r, const RenderParams& P, int samples,
-                   float* d_samples, hipStream_t stream, bool timed) {
+void enqueue_frame(rt_scene* s, const RenderParams& P, int samples, float* d_samples,
+                   hipStream_t stream, bool timed) {
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
-    hip_check(launch_render(P, r.d_nodes.p, r.d_prims.p, r.d_normals.p, r.d_mats.p, r.d_lights.p, fast,
-                            s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr, stream),
-              "render launch");
+    hip_check(launch_render(P, fast, s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr,
+                            stream), "render launch");
     return;
   }
-  enqueue_samples(s, r, P, samples, d_samples, stream, timed);
+  enqueue_samples(s, P, samples, d_samples, stream, timed);
   enqueue_resolve(s, P.width, P.height, samples, d_samples, P.out, 0, P.height, stream);
 }
 
@@ -731,41 +739,49 @@ RenderCtx* stream_ctx_for(Replica& r, void* stream) {
   return c;
 }
 
-// Contexts of one call on several replicas: pooled ones handed back on scope exit (rt_render),
-// or the caller stream's own (rt_render_device: consecutive frames on different caller streams
-// then run on different device streams, and frames on one caller stream stay ordered).
-struct CtxSet {
+// The contexts of one call, context d on replica d.
+using CtxList = std::vector<RenderCtx*>;
+
+// Pooled contexts of one synchronous call, one on each of the first n replicas: handed back on
+// every path, after their streams have drained.
+struct CtxLease {
   rt_scene* s;
-  std::vector<RenderCtx*> x;
-  bool pooled = true;
-  CtxSet(rt_scene* sc, size_t n) : s(sc) {
+  CtxList x;
+  CtxLease(rt_scene* sc, size_t n) : s(sc) {
     for (size_t d = 0; d < n; d++) x.push_back(acquire_ctx(*s->rep[d]));
   }
-  CtxSet(rt_scene* sc, size_t n, void* stream) : s(sc), pooled(false) {
-    for (size_t d = 0; d < n; d++) x.push_back(stream_ctx_for(*s->rep[d], stream));
-  }
-  ~CtxSet() {
-    if (!pooled) return;
-    for (size_t d = 0; d < x.size(); d++) release_ctx(*s->rep[d], x[d]);
+  CtxLease(const CtxLease&) = delete;
+  ~CtxLease() {
+    for (size_t d = 0; d < x.size(); d++) {
+      DeviceGuard g(s->rep[d]->device, std::nothrow);
+      (void)hipStreamSynchronize(x[d]->stream);
+      release_ctx(*s->rep[d], x[d]);
+    }
   }
 };
 
-// Sizes a context's per-call buffers for `sel_tiles` selected tiles of camera `cam` and points
-// P at them.
-void bind_ctx(rt_scene* s, RenderCtx* x, RenderParams& P, const rt_camera& c) {
-  const size_t lanes = (size_t)kTile * kTile * (size_t)std::max(1, P.num_sel_tiles);
-  x->d_hits.reserve(lanes, "alloc hit records");
-  P.hits = x->d_hits.p;
-  x->d_occ.reserve((size_t)P.occ_words * lanes, "alloc occlusion bits");
-  P.occ = x->d_occ.p;
-  x->d_sched.reserve((size_t)sched_words_for(lanes / (kTile * kTile)), "alloc tile schedule");
-  set_schedule(P, x->d_sched.p);
-  if (s->needs_recursion) {
-    x->d_frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
-    P.frames = x->d_frames.p;
-  }
-  if (c.num_samples > 1) x->d_samples.reserve(sample_floats(c), "alloc MSAA samples");
+}  // namespace
+
+void WorkSet::reserve_tiles(const HostScene& h, size_t tiles) {
+  const size_t lanes = (size_t)kTile * kTile * tiles;
+  hits.reserve(lanes, "alloc hit records");
+  occ.reserve((size_t)occ_words(h) * lanes, "alloc occlusion bits");
+  sched.reserve((size_t)sched_words_for(tiles), "alloc tile schedule");
 }
+
+void WorkSet::bind(const rt_scene* s, const rt_camera& c, RenderParams& P) {
+  reserve_tiles(s->host, (size_t)std::max(1, P.num_sel_tiles));
+  P.hits = hits.p;
+  P.occ = occ.p;
+  set_schedule(P, sched.p);
+  if (s->needs_recursion) {
+    frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
+    P.frames = frames.p;
+  }
+  if (c.num_samples > 1) samples.reserve(sample_floats(c), "alloc MSAA samples");
+}
+
+namespace {
 
 void add_counters(const std::vector<unsigned long long>& cnt, rt_stats* stats) {
   for (int r = 0; r < kCounterRows; r++) {
@@ -776,6 +792,54 @@ void add_counters(const std::vector<unsigned long long>& cnt, rt_stats* stats) {
   }
 }
 
+// Replica r's ray counters since they were last taken (rt_collect_stats, rt_debug_counters).
+std::vector<unsigned long long> take_counters(Replica& r) {
+  DeviceGuard g(r.device);
+  std::vector<unsigned long long> c(kCounterAlloc);
+  hip_check(hipMemcpy(c.data(), r.d_counters.p, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
+            "read counters");
+  hip_check(hipMemset(r.d_counters.p, 0, c.size() * sizeof c[0]), "reset counters");
+  return c;
+}
+
+// One synchronous call's own ray counts and kernel time, counted in its contexts' buffers
+// instead of the scene's: zeroes them and records e0 on the first context's stream; stop()
+// records e1 there; read() waits for every context's stream and fills `stats` (nullable).
+struct CallCounters {
+  rt_scene* s;
+  const CtxList& cx;
+  CallCounters(rt_scene* sc, const CtxList& c) : s(sc), cx(c) {
+    for (size_t d = 0; d < cx.size(); d++) {
+      DeviceGuard g(s->rep[d]->device);
+      hip_check(hipMemsetAsync(cx[d]->d_cnt.p, 0, sizeof(unsigned long long) * kCounterAlloc,
+                               cx[d]->stream),
+                "zero counters");
+    }
+    hip_check(hipEventRecord(cx[0]->e0, cx[0]->stream), "event record");
+  }
+  void stop() { hip_check(hipEventRecord(cx[0]->e1, cx[0]->stream), "event record"); }
+  void read(rt_stats* stats) {
+    std::vector<std::vector<unsigned long long>> cnt(cx.size(),
+                                                     std::vector<unsigned long long>(kCounterAlloc));
+    for (size_t d = 0; d < cx.size(); d++) {
+      DeviceGuard g(s->rep[d]->device);
+      hip_check(hipMemcpyAsync(cnt[d].data(), cx[d]->d_cnt.p, kCounterAlloc * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, cx[d]->stream),
+                "copy counters");
+    }
+    for (size_t d = 0; d < cx.size(); d++) {
+      DeviceGuard g(s->rep[d]->device);
+      hip_check(hipStreamSynchronize(cx[d]->stream), "synchronize");
+    }
+    if (!stats) return;
+    std::memset(stats, 0, sizeof *stats);
+    for (auto& v : cnt) add_counters(v, stats);
+    float ms = 0;
+    hip_check(hipEventElapsedTime(&ms, cx[0]->e0, cx[0]->e1), "elapsed");
+    stats->kernel_ms = ms;
+  }
+};
+
 // Device d's share of a multi-device frame on its way to the first device: `words` 4-B words
 // (floats or pixel records; 0: nothing to send) from src on device d to dst on the first.
 struct GatherPart {
@@ -784,15 +848,22 @@ struct GatherPart {
   size_t words;
 };
 
+// Orders `later` after what `earlier` holds so far, through event ev (both of the current device).
+void order_after(hipStream_t later, hipStream_t earlier, hipEvent_t ev) {
+  if (later == earlier) return;
+  hip_check(hipEventRecord(ev, earlier), "event record");
+  hip_check(hipStreamWaitEvent(later, ev, 0), "wait event");
+}
+
 // Lands part(d) of every device d > 0 on the first device, ordered after the work on device d's
 // context stream and on the first device's.  Copy gather: ev_out of context d, a wait and a peer
 // copy on the first device's stream, then ev_gathered there (the contexts' write-after-read
 // fence); else one RCCL group of send / receive pairs.  Caller holds s->multi_mu and has the
 // first device current.
 template <typename Part>
-void gather_parts(rt_scene* s, CtxSet& cx, Part&& part) {
+void gather_parts(rt_scene* s, const CtxList& cx, Part&& part) {
   const int D = (int)s->rep.size();
-  RenderCtx* x0 = cx.x[0];
+  RenderCtx* x0 = cx[0];
   if (D == 1) return;  // the one device rendered the frame in place
   if (s->copy_gather) {
     for (int d = 1; d < D; d++) {
@@ -800,9 +871,9 @@ void gather_parts(rt_scene* s, CtxSet& cx, Part&& part) {
       if (!g.words) continue;
       {
         DeviceGuard gd(s->rep[d]->device);
-        hip_check(hipEventRecord(cx.x[d]->ev_out, cx.x[d]->stream), "event record");
+        hip_check(hipEventRecord(cx[d]->ev_out, cx[d]->stream), "event record");
       }
-      hip_check(hipStreamWaitEvent(x0->stream, cx.x[d]->ev_out, 0), "wait event");
+      hip_check(hipStreamWaitEvent(x0->stream, cx[d]->ev_out, 0), "wait event");
       hip_check(hipMemcpyPeerAsync(g.dst, s->rep[0]->device, g.src, s->rep[d]->device,
                                    g.words * sizeof(float), x0->stream),
                 "gather copy");
@@ -814,7 +885,7 @@ void gather_parts(rt_scene* s, CtxSet& cx, Part&& part) {
   for (int d = 1; d < D; d++) {
     const GatherPart g = part(d);
     if (!g.words) continue;
-    nccl_check(ncclSend(g.src, g.words, ncclFloat, 0, s->comms[d], cx.x[d]->stream), "ncclSend");
+    nccl_check(ncclSend(g.src, g.words, ncclFloat, 0, s->comms[d], cx[d]->stream), "ncclSend");
     nccl_check(ncclRecv(g.dst, g.words, ncclFloat, d, s->comms[0], x0->stream), "ncclRecv");
   }
   nccl_check(ncclGroupEnd(), "ncclGroupEnd");
@@ -871,23 +942,22 @@ UntileParams checked_untile_params(const char* fn, bool records, const rt_scene*
 // resolves its band, and one RCCL group of send / receive pairs lands the bands in d_frame on
 // the first device.  Halo launches carry no counters, so the ray counts are one frame's.
 // Caller holds s->multi_mu.
-void render_multi_msaa(rt_scene* s, CtxSet& cx, int cam, float* d_frame, hipStream_t s0,
+void render_multi_msaa(rt_scene* s, const CtxList& cx, int cam, float* d_frame, hipStream_t s0,
                        bool per_call) {
   const int D = (int)s->rep.size();
   const rt_camera& c = s->host.cameras[cam];
   const int H = c.height, W = c.width, n = c.num_samples;
   const size_t frame = (size_t)W * H * 3;
-  RenderCtx* x0 = cx.x[0];
+  RenderCtx* x0 = cx[0];
   {
     DeviceGuard g(s->rep[0]->device);
-    hip_check(hipEventRecord(x0->ev_in, s0), "event record");  // d_frame's earlier work
-    hip_check(hipStreamWaitEvent(x0->stream, x0->ev_in, 0), "wait event");
+    order_after(x0->stream, s0, x0->ev_in);  // d_frame's earlier work
   }
   for (int d = 0; d < D; d++) {
     const int lo = (int)((long long)H * d / D), hi = (int)((long long)H * (d + 1) / D);
     if (hi <= lo) continue;
     Replica& r = *s->rep[d];
-    RenderCtx* x = cx.x[d];
+    RenderCtx* x = cx[d];
     DeviceGuard g(r.device);
     float* dst = d_frame;
     // copy gather: the previous frame's band copy out of d_image (on the first device's
@@ -899,30 +969,28 @@ void render_multi_msaa(rt_scene* s, CtxSet& cx, int cam, float* d_frame, hipStre
     }
     RenderParams P = make_params(s, r, cam, lo, 1, 0, 1, 0, dst, per_call ? x->d_cnt.p : r.d_counters.p);
     limit_rows(P, hi - lo);
-    bind_ctx(s, x, P, c);
-    enqueue_samples(s, r, P, n, x->d_samples.p, x->stream, d == 0);
+    WorkSet& ws = x->work;
+    ws.bind(s, c, P);
+    enqueue_samples(s, P, n, ws.samples.p, x->stream, d == 0);
     for (const int row : {lo - 1, hi}) {  // the halo rows the splat of the band's edges reads
       if (row < 0 || row >= H) continue;
       RenderParams Q = make_params(s, r, cam, row, 1, 0, 1, 0, dst, nullptr);
       limit_rows(Q, 1);
-      Q.hits = P.hits;
+      Q.hits = P.hits;  // a halo row shares the band's buffers (it has no more tiles)
       Q.occ = P.occ;
       Q.frames = P.frames;
-      set_schedule(Q, x->d_sched.p);
-      enqueue_samples(s, r, Q, n, x->d_samples.p, x->stream, false);
+      set_schedule(Q, ws.sched.p);
+      enqueue_samples(s, Q, n, ws.samples.p, x->stream, false);
     }
-    enqueue_resolve(s, W, H, n, x->d_samples.p, dst, lo, hi, x->stream);
+    enqueue_resolve(s, W, H, n, ws.samples.p, dst, lo, hi, x->stream);
   }
   DeviceGuard g(s->rep[0]->device);
   gather_parts(s, cx, [&](int d) {  // device d's band (an empty one is skipped)
     const int lo = (int)((long long)H * d / D), hi = (int)((long long)H * (d + 1) / D);
     const size_t off = (size_t)lo * W * 3;
-    return GatherPart{cx.x[d]->d_image.p + off, d_frame + off, (size_t)(hi - lo) * W * 3};
+    return GatherPart{cx[d]->d_image.p + off, d_frame + off, (size_t)(hi - lo) * W * 3};
   });
-  if (s0 != x0->stream) {
-    hip_check(hipEventRecord(x0->ev_out, x0->stream), "event record");
-    hip_check(hipStreamWaitEvent(s0, x0->ev_out, 0), "wait event");
-  }
+  order_after(s0, x0->stream, x0->ev_out);
 }
 
 // One frame (rows row0 + k*row_stride) of a pixel-centre camera over every device of a
@@ -936,7 +1004,7 @@ void render_multi_msaa(rt_scene* s, CtxSet& cx, int cam, float* d_frame, hipStre
 // whose resolve kernel shades the records into the rows (or untile kernel copies the RGB).
 // Counters: `per_call` adds each device's rays to its context's counters (rt_render's stats),
 // else to the replica's (rt_collect_stats).  Caller holds s->multi_mu.
-void render_multi(rt_scene* s, CtxSet& cx, int cam, int row0, int row_stride, float* d_frame,
+void render_multi(rt_scene* s, const CtxList& cx, int cam, int row0, int row_stride, float* d_frame,
                   hipStream_t s0, bool per_call) {
   const int D = (int)s->rep.size();
   const rt_camera& c = s->host.cameras[cam];
@@ -947,17 +1015,16 @@ void render_multi(rt_scene* s, CtxSet& cx, int cam, int row0, int row_stride, fl
   // the other devices' shares travel as 32-bit pixel records where the scene allows, else as RGB
   const bool records = records_ok(s, cam);
   const size_t tile_words = records ? (size_t)kTile * kTile : (size_t)kTileFloats;
-  RenderCtx* x0 = cx.x[0];
+  RenderCtx* x0 = cx[0];
   {
-    DeviceGuard g(s->rep[0]->device);
-    hip_check(hipEventRecord(x0->ev_in, s0), "event record");  // d_frame's earlier work
     // the first device renders its own blocks in place into d_frame (after d_frame's earlier
     // work); the others render tile-major into their slots for the gather
-    hip_check(hipStreamWaitEvent(x0->stream, x0->ev_in, 0), "wait event");
+    DeviceGuard g(s->rep[0]->device);
+    order_after(x0->stream, s0, x0->ev_in);
   }
   for (int d = 0; d < D; d++) {
     Replica& r = *s->rep[d];
-    RenderCtx* x = cx.x[d];
+    RenderCtx* x = cx[d];
     DeviceGuard g(r.device);
     // copy gather: the previous frame's peer copy out of d_out (on the first device's stream)
     // has finished before this frame renders into it
@@ -967,14 +1034,14 @@ void render_multi(rt_scene* s, CtxSet& cx, int cam, int row0, int row_stride, fl
                                  d == 0 ? RT_TILE_BLOCKS
                                         : RT_TILE_MAJOR | RT_TILE_BLOCKS | (records ? RT_TILE_RECORDS : 0),
                                  d == 0 ? d_frame : x->d_out.p, per_call ? x->d_cnt.p : r.d_counters.p);
-    bind_ctx(s, x, P, c);
-    enqueue_frame(s, r, P, 1, nullptr, x->stream, d == 0);
+    x->work.bind(s, c, P);
+    enqueue_frame(s, P, 1, nullptr, x->stream, d == 0);
   }
   DeviceGuard g(s->rep[0]->device);
   x0->d_recv.reserve((size_t)D * slot * tile_words, "alloc gathered slots");
   const size_t count = (size_t)slot * tile_words;  // 4-B words (floats or pixel records)
   gather_parts(s, cx, [&](int d) {
-    return GatherPart{cx.x[d]->d_out.p, x0->d_recv.p + (size_t)d * count, count};
+    return GatherPart{cx[d]->d_out.p, x0->d_recv.p + (size_t)d * count, count};
   });
   // (skip root: the first device's blocks are already in d_frame)
   UntileParams U = untile_params(c, tp, row0, row_stride, D, slot, 0,
@@ -990,10 +1057,7 @@ void render_multi(rt_scene* s, CtxSet& cx, int cam, int row0, int row_stride, fl
   } else if (D > 1) {
     hip_check(launch_untile(U, x0->stream), "untile launch");
   }
-  if (s0 != x0->stream) {
-    hip_check(hipEventRecord(x0->ev_out, x0->stream), "event record");
-    hip_check(hipStreamWaitEvent(s0, x0->ev_out, 0), "wait event");
-  }
+  order_after(s0, x0->stream, x0->ev_out);
 }
 
 // Frees the least recently used scratch no host thread is enqueueing on (its mutex is free:
@@ -1027,11 +1091,9 @@ StreamScratch* scratch_for(rt_scene* s, Replica& r, void* stream, std::unique_lo
   auto x = std::make_unique<StreamScratch>();
   x->stream = stream;
   x->used = ++r.tick;
-  const size_t most = s->most;
   x->done.create(hipEventDisableTiming);
-  x->hits.reserve(most, "alloc hit records");
-  x->occ.reserve(most * occ_words(s->host), "alloc occlusion bits");
-  x->sched.reserve(sched_words_for(most / (kTile * kTile)), "alloc tile schedule");
+  // (growing them later would free buffers the stream's frames in flight use: hipFree waits)
+  x->work.reserve_tiles(s->host, s->most / (kTile * kTile));
   r.streams.push_back(std::move(x));
   held = std::unique_lock<std::mutex>(r.streams.back()->mu);
   return r.streams.back().get();
@@ -1062,8 +1124,7 @@ std::vector<int> single_device(int device) {
 
 // Argument rules shared by the ray-query and radiance-query entries; they need no GPU.
 void check_query_args(const char* fn, const rt_scene* s, const void* rays, long long n,
-                      const void* out, bool out_aligned, int flags,
-                      int known_flags = RT_QUERY_REORDER) {
+                      const void* out, bool out_aligned, int flags, int known_flags) {
   const std::string f(fn);
   if (n < 0) throw std::invalid_argument(f + ": n < 0");
   if (flags & ~known_flags) throw std::invalid_argument(f + ": unknown flag bit");
@@ -1074,34 +1135,64 @@ void check_query_args(const char* fn, const rt_scene* s, const void* rays, long 
   if (s->multi) throw std::domain_error(f + ": ray queries on multi-device scenes are not supported");
 }
 
-// Enqueues the query over d_rays[0, n) on `stream`, at most kQueryMaxLaunch rays per launch;
-// `scratch` (the stream's or the context's) holds the reorder stage's buffers.
-void enqueue_query(rt_scene* s, const Replica& r, const rt_ray* d_rays, long long n, void* d_out,
-                   bool occlusion, int flags, DevBuf<unsigned>& scratch, hipStream_t stream) {
+// One query call: n rays and their n results in device memory; a radiance query's depth.
+struct QueryCall {
+  const rt_ray* rays;
+  long long n;
+  void* out;
+  int depth, flags;
+};
+
+// What the front ends (query_device, query_host) know of a kind of query.  `enqueue` enqueues a
+// call on `stream`, at most kQueryMaxLaunch rays per launch, with the stream's working set.
+struct QueryKind {
+  size_t stride;     // bytes of one result record
+  bool out_aligned;  // results at a 16-byte aligned address
+  int known_flags;
+  bool radiance;  // takes a depth (radiance_depth) and counts its rays into `counters`
+  void (*enqueue)(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws,
+                  unsigned long long* counters, hipStream_t stream);
+};
+
+// The kernels' view of a batch before its rays: the leaf -> object table and the box the reorder
+// stage cuts into origin cells (a root primitive: one cell).
+QueryParams query_params(const rt_scene* s, const Replica& r) {
   const HostScene& h = s->host;
-  const RenderParams P = scene_params(s, r);
-  const bool reorder = (flags & RT_QUERY_REORDER) != 0;
   QueryParams Q;
   std::memset(&Q, 0, sizeof Q);
   Q.leaf_object = r.d_leaf_object.p;
-  if (h.root_kind == kRootNode)  // (a root primitive: one origin cell)
+  if (h.root_kind == kRootNode)
     for (int a = 0; a < 3; a++) {
       const float ext = h.root_box[a + 3] - h.root_box[a];
       Q.box_lo[a] = h.root_box[a];
       Q.box_scale[a] = ext > 0.0f && std::isfinite(ext) ? 1.0f / ext : 0.0f;  // cells: kernel
     }
-  if (reorder) scratch.reserve(query_scratch_words(std::min(n, kQueryMaxLaunch)), "alloc query scratch");
-  const size_t out_stride = occlusion ? 1 : sizeof(rt_ray_hit);
-  for (long long done = 0; done < n; done += kQueryMaxLaunch) {
-    Q.rays = d_rays + done;
-    Q.out = static_cast<char*>(d_out) + (size_t)done * out_stride;
-    Q.n = std::min(n - done, kQueryMaxLaunch);
-    if (reorder) {
-      Q.perm_out = reinterpret_cast<int*>(scratch.p);
-      Q.hist = scratch.p + Q.n;
-      Q.totals = Q.hist + (size_t(1) << query_bin_bits(Q.n));
-    }
-    hip_check(launch_query(P, Q, r.d_nodes.p, occlusion, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
+  return Q;
+}
+
+// Points Q's reorder stage at ws.query for a launch of n rays: the permutation, then the
+// histogram, then the totals.  (A call's first launch is its largest.)
+void carve_reorder(QueryParams& Q, WorkSet& ws, long long n) {
+  ws.query.reserve(query_scratch_words(n), "alloc query scratch");
+  Q.perm_out = reinterpret_cast<int*>(ws.query.p);
+  Q.hist = ws.query.p + n;
+  Q.totals = Q.hist + (size_t(1) << query_bin_bits(n));
+}
+
+// Closest hits (rt_ray_hit records) or occlusion flags (bytes).
+template <bool OCCLUSION>
+void enqueue_hits(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws,
+                  unsigned long long*, hipStream_t stream) {
+  const RenderParams P = scene_params(s, r);
+  const bool reorder = (q.flags & RT_QUERY_REORDER) != 0;
+  const size_t stride = OCCLUSION ? 1 : sizeof(rt_ray_hit);
+  QueryParams Q = query_params(s, r);
+  for (long long done = 0; done < q.n; done += kQueryMaxLaunch) {
+    Q.rays = q.rays + done;
+    Q.out = static_cast<char*>(q.out) + (size_t)done * stride;
+    Q.n = std::min(q.n - done, kQueryMaxLaunch);
+    if (reorder) carve_reorder(Q, ws, Q.n);
+    hip_check(launch_query(P, Q, r.d_nodes.p, OCCLUSION, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
                            s->deep, s->has_spheres, stream),
               "query launch");
   }
@@ -1116,25 +1207,18 @@ int radiance_depth(const char* fn, const rt_scene* s, int depth) {
 
 size_t round_up_wave(long long n) { return (size_t)((n + 63) / 64 * 64); }
 
-// Enqueues the radiance query over d_rays[0, n) at `depth` on `stream`.  `scratch` holds the
-// reorder stage's buffers and `frames` the ray-tree frames of one chunk (the stream's or the
-// context's); a query that cannot recurse touches neither `frames` nor the limit.
-void enqueue_radiance(rt_scene* s, const Replica& r, const rt_ray* d_rays, long long n, int depth,
-                      rt_radiance* d_out, int flags, DevBuf<unsigned>& scratch,
-                      DevBuf<float>& frames, unsigned long long* counters, hipStream_t stream) {
-  const HostScene& h = s->host;
+// Radiance (rt_radiance records) at q.depth.  ws.frames holds the ray-tree frames of one chunk;
+// a query that cannot recurse touches neither it nor the limit.
+void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws,
+                      unsigned long long* counters, hipStream_t stream) {
+  const long long n = q.n;
+  const int depth = q.depth;
+  DevBuf<float>& frames = ws.frames;
   RenderParams P = scene_params(s, r);
   P.counters = counters;
-  const bool reorder = (flags & RT_QUERY_REORDER) != 0;
+  const bool reorder = (q.flags & RT_QUERY_REORDER) != 0;
   const bool recurse = depth > 0 && s->needs_recursion;
-  QueryParams Q;
-  std::memset(&Q, 0, sizeof Q);
-  if (h.root_kind == kRootNode)
-    for (int a = 0; a < 3; a++) {
-      const float ext = h.root_box[a + 3] - h.root_box[a];
-      Q.box_lo[a] = h.root_box[a];
-      Q.box_scale[a] = ext > 0.0f && std::isfinite(ext) ? 1.0f / ext : 0.0f;
-    }
+  QueryParams Q = query_params(s, r);
   long long chunk = kQueryMaxLaunch;  // rays per launch
   if (recurse) {
     const long long fit = (long long)(s->radiance_limit.load() / radiance_frame_bytes(depth)) /
@@ -1145,23 +1229,20 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const rt_ray* d_rays, long 
     frames.reserve(std::min((size_t)chunk, round_up_wave(n)) * kRadianceFrameFloats * (size_t)(depth + 1),
                    "alloc ray-tree frames");
   }
-  if (reorder) scratch.reserve(query_scratch_words(std::min(n, kQueryMaxLaunch)), "alloc query scratch");
   RadianceParams R;
   R.frames = recurse ? frames.p : nullptr;
   R.lanes = (long long)std::min((size_t)chunk, round_up_wave(n));
   R.depth = depth;
-  R.in_medium = (flags & RT_QUERY_IN_MEDIUM) ? 1 : 0;
+  R.in_medium = (q.flags & RT_QUERY_IN_MEDIUM) ? 1 : 0;
   // one permutation per kQueryMaxLaunch rays (32-bit entries), then that part chunk by chunk
   for (long long done = 0; done < n; done += kQueryMaxLaunch) {
     const long long part = std::min(n - done, kQueryMaxLaunch);
-    Q.rays = d_rays + done;
-    Q.out = d_out + done;
+    Q.rays = q.rays + done;
+    Q.out = static_cast<rt_radiance*>(q.out) + done;
     Q.n = part;
     Q.perm = nullptr;
     if (reorder) {
-      Q.perm_out = reinterpret_cast<int*>(scratch.p);
-      Q.hist = scratch.p + part;
-      Q.totals = Q.hist + (size_t(1) << query_bin_bits(part));
+      carve_reorder(Q, ws, part);
       hip_check(launch_query_sort(Q, stream), "query sort launch");
       Q.perm = Q.perm_out;
     }
@@ -1175,48 +1256,168 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const rt_ray* d_rays, long 
   }
 }
 
-int query_device(const char* fn, rt_scene* s, const rt_ray* d_rays, long long n, void* d_out,
-                 bool occlusion, int flags, void* stream) {
+const QueryKind kClosestHit{sizeof(rt_ray_hit), true, RT_QUERY_REORDER, false, enqueue_hits<false>};
+const QueryKind kOcclusion{1, false, RT_QUERY_REORDER, false, enqueue_hits<true>};
+const QueryKind kRadiance{sizeof(rt_radiance), true, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM, true,
+                          enqueue_radiance};
+
+// The front end of the `_device` entries: rays and results in device memory, enqueued on the
+// caller's stream with its working set; the ray counts go to the scene's counters.
+int query_device(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ray* d_rays,
+                 long long n, int depth, void* d_out, int flags, void* stream) {
   return guarded([&] {
-    check_query_args(fn, s, d_rays, n, d_out, !occlusion, flags);
+    check_query_args(fn, s, d_rays, n, d_out, kind.out_aligned, flags, kind.known_flags);
+    if (kind.radiance) depth = radiance_depth(fn, s, depth);
     if (n == 0) return RT_OK;
     Replica& r = *s->rep[0];
     DeviceGuard g(r.device);
     std::unique_lock<std::mutex> lk;
     StreamScratch* sc = scratch_for(s, r, stream, lk);
-    enqueue_query(s, r, d_rays, n, d_out, occlusion, flags, sc->query, (hipStream_t)stream);
+    kind.enqueue(s, r, QueryCall{d_rays, n, d_out, depth, flags}, sc->work, r.d_counters.p,
+                 (hipStream_t)stream);
     hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
     return RT_OK;
   });
 }
 
-int query_host(const char* fn, rt_scene* s, const rt_ray* rays, long long n, void* out,
-               bool occlusion, int flags) {
+// The front end of the host entries: rays up, the query on a pooled context, results down.  A
+// radiance query reports its own ray counts and kernel time in `stats` (nullable), as rt_render.
+int query_host(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ray* rays, long long n,
+               int depth, void* out, int flags, rt_stats* stats) {
   return guarded([&] {
-    check_query_args(fn, s, rays, n, out, !occlusion, flags);
+    check_query_args(fn, s, rays, n, out, kind.out_aligned, flags, kind.known_flags);
+    if (kind.radiance) depth = radiance_depth(fn, s, depth);
+    if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return RT_OK;
     Replica& r = *s->rep[0];
     DeviceGuard g(r.device);
-    struct Lease {  // a pooled context, handed back on every path
-      Replica& r;
-      RenderCtx* x;
-      ~Lease() {
-        (void)hipStreamSynchronize(x->stream);
-        release_ctx(r, x);
-      }
-    } lease{r, acquire_ctx(r)};
-    RenderCtx* x = lease.x;
-    const size_t out_bytes = occlusion ? (size_t)n : (size_t)n * sizeof(rt_ray_hit);
+    CtxLease lease(s, 1);
+    RenderCtx* x = lease.x[0];
+    const size_t out_bytes = (size_t)n * kind.stride;
     x->d_rays.reserve((size_t)n, "alloc rays");
     x->d_ray_out.reserve((out_bytes + sizeof(rt_ray_hit) - 1) / sizeof(rt_ray_hit), "alloc results");
     hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
                              x->stream), "upload rays");
-    enqueue_query(s, r, x->d_rays.p, n, x->d_ray_out.p, occlusion, flags, x->d_query, x->stream);
-    hip_check(hipMemcpyAsync(out, x->d_ray_out.p, out_bytes, hipMemcpyDeviceToHost, x->stream),
+    const QueryCall q{x->d_rays.p, n, x->d_ray_out.p, depth, flags};
+    std::optional<CallCounters> counted;
+    if (kind.radiance) counted.emplace(s, lease.x);
+    kind.enqueue(s, r, q, x->work, counted ? x->d_cnt.p : nullptr, x->stream);
+    if (counted) counted->stop();
+    hip_check(hipMemcpyAsync(out, q.out, out_bytes, hipMemcpyDeviceToHost, x->stream),
               "download results");
-    hip_check(hipStreamSynchronize(x->stream), "synchronize query");
+    if (counted)
+      counted->read(stats);
+    else
+      hip_check(hipStreamSynchronize(x->stream), "synchronize query");
     return RT_OK;
   });
+}
+
+// One rt_render call: rows row0 + k row_stride of camera `cam` into the caller's frame `out`.
+struct HostFrame {
+  rt_scene* s;
+  int cam, row0, row_stride;
+  float* out;
+  const rt_camera& camera() const { return s->host.cameras[cam]; }
+};
+
+// The selection's rows [lr0, lr1) from the device frame to the caller's (strided 2D copies
+// leave the rows outside the selection untouched).
+void copy_rows(const HostFrame& f, const float* d_frame, int lr0, int lr1, hipStream_t st) {
+  if (lr1 <= lr0) return;
+  const rt_camera& c = f.camera();
+  const size_t row_bytes = (size_t)c.width * 3 * sizeof(float);
+  const size_t off = (size_t)(f.row0 + (size_t)lr0 * f.row_stride) * c.width * 3;
+  hip_check(hipMemcpy2DAsync(f.out + off, row_bytes * f.row_stride, d_frame + off,
+                             row_bytes * f.row_stride, row_bytes, (size_t)(lr1 - lr0),
+                             hipMemcpyDeviceToHost, st),
+            "copy rows");
+}
+
+// The device-visible address of a caller buffer in pinned host memory (hipHostMalloc /
+// registered, e.g. torch pin_memory); nullptr for pageable memory.
+float* pinned_device_pointer(float* host) {
+  void* dp = nullptr;
+  if (hipHostGetDevicePointer(&dp, host, 0) == hipSuccess && dp) return static_cast<float*>(dp);
+  (void)hipGetLastError();  // pageable memory: not an error here
+  return nullptr;
+}
+
+// rt_render into pinned memory: the frame kernel writes the caller's buffer itself, through
+// its device-visible address `direct`; no copy.
+void render_pinned(const HostFrame& f, RenderCtx* x, float* direct, CallCounters& counted) {
+  rt_scene* s = f.s;
+  Replica& r = *s->rep[0];
+  RenderParams P = make_params(s, r, f.cam, f.row0, f.row_stride, 0, 1, 0, direct, x->d_cnt.p);
+  x->work.bind(s, f.camera(), P);
+  // block order: the frame is bound by its writes over PCIe, which the heavy-first (cold)
+  // order scatters (0.674 -> 0.742 ms per C3 frame, profiles/r06/ab_dropin_cold.jsonl)
+  P.tile_cost = nullptr;
+  P.pair_rows = RT_PAIR_ROWS;
+  enqueue_frame(s, P, 1, nullptr, x->stream, true);
+  counted.stop();
+}
+
+// rt_render into pageable memory (the drop-in seam): the frame as `chunks`
+// bands of tile rows, one launch each on the context's stream; each band goes to the caller's
+// buffer on the copy stream as soon as its launch is done, while the next bands render.
+void render_banded(const HostFrame& f, RenderCtx* x, int chunks, CallCounters& counted) {
+  rt_scene* s = f.s;
+  Replica& r = *s->rep[0];
+  const rt_camera& c = f.camera();
+  const TilePlan tp = plan(c, f.row0, f.row_stride);
+  const int tiles_y = tp.tiles_total / tp.tiles_x;
+  auto band = [&](int k) { return (int)((long long)tiles_y * k / chunks); };  // its first tile row
+  x->d_out.reserve((size_t)c.width * c.height * 3, "alloc frame");
+  x->copy_stream.create("copy stream");
+  for (int k = 0; k < chunks; k++) {
+    RenderParams P = make_params(s, r, f.cam, f.row0, f.row_stride, band(k) * tp.tiles_x, 1, 0,
+                                 x->d_out.p, x->d_cnt.p);
+    P.num_sel_tiles = (band(k + 1) - band(k)) * tp.tiles_x;
+    x->work.bind(s, c, P);
+    P.tile_cost = nullptr;  // no dispatch order for a next frame (nothing reuses it here)
+    enqueue_frame(s, P, 1, nullptr, x->stream, true);
+    x->ev_chunk[k].create(hipEventDisableTiming);
+    hip_check(hipEventRecord(x->ev_chunk[k], x->stream), "event record");
+  }
+  counted.stop();
+  // no copy into the caller's buffer is pending when a failure below leaves this call
+  struct Drain {
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(st);
+    }
+  } drain{x->copy_stream};
+  for (int k = 0; k < chunks; k++) {
+    hip_check(hipStreamWaitEvent(x->copy_stream, x->ev_chunk[k], 0), "wait band");
+    copy_rows(f, x->d_out.p, kTile * band(k), std::min(tp.rows, kTile * band(k + 1)), x->copy_stream);
+  }
+  drain.armed = false;
+  hip_check(hipStreamSynchronize(x->copy_stream), "synchronize copies");
+}
+
+// Every other rt_render (MSAA cameras, multi-device scenes, frames of one tile row): the frame
+// into a device buffer, then its rows to the caller's.
+void render_then_copy(const HostFrame& f, const CtxList& cx, CallCounters& counted) {
+  rt_scene* s = f.s;
+  const rt_camera& c = f.camera();
+  RenderCtx* x = cx[0];
+  // (a multi-device frame's d_out holds the first device's tile slot)
+  DevBuf<float>& frame = s->multi ? x->d_image : x->d_out;
+  frame.reserve((size_t)c.width * c.height * 3, "alloc frame");
+  if (s->multi && c.num_samples > 1) {
+    render_multi_msaa(s, cx, f.cam, frame.p, x->stream, true);
+  } else if (s->multi) {
+    render_multi(s, cx, f.cam, f.row0, f.row_stride, frame.p, x->stream, true);
+  } else {
+    Replica& r = *s->rep[0];
+    RenderParams P = make_params(s, r, f.cam, f.row0, f.row_stride, 0, 1, 0, frame.p, x->d_cnt.p);
+    x->work.bind(s, c, P);
+    enqueue_frame(s, P, c.num_samples, x->work.samples.p, x->stream, true);
+  }
+  counted.stop();
+  copy_rows(f, frame.p, 0, plan(c, f.row0, f.row_stride).rows, x->stream);
 }
 
 }  // namespace
@@ -1442,7 +1643,10 @@ int rt_render_device_range(rt_scene* s, int cam, int row0, int row_stride, int t
       if (tile_begin != 0 || tile_step != 1 || tile_major || tile_count >= 0)
         throw std::domain_error("multi-device scenes render whole row-major frames only");
       std::lock_guard<std::mutex> lk(s->multi_mu);
-      CtxSet cx(s, s->rep.size(), stream);
+      // the caller stream's own contexts: consecutive frames on different caller streams run on
+      // different device streams, and frames on one caller stream stay ordered
+      CtxList cx;
+      for (auto& r : s->rep) cx.push_back(stream_ctx_for(*r, stream));
       if (c.num_samples > 1)
         render_multi_msaa(s, cx, cam, d_out, (hipStream_t)stream, false);
       else
@@ -1455,30 +1659,19 @@ int rt_render_device_range(rt_scene* s, int cam, int row0, int row_stride, int t
     StreamScratch* sc = scratch_for(s, r, stream, lk);
     RenderParams P = make_params(s, r, cam, row0, row_stride, tile_begin, tile_step, tile_major,
                                  d_out, r.d_counters.p);
-    P.hits = sc->hits.p;
-    P.occ = sc->occ.p;
-    set_schedule(P, sc->sched.p);
     const int unit_tiles = P.block_deal ? 4 : 1;  // tile_count counts deal units
-    if (tile_count >= 0 && (long long)tile_count * unit_tiles < P.num_sel_tiles) {
-      if (c.num_samples > 1) throw std::domain_error("NumSamples > 1 renders whole row-major frames only");
-      P.num_sel_tiles = tile_count * unit_tiles;
-    }
-    if (s->needs_recursion) {
-      sc->frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
-      P.frames = sc->frames.p;
-    }
-    if (c.num_samples > 1) {
-      if (tile_begin != 0 || tile_step != 1 || tile_major)
-        throw std::domain_error("NumSamples > 1 renders whole row-major frames only");
-      sc->samples.reserve(sample_floats(c), "alloc MSAA samples");
-    }
+    const bool trimmed = tile_count >= 0 && (long long)tile_count * unit_tiles < P.num_sel_tiles;
+    if (c.num_samples > 1 && (trimmed || tile_begin != 0 || tile_step != 1 || tile_major))
+      throw std::domain_error("NumSamples > 1 renders whole row-major frames only");
+    if (trimmed) P.num_sel_tiles = tile_count * unit_tiles;
+    sc->work.bind(s, c, P);  // (the selection is final: the schedule's layout depends on it)
     // warm order: a frame of the same selection as the stream's previous one
     // dispatches its primary kernel heaviest-first by that frame's measured tile costs
     const std::array<long long, 7> key{cam, row0, row_stride, tile_begin, tile_step,
                                        P.num_sel_tiles, P.block_deal};
     const bool orderable = c.num_samples <= 1 && !P.frames && P.num_lights > 0;
     P.primary_order = orderable && sc->order_valid && sc->order_key == key ? 1 : 0;
-    enqueue_frame(s, r, P, c.num_samples, sc->samples.p, (hipStream_t)stream, true);
+    enqueue_frame(s, P, c.num_samples, sc->work.samples.p, (hipStream_t)stream, true);
     hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
     sc->order_key = key;
     sc->order_valid = orderable;
@@ -1520,7 +1713,7 @@ int rt_tile_costs(rt_scene* s, void* stream, unsigned* host_out, int capacity) {
     const long long n = x->order_key[5];  // the last selection's tiles
     if (n > capacity) throw std::invalid_argument("rt_tile_costs: capacity below the frame's tiles");
     hip_check(hipStreamSynchronize((hipStream_t)stream), "synchronize stream");
-    hip_check(hipMemcpy(host_out, x->sched.p + sched_snap_offset((unsigned long long)n),
+    hip_check(hipMemcpy(host_out, x->work.sched.p + sched_snap_offset((unsigned long long)n),
                         (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost),
               "read tile costs");
     return (int)n;
@@ -1571,88 +1764,32 @@ int rt_ray_query_version(void) { return 1; }
 
 int rt_trace_rays_device(rt_scene* s, const rt_ray* d_rays, long long n, rt_ray_hit* d_hits,
                          int flags, void* stream) {
-  return query_device("rt_trace_rays_device", s, d_rays, n, d_hits, false, flags, stream);
+  return query_device("rt_trace_rays_device", kClosestHit, s, d_rays, n, 0, d_hits, flags, stream);
 }
 
 int rt_occluded_device(rt_scene* s, const rt_ray* d_rays, long long n, unsigned char* d_occ,
                        int flags, void* stream) {
-  return query_device("rt_occluded_device", s, d_rays, n, d_occ, true, flags, stream);
+  return query_device("rt_occluded_device", kOcclusion, s, d_rays, n, 0, d_occ, flags, stream);
 }
 
 int rt_trace_rays(rt_scene* s, const rt_ray* rays, long long n, rt_ray_hit* hits, int flags) {
-  return query_host("rt_trace_rays", s, rays, n, hits, false, flags);
+  return query_host("rt_trace_rays", kClosestHit, s, rays, n, 0, hits, flags, nullptr);
 }
 
 int rt_occluded(rt_scene* s, const rt_ray* rays, long long n, unsigned char* occ, int flags) {
-  return query_host("rt_occluded", s, rays, n, occ, true, flags);
+  return query_host("rt_occluded", kOcclusion, s, rays, n, 0, occ, flags, nullptr);
 }
 
 int rt_radiance_query_version(void) { return 1; }
 
 int rt_shade_rays_device(rt_scene* s, const rt_ray* d_rays, long long n, int depth,
                          rt_radiance* d_out, int flags, void* stream) {
-  const char* fn = "rt_shade_rays_device";
-  return guarded([&] {
-    check_query_args(fn, s, d_rays, n, d_out, true, flags, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM);
-    depth = radiance_depth(fn, s, depth);
-    if (n == 0) return RT_OK;
-    Replica& r = *s->rep[0];
-    DeviceGuard g(r.device);
-    std::unique_lock<std::mutex> lk;
-    StreamScratch* sc = scratch_for(s, r, stream, lk);
-    enqueue_radiance(s, r, d_rays, n, depth, d_out, flags, sc->query, sc->frames, r.d_counters.p,
-                     (hipStream_t)stream);
-    hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
-    return RT_OK;
-  });
+  return query_device("rt_shade_rays_device", kRadiance, s, d_rays, n, depth, d_out, flags, stream);
 }
 
 int rt_shade_rays(rt_scene* s, const rt_ray* rays, long long n, int depth, rt_radiance* out,
                   int flags, rt_stats* stats) {
-  const char* fn = "rt_shade_rays";
-  return guarded([&] {
-    check_query_args(fn, s, rays, n, out, true, flags, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM);
-    depth = radiance_depth(fn, s, depth);
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n == 0) return RT_OK;
-    Replica& r = *s->rep[0];
-    DeviceGuard g(r.device);
-    struct Lease {  // a pooled context, handed back on every path
-      Replica& r;
-      RenderCtx* x;
-      ~Lease() {
-        (void)hipStreamSynchronize(x->stream);
-        release_ctx(r, x);
-      }
-    } lease{r, acquire_ctx(r)};
-    RenderCtx* x = lease.x;
-    static_assert(sizeof(rt_ray_hit) == 2 * sizeof(rt_radiance), "result buffer sizing");
-    x->d_rays.reserve((size_t)n, "alloc rays");
-    x->d_ray_out.reserve(((size_t)n + 1) / 2, "alloc results");
-    rt_radiance* d_out = reinterpret_cast<rt_radiance*>(x->d_ray_out.p);
-    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
-                             x->stream), "upload rays");
-    // this call's own counts, through the context's counter buffer (as rt_render)
-    hip_check(hipMemsetAsync(x->d_cnt.p, 0, sizeof(unsigned long long) * kCounterAlloc, x->stream),
-              "zero counters");
-    hip_check(hipEventRecord(x->e0, x->stream), "event record");
-    enqueue_radiance(s, r, x->d_rays.p, n, depth, d_out, flags, x->d_query, x->d_frames, x->d_cnt.p,
-                     x->stream);
-    hip_check(hipEventRecord(x->e1, x->stream), "event record");
-    hip_check(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_radiance), hipMemcpyDeviceToHost,
-                             x->stream), "download results");
-    std::vector<unsigned long long> cnt(kCounterAlloc);
-    hip_check(hipMemcpyAsync(cnt.data(), x->d_cnt.p, kCounterAlloc * sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, x->stream), "copy counters");
-    hip_check(hipStreamSynchronize(x->stream), "synchronize query");
-    if (stats) {
-      add_counters(cnt, stats);
-      float ms = 0;
-      hip_check(hipEventElapsedTime(&ms, x->e0, x->e1), "elapsed");
-      stats->kernel_ms = ms;
-    }
-    return RT_OK;
-  });
+  return query_host("rt_shade_rays", kRadiance, s, rays, n, depth, out, flags, stats);
 }
 
 int rt_set_radiance_scratch_limit(rt_scene* s, size_t bytes) {
@@ -1672,7 +1809,7 @@ long long rt_stream_frame_scratch_bytes(rt_scene* s, void* stream) {
   for (auto& rp : s->rep) {
     std::lock_guard<std::mutex> lk(rp->mu);
     for (auto& x : rp->streams)
-      if (x->stream == stream) bytes += (long long)(x->frames.cap * sizeof(float));
+      if (x->stream == stream) bytes += (long long)(x->work.frames.cap * sizeof(float));
   }
   return bytes;
 }
@@ -1732,14 +1869,7 @@ int rt_collect_stats(rt_scene* s, rt_stats* stats) {
   if (!s || !stats) return set_error(RT_E_INVALID, "rt_collect_stats: NULL argument");
   return guarded([&] {
     std::memset(stats, 0, sizeof *stats);
-    for (auto& rp : s->rep) {
-      DeviceGuard g(rp->device);
-      std::vector<unsigned long long> c(kCounterWidth * kCounterRows);
-      hip_check(hipMemcpy(c.data(), rp->d_counters.p, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
-                "read counters");
-      hip_check(hipMemset(rp->d_counters.p, 0, c.size() * sizeof c[0]), "reset counters");
-      add_counters(c, stats);
-    }
+    for (auto& rp : s->rep) add_counters(take_counters(*rp), stats);
     return RT_OK;
   });
 }
@@ -1749,11 +1879,7 @@ int rt_debug_counters(rt_scene* s, long long* out16) {
   return guarded([&] {
     for (int k = 0; k < kCounterWidth; k++) out16[k] = 0;
     for (auto& rp : s->rep) {
-      DeviceGuard g(rp->device);
-      std::vector<unsigned long long> c(kCounterWidth * kCounterRows);
-      hip_check(hipMemcpy(c.data(), rp->d_counters.p, c.size() * sizeof c[0], hipMemcpyDeviceToHost),
-                "read counters");
-      hip_check(hipMemset(rp->d_counters.p, 0, c.size() * sizeof c[0]), "reset counters");
+      const std::vector<unsigned long long> c = take_counters(*rp);
       for (int k = 0; k < kCounterWidth; k++) {
         unsigned long long sum = 0;
         for (int r = 0; r < kCounterRows; r++) sum += c[kCounterWidth * r + k];
@@ -1804,131 +1930,22 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
     const rt_camera& c = s->host.cameras[cam];
     const TilePlan tp = plan(c, row0, row_stride);
     if (tp.rows == 0) return RT_OK;
-    const bool multi = s->multi;
     std::unique_lock<std::mutex> multi_lock(s->multi_mu, std::defer_lock);
-    if (multi) multi_lock.lock();
-    CtxSet cx(s, multi ? s->rep.size() : 1);
-    Replica& r = *s->rep[0];
-    RenderCtx* x = cx.x[0];
-    DeviceGuard g(r.device);
-    const size_t frame = (size_t)c.width * c.height * 3;
-    float* d_frame = nullptr;
-    if (multi) {  // (d_out holds the first device's tile slot)
-      x->d_image.reserve(frame, "alloc frame");
-      d_frame = x->d_image.p;
-    } else {
-      x->d_out.reserve(frame, "alloc frame");
-      d_frame = x->d_out.p;
-    }
-    // Counters are per scene; this call reports its own deltas via the contexts' buffers.
-    for (size_t d = 0; d < cx.x.size(); d++) {
-      DeviceGuard gd(s->rep[d]->device);
-      hip_check(hipMemsetAsync(cx.x[d]->d_cnt.p, 0,
-                               sizeof(unsigned long long) * kCounterWidth * kCounterRows,
-                               cx.x[d]->stream),
-                "zero counters");
-    }
-    hip_check(hipEventRecord(x->e0, x->stream), "event record");
-    // rows j = row0 + k*row_stride only: strided 2D copies leave the others untouched
-    const size_t row_bytes = (size_t)c.width * 3 * sizeof(float);
-    auto copy_rows = [&](int lr0, int lr1, hipStream_t st) {  // logical rows [lr0, lr1)
-      if (lr1 <= lr0) return;
-      const size_t off = (size_t)(row0 + (size_t)lr0 * row_stride) * c.width * 3;
-      hip_check(hipMemcpy2DAsync(out_rgb + off, row_bytes * row_stride, d_frame + off,
-                                 row_bytes * row_stride, row_bytes, (size_t)(lr1 - lr0),
-                                 hipMemcpyDeviceToHost, st),
-                "copy rows");
-    };
-    const int tiles_y = tp.tiles_total / tp.tiles_x;
-    const int chunks = std::min(kRenderChunks, tiles_y);
-    // a caller buffer in pinned host memory (hipHostMalloc / registered, e.g. torch pin_memory)
-    // is written by the frame kernel itself, through its device-visible address: no copy
-    float* direct = nullptr;
-    if (!multi && c.num_samples <= 1 && RT_DIRECT_PINNED) {
-      void* dp = nullptr;
-      if (hipHostGetDevicePointer(&dp, out_rgb, 0) == hipSuccess && dp)
-        direct = static_cast<float*>(dp);
-      else
-        (void)hipGetLastError();  // pageable memory: not an error here
-    }
-    if (direct) {
-      RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, direct, x->d_cnt.p);
-      bind_ctx(s, x, P, c);
-      // block order: the frame is bound by its writes over PCIe, which the heavy-first (cold)
-      // order scatters (0.674 -> 0.742 ms per C3 frame, profiles/r06/ab_dropin_cold.jsonl)
-      P.tile_cost = nullptr;
-#ifndef RT_PAIR_ROWS  // (A/B builds: 0 = each wave writes its own tile)
-#define RT_PAIR_ROWS 1
-#endif
-      P.pair_rows = RT_PAIR_ROWS;
-      enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
-      hip_check(hipEventRecord(x->e1, x->stream), "event record");
-    } else if (!multi && c.num_samples <= 1 && chunks > 1) {
-      // the drop-in seam: the frame as `chunks` bands of tile rows, one
-      // launch each on the context's stream; each band goes to the caller's buffer on the copy
-      // stream as soon as its launch is done, while the next bands render
-      x->copy_stream.create("copy stream");
-      for (int k = 0; k < chunks; k++) {
-        const int ty0 = (int)((long long)tiles_y * k / chunks);
-        const int ty1 = (int)((long long)tiles_y * (k + 1) / chunks);
-        RenderParams P = make_params(s, r, cam, row0, row_stride, ty0 * tp.tiles_x, 1, 0, d_frame,
-                                     x->d_cnt.p);
-        P.num_sel_tiles = (ty1 - ty0) * tp.tiles_x;
-        bind_ctx(s, x, P, c);
-        P.tile_cost = nullptr;  // no dispatch order for a next frame (nothing reuses it here)
-        enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
-        x->ev_chunk[k].create(hipEventDisableTiming);
-        hip_check(hipEventRecord(x->ev_chunk[k], x->stream), "event record");
-      }
-      hip_check(hipEventRecord(x->e1, x->stream), "event record");
-      // no copy into out_rgb is pending when a failure below leaves this call
-      struct Drain {
-        hipStream_t st;
-        bool armed = true;
-        ~Drain() {
-          if (armed) (void)hipStreamSynchronize(st);
-        }
-      } drain{x->copy_stream};
-      for (int k = 0; k < chunks; k++) {
-        const int ty0 = (int)((long long)tiles_y * k / chunks);
-        const int ty1 = (int)((long long)tiles_y * (k + 1) / chunks);
-        hip_check(hipStreamWaitEvent(x->copy_stream, x->ev_chunk[k], 0), "wait band");
-        copy_rows(kTile * ty0, std::min(tp.rows, kTile * ty1), x->copy_stream);
-      }
-      drain.armed = false;
-      hip_check(hipStreamSynchronize(x->copy_stream), "synchronize copies");
-    } else {
-      if (multi && c.num_samples > 1) {
-        render_multi_msaa(s, cx, cam, d_frame, x->stream, true);
-      } else if (multi) {
-        render_multi(s, cx, cam, row0, row_stride, d_frame, x->stream, true);
-      } else {
-        RenderParams P = make_params(s, r, cam, row0, row_stride, 0, 1, 0, d_frame, x->d_cnt.p);
-        bind_ctx(s, x, P, c);
-        enqueue_frame(s, r, P, c.num_samples, x->d_samples.p, x->stream, true);
-      }
-      hip_check(hipEventRecord(x->e1, x->stream), "event record");
-      copy_rows(0, tp.rows, x->stream);
-    }
-    std::vector<std::vector<unsigned long long>> cnt(cx.x.size(),
-                                                     std::vector<unsigned long long>(kCounterAlloc));
-    for (size_t d = 0; d < cx.x.size(); d++) {
-      DeviceGuard gd(s->rep[d]->device);
-      hip_check(hipMemcpyAsync(cnt[d].data(), cx.x[d]->d_cnt.p, kCounterAlloc * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, cx.x[d]->stream),
-                "copy counters");
-    }
-    for (size_t d = 0; d < cx.x.size(); d++) {
-      DeviceGuard gd(s->rep[d]->device);
-      hip_check(hipStreamSynchronize(cx.x[d]->stream), "synchronize");
-    }
-    if (stats) {
-      std::memset(stats, 0, sizeof *stats);
-      for (auto& v : cnt) add_counters(v, stats);
-      float ms = 0;
-      hip_check(hipEventElapsedTime(&ms, x->e0, x->e1), "elapsed");
-      stats->kernel_ms = ms;
-    }
+    if (s->multi) multi_lock.lock();
+    CtxLease lease(s, s->multi ? s->rep.size() : 1);
+    DeviceGuard g(s->rep[0]->device);
+    CallCounters counted(s, lease.x);
+    const HostFrame f{s, cam, row0, row_stride, out_rgb};
+    const bool one_pass = !s->multi && c.num_samples <= 1;  // one device, pixel-centre camera
+    const int chunks = std::min(kRenderChunks, tp.tiles_total / tp.tiles_x);
+    float* direct = one_pass && RT_DIRECT_PINNED ? pinned_device_pointer(out_rgb) : nullptr;
+    if (direct)
+      render_pinned(f, lease.x[0], direct, counted);
+    else if (one_pass && chunks > 1)
+      render_banded(f, lease.x[0], chunks, counted);
+    else
+      render_then_copy(f, lease.x, counted);
+    counted.read(stats);
     return RT_OK;
   });
 }

@@ -231,9 +231,14 @@ struct UntileParams {
   int skip_root;    // 1: rank 0's units are left alone (it rendered them in place)
 };
 
-// Words of the per-stream schedule buffer for a launch of `tiles` selected tiles: tile costs
-// + the unit order lists (order_layout in rt_kernels.hip stays below sched_snap_offset), then
-// the snapshot of the tile costs the order kernel read (rt_tile_costs) in the last `tiles` words.
+// The schedule buffer (`sched`) of a launch of `tiles` selected tiles, sched_words_for(tiles)
+// words, `tiles` being the launch's final num_sel_tiles:
+//   [0, tiles)                         tile costs the frame kernel measures (RenderParams::tile_cost)
+//   [tiles, sched_snap_offset(tiles))  the unit order lists, regions x order_stride words
+//                                      (RenderParams::unit_order; order_geometry in rt_kernels.hip
+//                                      runs a launch whose lists would not fit in block order)
+//   [sched_snap_offset(tiles), +tiles) the snapshot of the costs the order kernel sorted
+//                                      (rt_tile_costs)
 constexpr unsigned long long sched_words_for(unsigned long long tiles) { return 10 * tiles + 64; }
 constexpr unsigned long long sched_snap_offset(unsigned long long tiles) { return 9 * tiles + 64; }
 

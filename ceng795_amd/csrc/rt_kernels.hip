@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "rt_internal.h"
@@ -1946,6 +1947,36 @@ static inline void mark(const hipEvent_t* marks, int k, hipStream_t stream) {
   if (marks) (void)hipEventRecord(marks[k], stream);
 }
 
+// Calls f(FAST, DEEP, SPHERES) with the three flags as std::bool_constants: the kernel variant
+// of a frame, query or radiance launch.  (The branches' order is the variants' order in the code
+// object: FAST ones first, and among them plain before DEEP before SPHERES.)
+template <typename F>
+static void dispatch_variant(bool fast, bool deep, bool spheres, F&& f) {
+  auto pick = [](bool b, auto&& g) {
+    if (!b)
+      g(std::false_type{});
+    else
+      g(std::true_type{});
+  };
+  pick(!fast, [&](auto slow) {
+    pick(deep, [&](auto de) {
+      pick(spheres, [&](auto sp) { f(std::bool_constant<!decltype(slow)::value>{}, de, sp); });
+    });
+  });
+}
+
+// FAST walks the culling tree: only when the scene has one (a root primitive or a tree of one
+// treelet has none, accel_build.cpp).
+static bool use_fast(const RenderParams& P, bool fast) {
+  return fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
+}
+
+// Dynamic LDS of a workgroup of `waves` waves: the DEEP variants' per-wave stacks.
+template <bool DEEP>
+constexpr size_t deep_lds_bytes(int waves) {
+  return DEEP ? sizeof(int) * kDeepWords * kDeepStack * waves : 0;
+}
+
 // Dispatch-order geometry of a traversal launch: units of one traversal
 // workgroup, `regions` regions of `chunk`-unit chunks (tile_block: half a row of 2x1 blocks), LPT
 // within each region.  Sets T's tile_block and order_* fields, the launch's unit count (tblocks)
@@ -1980,7 +2011,9 @@ static bool order_geometry(RenderParams& T, int& tblocks, int& per_region) {
   T.order_split = RT_ORDER_SPLIT && region_tiles <= RT_SPLIT_MAX_TILES
                       ? max(1, min(kMaxSplit, region_tiles / RT_SPLIT_DIV) / kTraceWaves) : 0;
   T.order_stride = per_region + (kQuadrants - 1) * T.order_split;
-  return (unsigned long long)T.num_sel_tiles + (unsigned long long)T.order_regions * T.order_stride <=
+  // the order lists end below the cost snapshot (sched layout: rt_internal.h sched_words_for)
+  return (unsigned long long)(T.unit_order - reinterpret_cast<int*>(T.tile_cost)) +
+             (unsigned long long)T.order_regions * T.order_stride <=
          sched_snap_offset((unsigned long long)T.num_sel_tiles);
 }
 
@@ -1997,16 +2030,16 @@ int launch_cold_order(RenderParams P, hipStream_t stream) {
 }
 
 template <bool FAST, bool DEEP, bool SPHERES>
-static void launch_variant(const RenderParams& P, const DevNode* nodes, const DevPrim* prims,
-                           const float* normals, const DevMaterial* mats,
-                           const DevLight* lights, int blocks, const hipEvent_t* marks,
+static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* marks,
                            hipStream_t stream) {
+  const DevNode* nodes = P.nodes;
+  const DevLight* lights = P.lights;
   if (P.frames) {  // recursive scenes: one kernel walks each pixel's ray tree
-    const size_t lds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kWavesPerBlock : 0;
+    const size_t lds = deep_lds_bytes<DEEP>(kWavesPerBlock);
     mark(marks, 0, stream);
     hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, SPHERES>), dim3(blocks),
-                       dim3(kWavesPerBlock * 64), lds, stream, P, nodes, prims, normals, mats,
-                       lights);
+                       dim3(kWavesPerBlock * 64), lds, stream, P, nodes, P.prims, P.normals,
+                       P.materials, lights);
     mark(marks, 1, stream);
     mark(marks, 2, stream);
     mark(marks, 3, stream);
@@ -2015,7 +2048,7 @@ static void launch_variant(const RenderParams& P, const DevNode* nodes, const De
   RenderParams T = P;
   int tblocks = 0, per_region = 0;
   bool ordered = order_geometry(T, tblocks, per_region);
-  const size_t tlds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kTraceWaves : 0;
+  const size_t tlds = deep_lds_bytes<DEEP>(kTraceWaves);
   int oblocks = ordered ? T.order_regions * T.order_stride : tblocks;
   const RenderParams S = T;
   // one kernel per frame, dispatched by the previous frame's heavy-first order when there is one
@@ -2574,19 +2607,6 @@ __global__ __launch_bounds__(kQueryThreads) void query_scatter_kernel(QueryParam
   if (active) Q.perm_out[at + Q.totals[key >> kQueryMinBinBits]] = (int)i;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES>
-static void launch_query_variant(const RenderParams& P, const QueryParams& Q, const DevNode* nodes,
-                                 bool occlusion, hipStream_t stream) {
-  const size_t lds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kWavesPerBlock : 0;
-  const dim3 grid((unsigned)((Q.n + kWavesPerBlock * 64 - 1) / (kWavesPerBlock * 64)));
-  if (occlusion)
-    hipLaunchKernelGGL((query_occluded_kernel<FAST, DEEP, SPHERES>), grid,
-                       dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes);
-  else
-    hipLaunchKernelGGL((query_closest_kernel<FAST, DEEP, SPHERES>), grid,
-                       dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes);
-}
-
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 
 // One query launch over Q.n rays (0 < n <= kQueryMaxLaunch); reorder: Q's hist / totals /
@@ -2601,23 +2621,17 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
     if (e != hipSuccess) return e;
     Q.perm = Q.perm_out;
   }
-  fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
-  const int v = (fast ? 4 : 0) | (deep ? 2 : 0) | (spheres ? 1 : 0);
-  switch (v) {
-#define RT_CASE(F, D, S)                                              \
-  case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                       \
-    launch_query_variant<F, D, S>(P, Q, nodes, occlusion, stream);    \
-    break;
-    RT_CASE(true, false, false)
-    RT_CASE(true, false, true)
-    RT_CASE(true, true, false)
-    RT_CASE(true, true, true)
-    RT_CASE(false, false, false)
-    RT_CASE(false, false, true)
-    RT_CASE(false, true, false)
-    RT_CASE(false, true, true)
-#undef RT_CASE
-  }
+  const dim3 grid((unsigned)((Q.n + kWavesPerBlock * 64 - 1) / (kWavesPerBlock * 64)));
+  dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
+    constexpr bool F = decltype(fa)::value, D = decltype(de)::value, S = decltype(sp)::value;
+    const size_t lds = deep_lds_bytes<D>(kWavesPerBlock);
+    if (occlusion)
+      hipLaunchKernelGGL((query_occluded_kernel<F, D, S>), grid, dim3(kWavesPerBlock * 64), lds,
+                         stream, P, Q, nodes);
+    else
+      hipLaunchKernelGGL((query_closest_kernel<F, D, S>), grid, dim3(kWavesPerBlock * 64), lds,
+                         stream, P, Q, nodes);
+  });
   return hipGetLastError();
 }
 
@@ -2639,18 +2653,6 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
   return hipGetLastError();
 }
 
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE>
-static void launch_radiance_variant(const RenderParams& P, const QueryParams& Q,
-                                    const RadianceParams& R, const DevNode* nodes,
-                                    hipStream_t stream) {
-  const size_t lds = DEEP ? sizeof(int) * kDeepWords * kDeepStack * kRadianceWaves : 0;
-  const long long rays = Q.n - R.first;
-  const dim3 grid((unsigned)((rays + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
-  hipLaunchKernelGGL((query_radiance_kernel<FAST, DEEP, SPHERES, RECURSE>), grid,
-                     dim3(kRadianceWaves * 64), lds, stream, P, Q, R, nodes, P.prims, P.normals,
-                     P.materials, P.lights);
-}
-
 // One chunk of a radiance query: the rays [R.first, Q.n) of Q's order (Q.perm: the whole batch's
 // permutation, or null), at most R.lanes of them.  R.frames == nullptr picks the variant that
 // cannot recurse.
@@ -2658,27 +2660,17 @@ hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const Ra
                            const DevNode* nodes, bool fast, bool deep, bool spheres,
                            hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
-  fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
-  const bool recurse = R.frames != nullptr;
-  const int v = (recurse ? 8 : 0) | (fast ? 4 : 0) | (deep ? 2 : 0) | (spheres ? 1 : 0);
-  switch (v) {
-#define RT_CASE(F, D, S)                                                  \
-  case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                           \
-    launch_radiance_variant<F, D, S, false>(P, Q, R, nodes, stream);      \
-    break;                                                                \
-  case 8 | (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                       \
-    launch_radiance_variant<F, D, S, true>(P, Q, R, nodes, stream);       \
-    break;
-    RT_CASE(true, false, false)
-    RT_CASE(true, false, true)
-    RT_CASE(true, true, false)
-    RT_CASE(true, true, true)
-    RT_CASE(false, false, false)
-    RT_CASE(false, false, true)
-    RT_CASE(false, true, false)
-    RT_CASE(false, true, true)
-#undef RT_CASE
-  }
+  const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
+  dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
+    constexpr bool F = decltype(fa)::value, D = decltype(de)::value, S = decltype(sp)::value;
+    const size_t lds = deep_lds_bytes<D>(kRadianceWaves);
+    if (R.frames == nullptr)  // (no RECURSE)
+      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, false>), grid, dim3(kRadianceWaves * 64), lds,
+                         stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights);
+    else
+      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, true>), grid, dim3(kRadianceWaves * 64), lds,
+                         stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights);
+  });
   return hipGetLastError();
 }
 
@@ -2727,31 +2719,14 @@ hipError_t launch_quot_check(unsigned long long seed, long long count, unsigned 
   return hipGetLastError();
 }
 
-hipError_t launch_render(const RenderParams& P, const DevNode* nodes, const DevPrim* prims,
-                         const float* normals, const DevMaterial* mats, const DevLight* lights,
-                         bool fast, bool deep, bool spheres, const hipEvent_t* marks,
-                         hipStream_t stream) {
+hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
+                         const hipEvent_t* marks, hipStream_t stream) {
   if (P.num_sel_tiles <= 0) return hipSuccess;
   const int blocks = (P.num_sel_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-  // FAST walks the culling tree: only when the scene has one (a root primitive or a tree of
-  // one treelet has none, accel_build.cpp)
-  fast = fast && P.accel_root >= 0 && P.root_kind == kRootNode && P.leaves != nullptr;
-  const int v = (fast ? 4 : 0) | (deep ? 2 : 0) | (spheres ? 1 : 0);
-  switch (v) {
-#define RT_CASE(F, D, S)                                                                 \
-  case (F ? 4 : 0) | (D ? 2 : 0) | (S ? 1 : 0):                                          \
-    launch_variant<F, D, S>(P, nodes, prims, normals, mats, lights, blocks, marks, stream); \
-    break;
-    RT_CASE(true, false, false)
-    RT_CASE(true, false, true)
-    RT_CASE(true, true, false)
-    RT_CASE(true, true, true)
-    RT_CASE(false, false, false)
-    RT_CASE(false, false, true)
-    RT_CASE(false, true, false)
-    RT_CASE(false, true, true)
-#undef RT_CASE
-  }
+  dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
+    launch_variant<decltype(fa)::value, decltype(de)::value, decltype(sp)::value>(
+        P, blocks, marks, stream);
+  });
   return hipGetLastError();
 }
 

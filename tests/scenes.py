@@ -60,6 +60,9 @@ MSAA = {
 # the 8x8 tile: partial tile rows and columns, pixels outside the frame in the last tiles.
 SPLIT = {
     "ragged": (lambda: G.soup_scene(12, 75, 53), "75x53: ragged tiles, 4 lights, spheres"),
+    # frames of 8 tiles across and many tile rows: a band is a small part of its selection
+    "tall": (lambda: G.soup_scene(13, 64, 640), "8x80 tiles, lit, no recursion"),
+    "taller": (lambda: G.soup_scene(13, 64, 1080), "8x135 tiles: C3's tile rows, 8 tiles across"),
 }
 
 SMALL = ["c1", "hf_small", "hf_side", "soup1", "soup2", "soup3", "single_sphere",

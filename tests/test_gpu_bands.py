@@ -4,6 +4,8 @@ rt_tile_costs returns the measured per-tile cost map of the last frame on a stre
 are cut from it; every rank's band is a tile range of rt_render_device_range rendered in place
 into the row-major frame (HW2/main.cpp:33-36 splits the frame over threads by rows too).  The
 frame assembled from the bands must be bit-identical to the oracle's for any cut."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -62,6 +64,50 @@ def test_bands_assemble_the_oracle_frame(scene_dir, name):
 
 def plan_sizes(s):
     return [(s.camera(c).width, s.camera(c).height) for c in range(s.num_cameras)]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_frame(xml):
+    ref = OracleScene(xml).render(0, threads=8)[0]
+    ref.setflags(write=False)
+    return ref
+
+
+# (scene, first tile, tiles) of a band of whole tile rows, 8 tiles across.  With 8 regions, 2
+# chunks per region and 2 waves per workgroup both bands' order lists take 8 x 7 = 56 and
+# 8 x 9 = 72 words.  Laid out from the untrimmed selection's count (640 - 0 and 1080 - 240 = 840
+# tiles) they would be words 640..696 and 840..912 of the schedule, and the bands' cost snapshots
+# (9 tiles + 64 up) are words 640..704 and 856..944: 56 words in common each.
+TRIMMED_BANDS = [("tall", 0, 8 * 8), ("taller", 8 * 30, 8 * 11)]
+
+
+@pytest.mark.parametrize("name,tile_begin,tile_count", TRIMMED_BANDS)
+def test_trimmed_band_rendered_warm(scene_dir, name, tile_begin, tile_count):
+    """A band that tile_count trims out of a much larger selection, rendered three times on one
+    stream (cold, warm, warm): the warm frames dispatch by the order the frame before left in
+    the schedule, next to the costs rt_tile_costs reads.  Every frame is the oracle's band, bit
+    for bit, no other row is touched, and every cost map is the band's."""
+    import torch
+    import ceng795_amd
+    xml = scenes.write(name, scene_dir)
+    ref = oracle_frame(xml)
+    with ceng795_amd.Scene(xml) as s:
+        assert s.num_tiles(0) // (s.camera(0).height // 8) == 8
+        y0, y1 = tile_begin, tile_begin + tile_count  # 8 tiles of 8 rows: tile k starts at row k
+        band = np.zeros(ref.shape[0], bool)
+        band[y0:y1] = True
+        st = torch.cuda.Stream()
+        for frame_no in range(3):
+            buf = torch.full(ref.shape, -1.0, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()  # the fill ran on the current stream
+            s.render_device(0, buf.data_ptr(), tile_begin=tile_begin, tile_step=1,
+                            tile_count=tile_count, stream=st.cuda_stream)
+            c = s.tile_costs(st.cuda_stream, tile_count)
+            assert c.shape == (tile_count,) and (c > 0).all(), frame_no
+            got = buf.cpu().numpy()
+            assert np.array_equal(got[band].view(np.uint32), ref[band].view(np.uint32)), frame_no
+            assert (got[~band] == -1.0).all(), frame_no
+        s.release_stream(st.cuda_stream)
 
 
 def test_c3_band_costs_balance(scene_dir):
