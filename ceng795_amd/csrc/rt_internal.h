@@ -43,7 +43,9 @@ enum : int {
 enum : int {
   kPhCycPrimTotal = 2 * kPhaseEvents, kPhCycPrimVisit, kPhCycPrimLoad, kPhCycPrimFlush,
   kPhCycShadTotal, kPhCycShadVisit, kPhCycShadLoad, kPhCycShadFlush, kPhCycShade,
-  kPhCycFrame, kPhWaves, kPhaseSlots
+  kPhCycFrame, kPhWaves,
+  // mid-walk leaf flushes (primary + shadow) by the remainder they carried: 0, 1-16, 48-63
+  kPhCarryZero, kPhCarryLow, kPhCarryHigh, kPhaseSlots
 };
 
 constexpr int kDefaultTreeletLeaves = 2;  // culling-tree treelets: lone leaves and leaf pairs

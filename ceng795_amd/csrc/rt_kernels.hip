@@ -47,6 +47,7 @@ struct Diag {  // per-wave traversal work (RT_DIAG builds)
   // (s_memrealtime, 100 MHz) of this wave spent in its phases
   unsigned long long ev[kPhaseEvents] = {};
   unsigned long long cyc_visit = 0, cyc_load = 0, cyc_flush = 0;
+  unsigned long long carry[3] = {};  // mid-walk flushes that carried 0 / 1-16 / 48-63 entries
 };
 #ifdef RT_DIAG
 // [0, kPhaseEvents): primary events, [kPhaseEvents, 2 kPhaseEvents): shadow events, then the
@@ -462,12 +463,22 @@ __device__ __forceinline__ bool advance(WaveStack<DEEP>& st, int c0, int c1, uin
 // lanes; without it 7 spill and the C3 frame kernel runs 0.406 -> 0.395 ms, four in flight
 // 0.385 -> 0.374, profiles/r05/ab_visit_flush.json.  LDS: 22.6 KB per 4-wave workgroup, seven
 // workgroups per CU.)
-#ifndef RT_BATCH_FLUSH  // (A/B builds)
+// A mid-walk flush runs whole 64-test batches only and carries the n & 63 left-over entries to
+// the front of the queue (leaf_flush_full); only the walk's last flush runs a partial batch, so a
+// traversal of T tests takes ceil(T / 64) batch iterations instead of one half-empty iteration
+// per flush (round 9).  Queue bound: a visit starts with fewer than the threshold
+// pending — at most 63 after a mid-walk flush — and adds at most a wide visit's pushes.
+#ifndef RT_BATCH_FLUSH  // primary walk (A/B builds)
 #define RT_BATCH_FLUSH 128
 #endif
+#ifndef RT_SHADOW_FLUSH  // shadow walk (A/B builds)
+#define RT_SHADOW_FLUSH 128
+#endif
 constexpr int kBatchFlush = RT_BATCH_FLUSH;
-constexpr int kBatchCap = kBatchFlush + kWideSlots * 2 * 64;
-constexpr int kShadowFlush = kBatchFlush;
+constexpr int kShadowFlush = RT_SHADOW_FLUSH;
+static_assert(kBatchFlush >= 64 && kShadowFlush >= 64, "a mid-walk flush runs a whole batch");
+constexpr int kBatchCap =
+    (kBatchFlush > kShadowFlush ? kBatchFlush : kShadowFlush) + kWideSlots * 2 * 64;
 
 // The primary traversal's queue pushes write every lane: lanes outside the push mask write a
 // junk entry past the queue (q[kBatchCap + ...], never read) instead of taking an exec-mask
@@ -482,7 +493,11 @@ struct WaveLeafLds {
   unsigned q[kBatchCap + kPushJunk];  // lane << kQueueLeafBits | leaf
   unsigned long long key[64];       // per lane: closest-hit key, or shadow flag
   int sub;  // the wave's quadrant of a split tile, -1: whole packet (trace_frame_kernel)
+  unsigned start;  // the packet's start time, low word (trace_frame_kernel; the struct's padding)
 };
+// 28 waves per CU: no larger than with the 128-entry threshold
+static_assert(sizeof(WaveLeafLds) <= 4 * (128 + kWideSlots * 2 * 64 + kPushJunk) + 8 * 64 + 8,
+              "WaveLeafLds grew");
 
 constexpr unsigned long long kNoHitKey = (0x7f800000ull << 32) | 0xffffffffull;  // (+inf, -1)
 
@@ -549,20 +564,31 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 // Runs the n queued tests; SHADOW: 0 < t < thr of the owner sets its flag, else the owner's
 // key takes min(key, (t, leaf)) for 0 < t < inf.  All lanes of the wave take part.  SKIP:
-// some lane of the wave skips an axis (else the guard test needs no skip flags).
-template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP = true>
-__device__ __forceinline__ void batch_flush(const RenderParams& P, WaveLeafLds& L, int n,
-                                            const LaneRay& r, float thr, Diag& dg) {
+// some lane of the wave skips an axis (else the guard test needs no skip flags).  CAMERA: every
+// lane's ray starts at the same point (the frame kernel's primary rays), so the owner's origin —
+// and `quot`, which depends on the origin and the scene only — is this lane's own: no fetch.
+// WHOLE: only the whole 64-entry batches run (every lane of an iteration holds an entry); returns
+// the number of entries run, n & ~63 (else n rounded up).
+template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP = true, bool CAMERA = false,
+          bool WHOLE = false>
+__device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L, int n,
+                                           const LaneRay& r, float thr, Diag& dg) {
   const int lane = lane_id();
-  for (int base = 0; base < n; base += 64) {
+  int base = 0;
+  for (; WHOLE ? base + 64 <= n : base < n; base += 64) {
     const int i = base + lane;
-    const bool valid = i < n;
+    const bool valid = WHOLE || i < n;
     const unsigned e = valid ? L.q[i] : 0u;
     const int src = (int)(e >> kQueueLeafBits), idx = (int)(e & kQueueLeafMask);
     LaneRay rr;
-    rr.o = v3(lane_f(src, r.o.x), lane_f(src, r.o.y), lane_f(src, r.o.z));
+    if constexpr (CAMERA) {
+      rr.o = r.o;
+      rr.quot = r.quot;
+    } else {
+      rr.o = v3(lane_f(src, r.o.x), lane_f(src, r.o.y), lane_f(src, r.o.z));
+      rr.quot = __builtin_amdgcn_ds_bpermute(src << 2, (int)r.quot) != 0;
+    }
     rr.d = v3(lane_f(src, r.d.x), lane_f(src, r.d.y), lane_f(src, r.d.z));
-    rr.quot = __builtin_amdgcn_ds_bpermute(src << 2, (int)r.quot) != 0;
     const float othr = SHADOW ? lane_f(src, thr) : 0.0f;
     float t = 0.0f;
     bool hit;
@@ -606,6 +632,26 @@ __device__ __forceinline__ void batch_flush(const RenderParams& P, WaveLeafLds& 
       atomicMin(&L.key[src], ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)leaf);
     }
   }
+  return base;
+}
+
+// A mid-walk flush (n >= 64 pending): the whole batches only; the n & 63 left-over entries move
+// to the front of the queue and stay pending.  The source range starts at full >= 64 > rem, so
+// the ranges do not overlap; LDS accesses of one wave complete in order, so the next visit's
+// pushes land after the move.  The same tests run as before, a batch later at most; a shadow
+// lane whose occluding test is carried stays `alive` until the next flush.
+// (The lane index is computed afresh, as in the shadow phase's light loop, so that no address
+// derived from it is kept live across the walk: the kernel sits at its 72-VGPR budget.)
+template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA = false>
+__device__ __forceinline__ void leaf_flush_full(const RenderParams& P, WaveLeafLds& L, int& n,
+                                                const LaneRay& r, float thr, Diag& dg) {
+  const int full = batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, true>(P, L, n, r, thr, dg);
+  const int rem = n - full;
+  const int lane = fresh_lane();
+  if (lane < rem) L.q[lane] = L.q[full + lane];
+  DIAG(dg.ev[kPhFlushes]++; dg.ev[kPhFlushIters] += full / 64;
+       dg.carry[0] += rem == 0; dg.carry[1] += rem >= 1 && rem <= 16; dg.carry[2] += rem >= 48);
+  n = rem;
 }
 
 // Queues the leaf tests of a visited reference node's leaf children for the lanes of h0 / h1.
@@ -780,8 +826,8 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
 // ------------------------------------------------------------------ closest hit
 // The reference's (t, leaf) for every active ray: leaf < 0 = miss.  FAST: the 8-wide culling
 // tree over reference treelets (the launch takes it only when the scene has one); otherwise
-// the reference tree itself.
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES>
+// the reference tree itself.  CAMERA: all rays share one origin (batch_flush).
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false>
 __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode* __restrict__ nodes,
                                             int* spill, WaveLeafLds& L, const LaneRay& r,
                                             bool active, float& best_t, int& best_leaf, Diag& dg) {
@@ -818,11 +864,9 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
     if (pending >= kBatchFlush) {  // between visits: only the ray and the stack are live
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
-      batch_flush<false, SPHERES, FAST, SKIP>(P, L, pending, r, 0.0f, dg);
+      leaf_flush_full<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, r, 0.0f, dg);
       RT_PRIO_FLUSH_END;
-      DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes]++;
-           dg.ev[kPhFlushIters] += (pending + 63) / 64);
-      pending = 0;
+      DIAG(dg.cyc_flush += clock_now() - tf0);
     }
     if constexpr (FAST) {
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
@@ -848,7 +892,7 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   if (pending) {
     DIAG(const unsigned long long tf0 = clock_now());
     RT_PRIO_FLUSH_BEGIN;
-    batch_flush<false, SPHERES, FAST, SKIP>(P, L, pending, r, 0.0f, dg);
+    batch_flush<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, r, 0.0f, dg);
     RT_PRIO_FLUSH_END;
     DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes]++;
          dg.ev[kPhFlushIters] += (pending + 63) / 64);
@@ -897,11 +941,9 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
     if (pending >= kShadowFlush) {  // between visits; a lane found occluded stops entering nodes
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
-      batch_flush<true, SPHERES, FAST, SKIP>(P, L, pending, r, thr, dg);
+      leaf_flush_full<true, SPHERES, FAST, SKIP>(P, L, pending, r, thr, dg);
       RT_PRIO_FLUSH_END;
-      DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes]++;
-           dg.ev[kPhFlushIters] += (pending + 63) / 64);
-      pending = 0;
+      DIAG(dg.cyc_flush += clock_now() - tf0);
       alive &= ~ballot(L.key[lane] != 0ull);
       m &= alive;
       if (!m && !st.pop_live(node, m, alive)) break;
@@ -1063,6 +1105,9 @@ __device__ __forceinline__ int hit_leaf(int2_t rec) { return rec.x; }
 
 // One wave = the 8x8 packet of selected tile `sel` (< num_sel_tiles): closest hit per pixel
 // into its 8-B record.
+#ifndef RT_CAMERA_ORIGIN  // (A/B builds: 0 = the leaf batch fetches the owner's origin here too)
+#define RT_CAMERA_ORIGIN 1
+#endif
 template <bool FAST, bool DEEP, bool SPHERES>
 __device__ __forceinline__ void primary_packet(const RenderParams& P,
                                                const DevNode* __restrict__ nodes, int sel,
@@ -1077,10 +1122,12 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   Diag dg;
   float t;
   int leaf;
+  // (CAMERA: every lane's origin is cam_e, so the leaf batch fetches no owner origin)
+  constexpr bool kCam = RT_CAMERA_ORIGIN != 0;
   if (ballot(any_skip))
-    closest_hit<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+    closest_hit<true, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   else
-    closest_hit<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+    closest_hit<false, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   const RenderParams& Pw = fresh_params(P);  // post-traversal fields: not live across it
   const PacketPixel qw = packet_pixel(Pw, sel, wave_sub(L));  // (recomputed, not kept)
   int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
@@ -1104,6 +1151,7 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     atomicAdd(&g_phase[kPhCycPrimVisit], dg.cyc_visit);
     atomicAdd(&g_phase[kPhCycPrimLoad], dg.cyc_load);
     atomicAdd(&g_phase[kPhCycPrimFlush], dg.cyc_flush);
+    for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
 #endif
   }
 }
@@ -1176,6 +1224,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       atomicAdd(&g_phase[kPhCycShadVisit], dg.cyc_visit);
       atomicAdd(&g_phase[kPhCycShadLoad], dg.cyc_load);
       atomicAdd(&g_phase[kPhCycShadFlush], dg.cyc_flush);
+      for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
 #endif
     }
   }
@@ -1887,9 +1936,11 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
   if (sel >= 0) {
     const int e = Q.use_order ? order_entry(Q) : -1;
     L.sub = e <= -2 ? ((-2 - e) % kSplitEntries) * kTraceWaves + ((int)threadIdx.x >> 6) : -1;
-    // the packet's start time waits in LDS (kept in SGPRs across the traversals it spilled)
-    __shared__ unsigned long long start[kTraceWaves];
-    start[threadIdx.x >> 6] = __builtin_amdgcn_s_memrealtime();
+    // the packet's start time waits in the wave's LDS block (kept in SGPRs across the
+    // traversals it spilled; in an array of its own, the slot's address was a VGPR held, and
+    // with the carried leaf queue spilled to scratch, across them): its low word, which gives
+    // the elapsed ticks modulo 2^32 (43 s at 100 MHz)
+    L.start = (unsigned)__builtin_amdgcn_s_memrealtime();
     DIAG(const unsigned long long c0 = clock_now());
     primary_packet<FAST, DEEP, SPHERES>(Q, nodes, sel, spill, L);
     DIAG(const unsigned long long c1 = clock_now());
@@ -1916,8 +1967,7 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
 #endif
     const RenderParams& Pw = fresh_params(P);
     if (Pw.tile_cost && lane_id() == 0) {  // the next frame's dispatch order
-      const unsigned c = (unsigned)min(__builtin_amdgcn_s_memrealtime() - start[threadIdx.x >> 6],
-                                       0xffffffffull);
+      const unsigned c = (unsigned)__builtin_amdgcn_s_memrealtime() - L.start;
       if (wave_sub(L) < 0)
         Pw.tile_cost[sel] = c;
       else  // a quadrant: the tile's cost is the sum of its quadrants' (zeroed by order_kernel)

@@ -76,6 +76,8 @@ def main():
            "cycles": cyc,
            "cycle_share_of_frame": {k: round(cyc[k] / frame, 4) for k in CYCLES
                                     if k not in ("frame", "waves")}}
+    if n >= 34:  # mid-walk flushes by the remainder they carried (primary + shadow)
+        res["midwalk_flushes_by_carry"] = dict(zip(["zero", "1_16", "48_63"], v[31:34]))
     print(json.dumps(res))
 
 
