@@ -40,6 +40,7 @@ hipError_t launch_quot_check(unsigned long long seed, long long count, unsigned 
 bool diag_build();
 long long read_reset_timeline(unsigned long long* out, long long max_values);
 long long read_reset_phases(unsigned long long* out, long long max_values);
+hipError_t frame_kernel_occupancy(int* out4);
 int launch_cold_order(RenderParams P, hipStream_t stream);
 hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
                         bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream);
@@ -1903,6 +1904,15 @@ long long rt_debug_timeline(unsigned long long* out, long long max_values) {
   const long long n = read_reset_timeline(out, max_values);
   if (n < 0) return set_error(RT_E_INVALID, "rt_debug_timeline: buffer too small or copy failed");
   return n;
+}
+
+int rt_debug_frame_occupancy(int device, int* out4) {
+  if (!out4) return set_error(RT_E_INVALID, "rt_debug_frame_occupancy: bad argument");
+  return guarded([&] {
+    DeviceGuard g(device);
+    hip_check(frame_kernel_occupancy(out4), "occupancy query");
+    return RT_OK;
+  });
 }
 
 int rt_debug_quotient_check(int device, unsigned long long seed, long long count,

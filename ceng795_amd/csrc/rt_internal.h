@@ -45,7 +45,18 @@ enum : int {
   kPhCycShadTotal, kPhCycShadVisit, kPhCycShadLoad, kPhCycShadFlush, kPhCycShade,
   kPhCycFrame, kPhWaves,
   // mid-walk leaf flushes (primary + shadow) by the remainder they carried: 0, 1-16, 48-63
-  kPhCarryZero, kPhCarryLow, kPhCarryHigh, kPhaseSlots
+  kPhCarryZero, kPhCarryLow, kPhCarryHigh,
+  // the leaf batch's deferred guard, kDeferEvents values per traversal kind:
+  // primary from kPhDeferPrim, shadow from kPhDeferShad
+  kPhDeferPrim, kPhDeferShad = kPhDeferPrim + 4, kPhaseSlots = kPhDeferShad + 4
+};
+// Per traversal kind: queued tests whose triangle / sphere test hit in range (the only ones whose
+// guard decision is used), the 64-survivor guard iterations, the guard batches in which one
+// 64-test iteration's survivors fell on both sides of the full survivor buffer, and the
+// survivors the guard rejected.  (A walk that takes the guard decision before the triangle test
+// counts the first and the last and leaves the other two at 0.)
+enum : int {
+  kDfSurvivors = 0, kDfGuardIters = 1, kDfSplitDrains = 2, kDfRejected = 3, kDeferEvents = 4
 };
 
 constexpr int kDefaultTreeletLeaves = 2;  // culling-tree treelets: lone leaves and leaf pairs

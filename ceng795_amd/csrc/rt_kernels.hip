@@ -48,6 +48,7 @@ struct Diag {  // per-wave traversal work (RT_DIAG builds)
   unsigned long long ev[kPhaseEvents] = {};
   unsigned long long cyc_visit = 0, cyc_load = 0, cyc_flush = 0;
   unsigned long long carry[3] = {};  // mid-walk flushes that carried 0 / 1-16 / 48-63 entries
+  unsigned long long defer[kDeferEvents] = {};  // the deferred guard's kDf* counts
 };
 #ifdef RT_DIAG
 // [0, kPhaseEvents): primary events, [kPhaseEvents, 2 kPhaseEvents): shadow events, then the
@@ -452,10 +453,11 @@ __device__ __forceinline__ bool advance(WaveStack<DEEP>& st, int c0, int c1, uin
 // load), once kBatchFlush are pending and when the walk ends.  Results land per ray by LDS
 // atomics: closest hit = atomic min of the key (t bits << 32 | DFS leaf), which for 0 < t
 // orders exactly like the reference's (t, DFS leaf) rule; shadow = a flag.
-// CULL (the culling tree): an entry is a DevLeaf, and its lane first takes the reference's
-// decision on the leaf's GUARD box — the fast slab test with the 2^-20 band, which on accept
+// CULL (the culling tree): an entry is a DevLeaf, and its lane takes the reference's decision on
+// the leaf's GUARD box (before the triangle test here, after it for the tests that hit in
+// batch_flush_deferred below) — the fast slab test with the 2^-20 band, which on accept
 // implies every enclosing reference box accepts, else guard_exact over the
-// ancestry — so exactly the leaves the reference reaches are tested.  Without CULL (reference
+// ancestry — so exactly the tests the reference makes count.  Without CULL (reference
 // walk) an entry is a DFS leaf whose boxes the walk has already decided.
 // The queue is flushed only between visits, once kBatchFlush tests are pending, and holds a whole
 // wide visit's pushes (8 slots x 2 leaves x 64 lanes) above that: no flush inside the slot loop.
@@ -468,11 +470,13 @@ __device__ __forceinline__ bool advance(WaveStack<DEEP>& st, int c0, int c1, uin
 // traversal of T tests takes ceil(T / 64) batch iterations instead of one half-empty iteration
 // per flush (round 9).  Queue bound: a visit starts with fewer than the threshold
 // pending — at most 63 after a mid-walk flush — and adds at most a wide visit's pushes.
+// (Round 10: 88, not 128 — the 160 B per queue pay for most of the survivor buffer below; round 9
+// had measured thresholds down to 96 neutral, profiles/r09/ab_thresholds.json.)
 #ifndef RT_BATCH_FLUSH  // primary walk (A/B builds)
-#define RT_BATCH_FLUSH 128
+#define RT_BATCH_FLUSH 88
 #endif
 #ifndef RT_SHADOW_FLUSH  // shadow walk (A/B builds)
-#define RT_SHADOW_FLUSH 128
+#define RT_SHADOW_FLUSH 88
 #endif
 constexpr int kBatchFlush = RT_BATCH_FLUSH;
 constexpr int kShadowFlush = RT_SHADOW_FLUSH;
@@ -482,8 +486,18 @@ constexpr int kBatchCap =
 
 // The primary traversal's queue pushes write every lane: lanes outside the push mask write a
 // junk entry past the queue (q[kBatchCap + ...], never read) instead of taking an exec-mask
-// branch (the shadow traversal keeps the branch: junk writes cost it VGPR spills).
-constexpr int kPushJunk = 128;
+// branch (the shadow traversal keeps the branch: junk writes cost it VGPR spills).  A lane's junk
+// word is q[kBatchCap + lane], a pair's second one the next lane's first (both garbage): 65
+// words, one more to keep the keys 8-byte aligned.
+constexpr int kPushJunk = 66;
+
+// Survivors of the leaf batch's triangle tests wait here for their guard decision (batch_flush):
+// kSurvivorCap records of (t bits << 32 | queue entry).  Capacity rule: a 64-test iteration
+// appends its survivors below the cap; when the buffer is full the guard batch runs on all
+// kSurvivorCap of them, and the iteration's survivors that did not fit — the buffer is empty
+// again and one iteration has at most 64 — are appended then.  So any number of survivors per
+// iteration, 0 to 64, is held, and every guard batch but a walk's last runs on a full wave.
+constexpr int kSurvivorCap = 64;
 
 // A queue entry is one 32-bit word: the owner lane above kQueueLeafBits, the leaf (DevLeaf or
 // DFS index, < 2^26: rt_api.hip refuses larger scenes) below.
@@ -492,12 +506,15 @@ constexpr unsigned kQueueLeafMask = (1u << kQueueLeafBits) - 1u;
 struct WaveLeafLds {
   unsigned q[kBatchCap + kPushJunk];  // lane << kQueueLeafBits | leaf
   unsigned long long key[64];       // per lane: closest-hit key, or shadow flag
+  unsigned long long sv[kSurvivorCap];  // t bits << 32 | queue entry (see kSurvivorCap)
   int sub;  // the wave's quadrant of a split tile, -1: whole packet (trace_frame_kernel)
   unsigned start;  // the packet's start time, low word (trace_frame_kernel; the struct's padding)
 };
-// 28 waves per CU: no larger than with the 128-entry threshold
-static_assert(sizeof(WaveLeafLds) <= 4 * (128 + kWideSlots * 2 * 64 + kPushJunk) + 8 * 64 + 8,
-              "WaveLeafLds grew");
+// 28 waves per CU = 14 two-wave workgroups.  The frame kernel's workgroup holds
+// two of these and 8 B more, and must stay within 11,520 B: 14 of them fit the CU's 160 KiB
+// whether the hardware hands LDS out byte-exact (14 x 11,702) or in 512-B or 1,280-B granules
+// (11,520 is a multiple of both) — the pre-round-10 workgroup (11,288 B) rounds up to the same.
+static_assert(2 * sizeof(WaveLeafLds) + 8 <= 11520, "WaveLeafLds: 14 workgroups per CU");
 
 constexpr unsigned long long kNoHitKey = (0x7f800000ull << 32) | 0xffffffffull;  // (+inf, -1)
 
@@ -545,7 +562,7 @@ __device__ __forceinline__ void batch_push_n(WaveLeafLds& L, int& n, int leaf, u
   if (ALL) {
     int at;
     asm("v_cndmask_b32 %0, %1, %2, %3"
-        : "=v"(at) : "v"(kBatchCap + 2 * lane), "v"(n + (below << p)), "s"(m));
+        : "=v"(at) : "v"(kBatchCap + lane), "v"(n + (below << p)), "s"(m));
     L.q[at] = e;
     L.q[at + (int)p] = e + p;
   } else if (lane_in(m)) {
@@ -621,6 +638,9 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
         hit = tri_test(v0, v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), rr, t);
       else
         hit = sphere_test(v0, q1.x, rr, t);
+      DIAG(const bool sv = valid & hit & (t > 0.0f) & (SHADOW ? t < othr : t < RT_INF);
+           dg.defer[kDfSurvivors] += __builtin_popcountll(ballot(sv));
+           dg.defer[kDfRejected] += __builtin_popcountll(ballot(sv & !ok)));
       hit &= ok;
     } else {
       hit = leaf_test<SPHERES>(P.prims, idx, rr, t);  // leaf 0 for idle lanes: unused
@@ -635,6 +655,157 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
   return base;
 }
 
+// ---- the guard deferred to the tests that hit (round 10; culling tree only)
+// The guard's outcome is used only where the triangle test hits in range — on C3 one queued
+// test in eight to ten — and a wave issues an instruction if any lane needs it, so masking the
+// guard inside the iteration saves nothing.  Instead the batch runs in two stages.  Stage 1, per
+// 64 queue entries: the owner's ray, three of the DevLeaf's four 16-B words, the triangle or
+// sphere test, and the survivors (hit, 0 < t, t in range) appended, compacted by their ballot,
+// to WaveLeafLds::sv.  Stage 2 (guard_batch), per kSurvivorCap survivors: the guard decision
+// exactly as batch_flush takes it, and the commit for the lanes it accepts.  The committed set
+// {guard ok, hit, in range} is the same, and neither atomicMin nor the any-hit flag depends on
+// the order.  The survivor count `ns` is wave-uniform and lives across the walk like `pending`.
+// Modes (A/B builds set them per walk): 0 the guard first, as batch_flush above; 1 deferred, every
+// flush drains its survivors (the last guard batch of a flush partial); 2 deferred, survivors wait
+// across flushes for a full batch and only the walk's last guard batch is partial (a shadow lane
+// with a waiting survivor stays `alive`, as one with a carried queue entry does).
+// Shipped: the primary walk 2, the shadow walk 0.  C3, same box, five interleaved rounds, frame
+// kernel / six in flight (profiles/r10/ab_defer.json): primary alone 0.3269 -> 0.3168 / 0.3063 ->
+// 0.2969 ms; shadow alone, mode 1 0.3270 / 0.3064 and mode 2 0.3259 / 0.3053, inside the
+// run-to-run range although no C3 shadow test survives — the shadow walk's time is its visits,
+// the batches fill their gaps.
+#ifndef RT_DEFER_PRIMARY
+#define RT_DEFER_PRIMARY 2
+#endif
+#ifndef RT_DEFER_SHADOW
+#define RT_DEFER_SHADOW 0
+#endif
+static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADOW >= 0 &&
+              RT_DEFER_SHADOW <= 2, "deferred-guard modes");
+
+// Stage 2: the guard decision of the first ns (<= kSurvivorCap) waiting survivors, one per lane,
+// and their commit.
+template <bool SHADOW, bool SKIP, bool CAMERA>
+__device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& L, int ns,
+                                            const LaneRay& r, Diag& dg) {
+  const int lane = lane_id();
+  const bool valid = lane < ns;
+  const unsigned long long s = valid ? L.sv[lane] : 0ull;
+  const unsigned e = (unsigned)s;
+  const int src = (int)(e >> kQueueLeafBits), idx = (int)(e & kQueueLeafMask);
+  LaneRay rr;
+  if constexpr (CAMERA)
+    rr.o = r.o;
+  else
+    rr.o = v3(lane_f(src, r.o.x), lane_f(src, r.o.y), lane_f(src, r.o.z));
+  rr.d = v3(lane_f(src, r.d.x), lane_f(src, r.d.y), lane_f(src, r.d.z));
+  const float* q = reinterpret_cast<const float*>(P.leaves + idx);  // idle lanes: record 0, unused
+  const int leaf = __float_as_int(q[3]) & ~kLeafSphere;
+  const float g0 = q[7], g1 = q[11];
+  const f4 q3 = reinterpret_cast<const f4*>(q)[3];
+  // the guard: the holder box {q1.w, q2.w, q3.x, q3.y, q3.z, q3.w}
+  rr.r = v3(__builtin_amdgcn_rcpf(rr.d.x), __builtin_amdgcn_rcpf(rr.d.y),
+            __builtin_amdgcn_rcpf(rr.d.z));
+  rr.skip0 = SKIP && __builtin_fabsf(rr.d.x) < kEps;
+  rr.skip1 = SKIP && __builtin_fabsf(rr.d.y) < kEps;
+  rr.skip2 = SKIP && __builtin_fabsf(rr.d.z) < kEps;
+  const float g[6] = {g0, g1, q3.x, q3.y, q3.z, q3.w};
+  float tn, tf;
+  slab_span<SKIP>(g, rr, tn, tf);
+  bool in, out;
+  decide_sure(tn, tf, in, out);
+  bool ok = valid & in;
+  const bool und = valid & !(in | out);
+  if (ballot(und)) {
+    if (und) ok = guard_exact(P, ~leaf, rr);
+    DIAG(if (und) atomicAdd(&g_exact_fallbacks, 1ull));
+  }
+  DIAG(dg.defer[kDfGuardIters]++;
+       dg.defer[kDfRejected] += __builtin_popcountll(ballot(valid & !ok)));
+  if (SHADOW) {
+    if (ok) L.key[src] = 1ull;  // any writer: same value
+  } else if (ok) {
+    atomicMin(&L.key[src], (s & 0xffffffff00000000ull) | (unsigned)leaf);
+  }
+}
+
+// Stage 1 over the n queued tests (WHOLE: the whole 64-entry batches only, as batch_flush), the
+// guard batches that fill up on the way, and with DRAIN the survivors still waiting at the end.
+// ns: survivors waiting, in and out.  Returns the number of queue entries run.
+template <bool SHADOW, bool SPHERES, bool SKIP, bool CAMERA, bool WHOLE, bool DRAIN>
+__device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveLeafLds& L, int n,
+                                                    int& nsurv, const LaneRay& r, float thr,
+                                                    Diag& dg) {
+  const int lane = lane_id();
+  int base = 0, ns = nsurv;
+  for (;;) {
+    const bool more = WHOLE ? base + 64 <= n : base < n;
+    if (!more && (!DRAIN || ns == 0)) break;
+    bool late = false;  // this lane's survivor waits for the full buffer's guard batch
+    int rank = 0;
+    unsigned long long rec = 0ull;
+    if (more) {
+      const int i = base + lane;
+      const bool valid = WHOLE || i < n;
+      const unsigned e = valid ? L.q[i] : 0u;
+      const int src = (int)(e >> kQueueLeafBits), idx = (int)(e & kQueueLeafMask);
+      LaneRay rr;
+      if constexpr (CAMERA) {
+        rr.o = r.o;
+        rr.quot = r.quot;
+      } else {
+        rr.o = v3(lane_f(src, r.o.x), lane_f(src, r.o.y), lane_f(src, r.o.z));
+        rr.quot = __builtin_amdgcn_ds_bpermute(src << 2, (int)r.quot) != 0;
+      }
+      rr.d = v3(lane_f(src, r.d.x), lane_f(src, r.d.y), lane_f(src, r.d.z));
+      const float othr = SHADOW ? lane_f(src, thr) : 0.0f;
+      // (the guard words q1.w and q2.w ride along unused; q[3] is not loaded)
+      const f4* q = reinterpret_cast<const f4*>(P.leaves + idx);  // idle lanes: record 0, unused
+      const f4 q0 = q[0], q1 = q[1], q2 = q[2];
+      const V3 v0 = v3(q0.x, q0.y, q0.z);
+      float t = 0.0f;
+      bool hit;
+      if (!SPHERES || !(__float_as_int(q0.w) & kLeafSphere))
+        hit = tri_test(v0, v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), rr, t);
+      else
+        hit = sphere_test(v0, q1.x, rr, t);
+      const bool surv = valid & hit & (t > 0.0f) & (SHADOW ? t < othr : t < RT_INF);
+      DIAG(dg.guard += __builtin_popcountll(ballot(valid)));
+      base += 64;
+      const uint64_t sm = ballot(surv);
+      if (sm) {
+        rank = ns + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(sm >> 32),
+                                                   __builtin_amdgcn_mbcnt_lo((unsigned)sm, 0u));
+        rec = ((unsigned long long)__float_as_uint(t) << 32) | e;
+        if (surv && rank < kSurvivorCap) L.sv[rank] = rec;
+        late = surv && rank >= kSurvivorCap;
+        ns += __builtin_popcountll(sm);
+        DIAG(dg.defer[kDfSurvivors] += __builtin_popcountll(sm));
+      }
+    }
+    if (ns >= kSurvivorCap || !more) {
+      guard_batch<SHADOW, SKIP, CAMERA>(P, L, ns < kSurvivorCap ? ns : kSurvivorCap, r, dg);
+      DIAG(dg.defer[kDfSplitDrains] += ns > kSurvivorCap);
+      ns = ns > kSurvivorCap ? ns - kSurvivorCap : 0;
+      if (late) L.sv[rank - kSurvivorCap] = rec;  // the buffer is empty again
+    }
+  }
+  nsurv = ns;
+  return base;
+}
+
+// The leaf batches of one flush, by the walk's mode (RT_DEFER_*): see above.
+template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA, bool WHOLE>
+__device__ __forceinline__ int leaf_batches(const RenderParams& P, WaveLeafLds& L, int n, int& ns,
+                                            const LaneRay& r, float thr, Diag& dg) {
+  constexpr int mode = !CULL ? 0 : (SHADOW ? RT_DEFER_SHADOW : RT_DEFER_PRIMARY);
+  if constexpr (mode == 0)
+    return batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, WHOLE>(P, L, n, r, thr, dg);
+  else
+    return batch_flush_deferred<SHADOW, SPHERES, SKIP, CAMERA, WHOLE, !WHOLE || mode == 1>(
+        P, L, n, ns, r, thr, dg);
+}
+
 // A mid-walk flush (n >= 64 pending): the whole batches only; the n & 63 left-over entries move
 // to the front of the queue and stay pending.  The source range starts at full >= 64 > rem, so
 // the ranges do not overlap; LDS accesses of one wave complete in order, so the next visit's
@@ -644,8 +815,8 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
 // derived from it is kept live across the walk: the kernel sits at its 72-VGPR budget.)
 template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA = false>
 __device__ __forceinline__ void leaf_flush_full(const RenderParams& P, WaveLeafLds& L, int& n,
-                                                const LaneRay& r, float thr, Diag& dg) {
-  const int full = batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, true>(P, L, n, r, thr, dg);
+                                                int& ns, const LaneRay& r, float thr, Diag& dg) {
+  const int full = leaf_batches<SHADOW, SPHERES, CULL, SKIP, CAMERA, true>(P, L, n, ns, r, thr, dg);
   const int rem = n - full;
   const int lane = fresh_lane();
   if (lane < rem) L.q[lane] = L.q[full + lane];
@@ -857,14 +1028,14 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   const int lane = lane_id();
   WaveStack<DEEP> st;
   st.lds = spill;
-  int pending = 0;
+  int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
   L.key[lane] = kNoHitKey;
   int node = FAST ? P.accel_root : P.root_ref;
   for (;;) {
     if (pending >= kBatchFlush) {  // between visits: only the ray and the stack are live
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
-      leaf_flush_full<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, r, 0.0f, dg);
+      leaf_flush_full<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, waiting, r, 0.0f, dg);
       RT_PRIO_FLUSH_END;
       DIAG(dg.cyc_flush += clock_now() - tf0);
     }
@@ -889,12 +1060,12 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
       if (!advance(st, N.child[0], N.child[1], m0, m1, t0, t1, node, m, ~0ull)) break;
     }
   }
-  if (pending) {
+  if (pending | waiting) {  // the last tests, and the survivors still waiting for their guard
     DIAG(const unsigned long long tf0 = clock_now());
     RT_PRIO_FLUSH_BEGIN;
-    batch_flush<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, r, 0.0f, dg);
+    leaf_batches<false, SPHERES, FAST, SKIP, CAMERA, false>(P, L, pending, waiting, r, 0.0f, dg);
     RT_PRIO_FLUSH_END;
-    DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes]++;
+    DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes] += pending != 0;
          dg.ev[kPhFlushIters] += (pending + 63) / 64);
   }
   DIAG(dg.ev[kPhPushes] += st.pushes; dg.ev[kPhPops] += st.pops);
@@ -932,7 +1103,7 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
   const int lane = lane_id();
   WaveStack<DEEP> st;
   st.lds = spill;
-  int pending = 0;
+  int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
   unsigned long long clear = 0ull;
   asm volatile("" : "+v"(clear));  // a fresh zero here, not one kept (and spilled) across the walk
   L.key[lane] = clear;
@@ -941,7 +1112,7 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
     if (pending >= kShadowFlush) {  // between visits; a lane found occluded stops entering nodes
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
-      leaf_flush_full<true, SPHERES, FAST, SKIP>(P, L, pending, r, thr, dg);
+      leaf_flush_full<true, SPHERES, FAST, SKIP>(P, L, pending, waiting, r, thr, dg);
       RT_PRIO_FLUSH_END;
       DIAG(dg.cyc_flush += clock_now() - tf0);
       alive &= ~ballot(L.key[lane] != 0ull);
@@ -968,12 +1139,12 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
       if (!advance(st, N.child[0], N.child[1], m0, m1, t0, t1, node, m, alive)) break;
     }
   }
-  if (pending) {
+  if (pending | waiting) {
     DIAG(const unsigned long long tf0 = clock_now());
     RT_PRIO_FLUSH_BEGIN;
-    batch_flush<true, SPHERES, FAST, SKIP>(P, L, pending, r, thr, dg);
+    leaf_batches<true, SPHERES, FAST, SKIP, false, false>(P, L, pending, waiting, r, thr, dg);
     RT_PRIO_FLUSH_END;
-    DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes]++;
+    DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes] += pending != 0;
          dg.ev[kPhFlushIters] += (pending + 63) / 64);
   }
   DIAG(dg.ev[kPhPushes] += st.pushes; dg.ev[kPhPops] += st.pops);
@@ -1152,6 +1323,7 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     atomicAdd(&g_phase[kPhCycPrimLoad], dg.cyc_load);
     atomicAdd(&g_phase[kPhCycPrimFlush], dg.cyc_flush);
     for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
+    for (int k = 0; k < kDeferEvents; k++) atomicAdd(&g_phase[kPhDeferPrim + k], dg.defer[k]);
 #endif
   }
 }
@@ -1225,6 +1397,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       atomicAdd(&g_phase[kPhCycShadLoad], dg.cyc_load);
       atomicAdd(&g_phase[kPhCycShadFlush], dg.cyc_flush);
       for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
+      for (int k = 0; k < kDeferEvents; k++) atomicAdd(&g_phase[kPhDeferShad + k], dg.defer[k]);
 #endif
     }
   }
@@ -2822,6 +2995,24 @@ long long read_reset_phases(unsigned long long* out, long long max_values) {
   (void)max_values;
   return 0;
 #endif
+}
+
+// The runtime's occupancy query for the frame kernel's instantiation of a culling-tree scene
+// without spheres or a deep tree (C3), on the current device: out4 = workgroups per CU, waves per
+// CU, static LDS bytes per workgroup, VGPRs per lane.
+hipError_t frame_kernel_occupancy(int* out4) {
+  const auto kernel = trace_frame_kernel<true, false, false>;
+  int blocks = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, kTraceWaves * 64, 0);
+  if (e != hipSuccess) return e;
+  hipFuncAttributes attr;
+  e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel));
+  if (e != hipSuccess) return e;
+  out4[0] = blocks;
+  out4[1] = blocks * kTraceWaves;
+  out4[2] = (int)attr.sharedSizeBytes;
+  out4[3] = attr.numRegs;
+  return hipSuccess;
 }
 
 bool diag_build() {

@@ -352,6 +352,11 @@ long long rt_debug_timeline(unsigned long long* out, long long max_values);
  * number of values written (0 in other builds) or a negative RT_E_* code. */
 long long rt_debug_phases(unsigned long long* out, long long max_values);
 
+/* The HIP runtime's occupancy query for the frame kernel as a culling-tree scene without spheres
+ * runs it (the benchmark's C3), on `device`: out4 = workgroups per CU, waves per CU, static LDS
+ * bytes per workgroup, VGPRs per lane. */
+int rt_debug_frame_occupancy(int device, int* out4);
+
 /* Device self-check of the triangle test's shared-reciprocal quotients (rt_kernels.hip,
  * tri_quotients) against IEEE division on `count` seeded random operand pairs of the fast
  * range; out2[0] = mismatching quotients (must be 0), out2[1] = cases run. */

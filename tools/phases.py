@@ -4,7 +4,9 @@ loop events and 100 MHz real-time clock ticks (rt_debug_phases), one warm frame.
 
 Events per traversal kind (primary / shadow): visits, slots tested, slot hits (some lane
 entered), leafy / pair / inner hits, stack pushes and pops, leaf-batch flushes and their
-64-test iterations.  Cycles (s_memrealtime, 100 MHz, summed over waves): the whole primary / shadow / shading
+64-test iterations; and of the leaf batch's deferred guard the tests that
+survive their triangle test, the 64-survivor guard iterations, the guard batches that split an
+iteration's survivors and the survivors the guard rejected.  Cycles (s_memrealtime, 100 MHz, summed over waves): the whole primary / shadow / shading
 phase of each packet, and inside the traversals the node visits (of which the node load: issue
 to data), and the leaf-batch flushes.  The clock reads themselves perturb the timing (an SMEM
 round trip each), so the cycle split is a proportion, not a kernel time.
@@ -24,6 +26,7 @@ EVENTS = ["visits", "slots_tested", "slot_hits", "leafy_hits", "pair_hits", "inn
           "stack_pushes", "stack_pops", "flushes", "flush_iters"]
 CYCLES = ["prim_total", "prim_visit", "prim_load", "prim_flush", "shad_total", "shad_visit",
           "shad_load", "shad_flush", "shade", "frame", "waves"]
+DEFER = ["survivors", "guard_iters", "split_drains", "guard_rejected"]
 
 
 def main():
@@ -78,6 +81,13 @@ def main():
                                     if k not in ("frame", "waves")}}
     if n >= 34:  # mid-walk flushes by the remainder they carried (primary + shadow)
         res["midwalk_flushes_by_carry"] = dict(zip(["zero", "1_16", "48_63"], v[31:34]))
+    if n >= 42:  # the deferred guard (rt_internal.h kDf*), per traversal kind
+        for kind, at, tests in (("primary", 34, d["prim_leaf_lanes"]),
+                                ("shadow", 38, d["shad_leaf_lanes"])):
+            dv = dict(zip(DEFER, v[at:at + 4]))
+            dv["leaf_tests"] = tests
+            dv["survivor_share"] = round(dv["survivors"] / max(1, tests), 5)
+            res.setdefault("deferred_guard", {})[kind] = dv
     print(json.dumps(res))
 
 
