@@ -839,4 +839,93 @@ int cpuref_primary_records(const cpuref_scene* s, int cam, float* out8) {
   return 0;
 }
 
+// The shapes' primitives (triangles and spheres) are created in object-list order: every
+// mesh's faces in mesh order, the loose triangles, the spheres.  rank[shape] = that index.
+static std::vector<int> object_ranks(const Scene& sc) {
+  std::vector<int> rank(sc.shapes.size(), -1);
+  int k = 0;
+  for (size_t i = 0; i < sc.shapes.size(); i++)
+    if (sc.shapes[i].kind == kTri || sc.shapes[i].kind == kSphere) rank[i] = k++;
+  return rank;
+}
+
+int cpuref_intersect_rays(const cpuref_scene* s, long long n, const float* o3, const float* d3,
+                          float* out8, int* leaf_shape) {
+  if (n < 0 || !o3 || !d3 || !out8) return -1;
+  const Scene& sc = s->sc;
+  const std::vector<int> rank = leaf_shape ? object_ranks(sc) : std::vector<int>();
+  Counters ctr;
+  for (long long k = 0; k < n; k++) {
+    const Ray r{{o3[3 * k], o3[3 * k + 1], o3[3 * k + 2]},
+                {d3[3 * k], d3[3 * k + 1], d3[3 * k + 2]}, false};
+    Hit h{kInf, -1, {0, 0, 0}};
+    const bool hit = sc.intersect(sc.root, r, h, ctr);
+    float* o = out8 + 8 * k;
+    o[0] = r.d.x;
+    o[1] = r.d.y;
+    o[2] = r.d.z;
+    o[3] = hit ? h.t : 0.f;
+    o[4] = hit ? h.normal.x : 0.f;
+    o[5] = hit ? h.normal.y : 0.f;
+    o[6] = hit ? h.normal.z : 0.f;
+    o[7] = hit ? 1.f : 0.f;
+    if (leaf_shape) leaf_shape[k] = hit && h.shape >= 0 ? rank[h.shape] : -1;
+  }
+  return 0;
+}
+
+int cpuref_shade_rays(const cpuref_scene* s, long long n, const float* o3, const float* d3,
+                      int depth, int in_medium, float* rgb_t4, cpuref_stats* stats) {
+  if (n < 0 || !o3 || !d3 || !rgb_t4) return -1;
+  const Scene& sc = s->sc;
+  if (depth == -1) depth = sc.max_depth;
+  if (depth < 0 || depth > sc.max_depth) return -2;
+  // Rays are independent and the counters are integers: any split over threads gives the
+  // same bytes and the same sums.
+  int threads = (int)std::thread::hardware_concurrency();
+  threads = threads < 1 ? 1 : (threads > 8 ? 8 : threads);
+  if (n < 256) threads = 1;
+  std::vector<cpuref_stats> st(threads);
+  std::vector<Counters> ctr(threads * 3);
+  auto work = [&](int ti) {
+    cpuref_stats& S = st[ti];
+    std::memset(&S, 0, sizeof S);
+    Counters first;
+    for (long long k = n * ti / threads; k < n * (ti + 1) / threads; k++) {
+      const Ray r{{o3[3 * k], o3[3 * k + 1], o3[3 * k + 2]},
+                  {d3[3 * k], d3[3 * k + 1], d3[3 * k + 2]}, in_medium != 0};
+      const V3 col = sc.trace(r, depth, &ctr[ti * 3], &S);
+      S.primary_rays++;
+      Hit h{kInf, -1, {0, 0, 0}};  // the first hit again, for its t alone
+      const bool hit = sc.intersect(sc.root, r, h, first);
+      float* o = rgb_t4 + 4 * k;
+      o[0] = 0.0f + col.x * 1.0f;  // Pixel::add_color(color, 1) on a zeroed pixel
+      o[1] = 0.0f + col.y * 1.0f;
+      o[2] = 0.0f + col.z * 1.0f;
+      o[3] = hit ? h.t : kInf;
+    }
+  };
+  if (threads == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; t++) pool.emplace_back(work, t);
+    for (auto& t : pool) t.join();
+  }
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    for (int t = 0; t < threads; t++) {
+      stats->primary_rays += st[t].primary_rays;
+      stats->shadow_rays += st[t].shadow_rays;
+      stats->secondary_rays += st[t].secondary_rays;
+      stats->primary_hits += st[t].primary_hits;
+      for (int k = 0; k < 3; k++) {
+        stats->box_tests[k] += ctr[t * 3 + k].box;
+        stats->prim_tests[k] += ctr[t * 3 + k].prim;
+      }
+    }
+  }
+  return 0;
+}
+
 }  // extern "C"

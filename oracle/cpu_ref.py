@@ -49,8 +49,20 @@ def lib():
         L.cpuref_msaa_seed.restype = C.c_ulonglong
         L.cpuref_dump_bvh.argtypes = [C.c_void_p, C.c_char_p]
         L.cpuref_primary_records.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.cpuref_intersect_rays.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.cpuref_shade_rays.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_void_p, C.POINTER(Stats)]
         _LIB = L
     return _LIB
+
+
+def _rays(origins, directions):
+    o = np.ascontiguousarray(origins, np.float32)
+    d = np.ascontiguousarray(directions, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be (n, 3) arrays")
+    return o, d
 
 
 def minstd_uniform(seed: int, count: int) -> np.ndarray:
@@ -137,3 +149,27 @@ class OracleScene:
         out = np.zeros((info.height, info.width, 8), np.float32)
         lib().cpuref_primary_records(self._h, cam, out.ctypes.data)
         return out
+
+    def intersect_rays(self, origins, directions):
+        """bvh->intersect(Ray(o, d)) of caller-supplied rays (d as given, not normalised):
+        ((n, 8) records {d, t, normal, hit} as primary_records, (n,) the hit primitive's index
+        in object-list order or -1)."""
+        o, d = _rays(origins, directions)
+        out = np.zeros((len(o), 8), np.float32)
+        shape = np.full(len(o), -1, np.int32)
+        if lib().cpuref_intersect_rays(self._h, len(o), o.ctypes.data, d.ctypes.data,
+                                       out.ctypes.data, shape.ctypes.data):
+            raise RuntimeError("cpuref_intersect_rays failed")
+        return out, shape
+
+    def shade_rays(self, origins, directions, depth: int = -1, in_medium: bool = False):
+        """Scene::trace_ray(Ray{o, d, in_medium}, depth) of caller-supplied rays; depth -1 = the
+        scene's maximum.  Returns ((n, 4) {r, g, b, first hit's t or +inf}, Stats)."""
+        o, d = _rays(origins, directions)
+        out = np.zeros((len(o), 4), np.float32)
+        st = Stats()
+        rc = lib().cpuref_shade_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, int(depth),
+                                     int(bool(in_medium)), out.ctypes.data, C.byref(st))
+        if rc:
+            raise RuntimeError(f"cpuref_shade_rays failed ({rc})")
+        return out, st

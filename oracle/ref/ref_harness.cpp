@@ -16,6 +16,9 @@
 //                                                   get_color truncates; MSAA cameras)
 //   bvh    <xml> <out.txt>                          preorder BVH topology, floats as hex bits
 //   rays   <xml> <cam> <out.bin>                    per-pixel primary hit: t, normal (hex) + hit flag
+//   anyrays <xml> <rays.bin> <out.bin>              rays.bin: 24-B records (o, d), any origin and
+//                                                   direction; bvh->intersect(Ray(o, d)) of each,
+//                                                   written as the `rays` record
 //   time   <xml> <cam> <threads> <reps> <row_step> [warm]  median wall time of render_image
 //          over rows, after `warm` untimed renders
 //                                                   j = 0 (mod row_step); prints one JSON line
@@ -106,7 +109,7 @@ static long long count_rays(const Scene& scene, int cam, int first_row, int row_
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::cerr << "usage: ref_harness render|bvh|rays|time ..." << std::endl;
+    std::cerr << "usage: ref_harness render|resolved|png|bvh|rays|anyrays|time ..." << std::endl;
     return 2;
   }
   const std::string cmd = argv[1];
@@ -170,6 +173,28 @@ int main(int argc, char** argv) {
                         hit ? hd.normal.y : 0.f, hit ? hd.normal.z : 0.f, hit ? 1.f : 0.f};
         f.write(reinterpret_cast<const char*>(rec), sizeof rec);
       }
+  } else if (cmd == "anyrays") {
+    if (argc < 5) {
+      std::cerr << "usage: ref_harness anyrays <xml> <rays.bin> <out.bin>" << std::endl;
+      return 2;
+    }
+    std::ifstream in(argv[3], std::ios::binary);
+    if (!in) {
+      std::cerr << "cannot read " << argv[3] << std::endl;
+      return 1;
+    }
+    std::ofstream f(argv[4], std::ios::binary);
+    float od[6];
+    while (in.read(reinterpret_cast<char*>(od), sizeof od)) {
+      Hit_data hd;
+      hd.t = std::numeric_limits<float>::infinity();
+      hd.shape = NULL;
+      const Ray r(Vector3(od[0], od[1], od[2]), Vector3(od[3], od[4], od[5]));
+      const bool hit = scene.bvh->intersect(r, hd);
+      float rec[8] = {r.d.x, r.d.y, r.d.z, hit ? hd.t : 0.f, hit ? hd.normal.x : 0.f,
+                      hit ? hd.normal.y : 0.f, hit ? hd.normal.z : 0.f, hit ? 1.f : 0.f};
+      f.write(reinterpret_cast<const char*>(rec), sizeof rec);
+    }
   } else if (cmd == "time") {
     const int cam = std::atoi(argv[3]);
     const int threads = std::atoi(argv[4]);

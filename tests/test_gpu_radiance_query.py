@@ -15,11 +15,11 @@ import rq_util
 import scenes
 from conftest import assert_parity
 from oracle.cpu_ref import OracleScene
+from rq_util import INF, bits, shade_device, to_device
 
 pytestmark = pytest.mark.gpu
 
 FLAT = ["soup1", "hf_small", "single_sphere", "single_triangle", "graze_plane"]
-INF = np.float32(np.inf)
 MODES = ["fast", "reference"]
 
 
@@ -65,10 +65,6 @@ def with_depth(k):
     return change
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def same_bytes(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint8),
                           np.ascontiguousarray(b).view(np.uint8))
@@ -77,29 +73,6 @@ def same_bytes(a, b):
 def library_frames(s):
     """render_image of every camera as (n, 3) in ray order, concatenated."""
     return np.concatenate([s.render_image(c)[0].reshape(-1, 3) for c in range(s.num_cameras)])
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
-def shade_device(s, o, d, *, n=None, pad=0, stream=None, **kw):
-    """rt_shade_rays_device over the first n rays; the output holds `pad` more slots of 0xA5
-    bytes.  Returns (radiance[n], the pad slots' bytes)."""
-    import torch
-    import ceng795_amd
-    rays = ceng795_amd.pack_rays(o, d)
-    n = len(rays) if n is None else n
-    dr = to_device(rays) if len(rays) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    out = torch.full(((n + pad) * 16 + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-    st = torch.cuda.current_stream() if stream is None else stream
-    torch.cuda.synchronize()  # the buffers were filled on the current stream
-    with torch.cuda.stream(st):
-        s.shade_rays_device(dr.data_ptr(), n, out.data_ptr(), stream=st.cuda_stream, **kw)
-    st.synchronize()
-    raw = out.cpu().numpy()
-    return raw[:n * 16].view(ceng795_amd.RADIANCE_DTYPE).copy(), raw[n * 16:(n + pad) * 16]
 
 
 def assert_t_matches(rad, b, what):

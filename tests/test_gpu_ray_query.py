@@ -15,11 +15,11 @@ import desc_xml
 import rq_util
 from conftest import assert_parity
 from oracle.cpu_ref import OracleScene
+from rq_util import INF, assert_hits_match, bits, occlusion, same_records, to_device, trace
 
 pytestmark = pytest.mark.gpu
 
 SCENES = ["soup1", "hf_small", "single_sphere", "single_triangle", "graze_plane"]
-INF = np.float32(np.inf)
 
 
 @functools.lru_cache(maxsize=None)
@@ -35,70 +35,6 @@ def assert_mix(name, b):
     assert b.skipped_axis.sum() >= 100
     if name == "single_sphere":
         assert (b.hit & (b.t < 0)).sum() >= 50
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
-def trace(s, o, d, *, reorder=False, n=None, stream=None, pad=0, fill=0xA5):
-    """rt_trace_rays_device over the first n rays; the output holds `pad` more slots of `fill`
-    bytes.  Returns (hits[n], the pad slots' bytes)."""
-    import torch
-    import ceng795_amd
-    rays = ceng795_amd.pack_rays(o, d)
-    n = len(rays) if n is None else n
-    dr = to_device(rays) if len(rays) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    out = torch.full(((n + pad) * 32 + 32,), fill, dtype=torch.uint8, device="cuda")
-    st = torch.cuda.current_stream() if stream is None else stream
-    torch.cuda.synchronize()  # the buffers were filled on the current stream
-    with torch.cuda.stream(st):
-        s.trace_rays_device(dr.data_ptr(), n, out.data_ptr(), reorder=reorder,
-                            stream=st.cuda_stream)
-    st.synchronize()
-    raw = out.cpu().numpy()
-    return raw[:n * 32].view(ceng795_amd.HIT_DTYPE).copy(), raw[n * 32:(n + pad) * 32]
-
-
-def occlusion(s, o, d, tmax, *, reorder=False, n=None, stream=None, pad=0, fill=0xA5):
-    import torch
-    import ceng795_amd
-    rays = ceng795_amd.pack_rays(o, d, tmax)
-    n = len(rays) if n is None else n
-    dr = to_device(rays) if len(rays) else torch.zeros(32, dtype=torch.uint8, device="cuda")
-    out = torch.full((n + pad + 1,), fill, dtype=torch.uint8, device="cuda")
-    st = torch.cuda.current_stream() if stream is None else stream
-    torch.cuda.synchronize()  # the buffers were filled on the current stream
-    with torch.cuda.stream(st):
-        s.occluded_device(dr.data_ptr(), n, out.data_ptr(), reorder=reorder,
-                          stream=st.cuda_stream)
-    st.synchronize()
-    raw = out.cpu().numpy()
-    return raw[:n].copy(), raw[n:n + pad]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_hits_match(hits, b, what):
-    """t and normal bit-equal to the oracle's record, ids >= 0 exactly on its hits; a miss is
-    (+inf, -1, -1, -1, 0 0 0)."""
-    hit = b.hit
-    assert np.array_equal(hits["object"] >= 0, hit), what
-    assert np.array_equal(hits["leaf"] >= 0, hit) and np.array_equal(hits["material"] >= 0, hit), what
-    assert np.array_equal(bits(hits["t"][hit]), bits(b.t[hit])), what
-    assert np.array_equal(bits(hits["normal"][hit]), bits(b.normal[hit])), what
-    miss = ~hit
-    assert (bits(hits["t"][miss]) == bits(INF)).all(), what
-    for f in ("object", "material", "leaf"):
-        assert (hits[f][miss] == -1).all(), (what, f)
-    assert (bits(hits["normal"][miss]) == 0).all() and (hits["pad"] == 0).all(), what
-
-
-def same_records(a, b):
-    return np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def closest_hit_case(s, name, b, reorder):
