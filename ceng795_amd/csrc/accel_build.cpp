@@ -409,13 +409,44 @@ int collapse_wide(HostScene& s, const SahBuilder& B, int broot, const std::vecto
   return w0 | kWideTag;
 }
 
+// Copies 1..7 of the culling nodes after copy 0 (rt_internal.h DevNode8): in copy k every slot
+// word of an axis whose bit of k is set has its fp16 halves swapped, so a ray of direction-sign
+// octant k finds its ENTRY plane in the low half of every word, and inner_base points into the
+// same copy.
+void add_octant_copies(HostScene& s, size_t nref, size_t nw) {
+  s.accel_stride = 0;
+  if (kOctantCopies == 1) return;
+  s.accel_stride = (int)nw;
+  s.nodes.resize(nref + (size_t)kOctantCopies * nw);
+  for (int k = 1; k < kOctantCopies; k++)
+    for (size_t i = 0; i < nw; i += 2) {
+      DevNode8 W;
+      std::memcpy(&W, &s.nodes[nref + i], sizeof W);
+      if ((unsigned)W.kinds & ~((unsigned)W.kinds >> 8) & 0xffu) W.inner_base += k * (int)nw;
+      for (int c = 0; c < kWideSlots; c++)
+        for (int x = 0; x < 3; x++)
+          if (k >> x & 1) W.box[c][x] = W.box[c][x] << 16 | W.box[c][x] >> 16;
+      std::memcpy(&s.nodes[nref + (size_t)k * nw + i], &W, sizeof W);
+    }
+}
+
 }  // namespace
+
+std::string accel_slots_error(size_t ref_slots, size_t wide_slots) {
+  const size_t total = ref_slots + (size_t)kOctantCopies * wide_slots;
+  if (total < kMaxNodeSlots) return "";
+  return "scene too large for the culling tree: " + std::to_string(ref_slots) +
+         " reference node slots + " + std::to_string(kOctantCopies) + " x " +
+         std::to_string(wide_slots) + " culling node slots = " + std::to_string(total) +
+         ", the limit is " + std::to_string(kMaxNodeSlots - 1) + " (32-bit node byte offsets)";
+}
 
 void build_accel(HostScene& s, int K) {
   if (s.accel_root >= 0) s.nodes.resize(s.accel_root & ~kWideTag);  // drop an earlier culling tree
   s.accel_root = -1;
   s.accel_depth = 0;
   s.accel_items = 0;
+  s.accel_stride = 0;
   s.ancestry.clear();
   s.leaves.clear();
   K = std::min(K, 2);
@@ -499,13 +530,11 @@ void build_accel(HostScene& s, int K) {
   }
   s.accel_items = (int)items.size();
   s.accel_root = collapse_wide(s, B, broot, holder, ref_box);
-  if (s.nodes.size() >= kMaxNodeSlots) {  // the kernels address wide nodes by 32-bit byte offset
-    s.nodes.resize(s.accel_root & ~kWideTag);
-    s.accel_root = -1;  // (the reference traversal has no such limit)
-    s.accel_depth = 0;
-    s.accel_items = 0;
-    s.leaves.clear();
-  }
+  const size_t nref = (size_t)(s.accel_root & ~kWideTag), nw = s.nodes.size() - nref;
+  // the kernels address wide nodes by 32-bit byte offset
+  const std::string err = accel_slots_error(nref, nw);
+  if (!err.empty()) throw std::domain_error(err);
+  add_octant_copies(s, nref, nw);
 }
 
 // Structural invariants of the culling tree the kernels' exactness argument relies on
@@ -542,6 +571,13 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
   struct Frame {
     int node, depth;
   };
+  // copy 0 of the culling nodes: [nref, nref + ncull); the octant copies follow it
+  const size_t ncull = s.accel_stride > 0 ? (size_t)s.accel_stride : s.nodes.size() - (size_t)nref;
+  if ((kOctantCopies > 1) != (s.accel_stride > 0)) return "octant copies and their stride disagree";
+  if (s.nodes.size() != (size_t)nref + (size_t)kOctantCopies * ncull || ncull % 2)
+    return "node array is not the reference nodes and " + std::to_string(kOctantCopies) +
+           " copies of the culling nodes";
+  if (!accel_slots_error((size_t)nref, ncull).empty()) return "node array past the offset limit";
   std::vector<Frame> todo{{s.accel_root, 1}};
   std::vector<int> order;
   std::vector<double> ulo(s.nodes.size() * 3, INFINITY), uhi(s.nodes.size() * 3, -INFINITY);
@@ -550,7 +586,7 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
     todo.pop_back();
     if (!(f.node & kWideTag)) return "culling child is not a wide node";
     const int idx = f.node & ~kWideTag;
-    if (idx < nref || (size_t)idx + 1 >= s.nodes.size()) return "wide node index out of range";
+    if (idx < nref || (size_t)idx + 1 >= (size_t)nref + ncull) return "wide node index out of range";
     DevNode8 W;
     std::memcpy(&W, &s.nodes[idx], sizeof W);
     nodes++;
@@ -644,6 +680,27 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
   for (int a = 0; a < 3; a++)
     if (s.accel_box[a] > ulo[r0 + a] || s.accel_box[a + 3] < uhi[r0 + a])
       return "culling root box does not contain the tree";
+  // octant copies: copy k is copy 0 with the halves of its set axes' slot words swapped and its
+  // inner children in copy k (every slot of copy 0, reached or not, so a copy holds nothing else)
+  for (int k = 1; k < kOctantCopies; k++)
+    for (size_t i = 0; i < ncull; i += 2) {
+      DevNode8 W, C;
+      std::memcpy(&W, &s.nodes[nref + i], sizeof W);
+      std::memcpy(&C, &s.nodes[nref + (size_t)k * ncull + i], sizeof C);
+      const bool has_inner = ((unsigned)W.kinds & ~((unsigned)W.kinds >> 8) & 0xffu) != 0;
+      if (C.inner_base != W.inner_base + (has_inner ? k * (int)ncull : 0))
+        return "octant copy " + std::to_string(k) + ": inner_base not shifted by k * stride";
+      for (int c = 0; c < kWideSlots; c++)
+        for (int x = 0; x < 3; x++) {
+          const uint32_t w = W.box[c][x];
+          if (C.box[c][x] != ((k >> x & 1) ? (w << 16 | w >> 16) : w))
+            return "octant copy " + std::to_string(k) + ": slot word halves not as its octant's";
+        }
+      C.inner_base = W.inner_base;
+      std::memcpy(C.box, W.box, sizeof C.box);
+      if (std::memcmp(&C, &W, sizeof W))
+        return "octant copy " + std::to_string(k) + " differs from copy 0 outside the planes";
+    }
   stats[0] = items;
   stats[1] = nodes;
   stats[3] = lone;

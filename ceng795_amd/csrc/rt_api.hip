@@ -505,6 +505,7 @@ RenderParams scene_params(const rt_scene* s, const Replica& r) {
   P.root_ref = h.root_ref;
   std::memcpy(P.root_box, h.root_box, sizeof P.root_box);
   P.accel_root = h.accel_root;
+  P.accel_stride = h.accel_stride;
   P.quot_ok = h.quot_ok;
   std::memcpy(P.accel_box, h.accel_box, sizeof P.accel_box);
   P.anc = r.d_anc.p;
@@ -1600,6 +1601,13 @@ int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long l
     accel_slot_histogram(h, hist9);
     return RT_OK;
   });
+}
+
+int rt_host_accel_slots_check(long long ref_slots, long long wide_slots) {
+  if (ref_slots < 0 || wide_slots < 0)
+    return set_error(RT_E_INVALID, "rt_host_accel_slots_check: bad argument");
+  const std::string err = accel_slots_error((size_t)ref_slots, (size_t)wide_slots);
+  return err.empty() ? RT_OK : set_error(RT_E_UNSUPPORTED, err);
 }
 
 int rt_set_traversal(rt_scene* s, int mode) {

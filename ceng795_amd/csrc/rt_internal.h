@@ -48,7 +48,11 @@ enum : int {
   kPhCarryZero, kPhCarryLow, kPhCarryHigh,
   // the leaf batch's deferred guard, kDeferEvents values per traversal kind:
   // primary from kPhDeferPrim, shadow from kPhDeferShad
-  kPhDeferPrim, kPhDeferShad = kPhDeferPrim + 4, kPhaseSlots = kPhDeferShad + 4
+  kPhDeferPrim, kPhDeferShad = kPhDeferPrim + 4,
+  // the frame kernel's octant loop: packets with an active lane and their sub-walks (one per
+  // direction-sign octant among the active lanes), primary then shadow (per light)
+  kPhOctPrimPackets = kPhDeferShad + 4, kPhOctPrimWalks, kPhOctShadPackets, kPhOctShadWalks,
+  kPhaseSlots
 };
 // Per traversal kind: queued tests whose triangle / sphere test hit in range (the only ones whose
 // guard decision is used), the 64-survivor guard iterations, the guard batches in which one
@@ -84,8 +88,27 @@ static_assert(sizeof(DevNode) == 64, "node must be one 64-byte scalar load");
 // exact decision (the treelet's guard box) is taken per ray in the leaf batch.  An invalid
 // slot holds NaN planes, which every slab test rejects.
 constexpr int32_t kWideTag = 1 << 30;
-// node slots a scene may have with a culling tree: the traversal loads a wide node at the 32-bit
-// byte offset (ref << 6) (rt_kernels.hip load_node8); larger scenes walk the reference tree
+// The culling nodes exist once per direction-sign octant (RT_OCTANT_NODES):
+// copy k = (1/d_x < 0) | (1/d_y < 0) << 1 | (1/d_z < 0) << 2 follows copy k - 1 at a stride of
+// HostScene::accel_stride node slots (RenderParams::accel_stride).  In copy k the slot words
+// box[c][x] of every axis x whose bit of k is set have their halves swapped — the ENTRY plane of
+// a ray of octant k is the low half of every word — and inner_base points into the same copy, so
+// a walk that starts at accel_root + k * stride stays in copy k.  leaf_base, kinds, offs and the
+// leaf records are the same in every copy.
+//   RT_OCTANT_NODES  0: no copies, the frame kernel orders the planes per lane (v_alignbit) like
+//                       every other kernel;  1 (A/B builds): the copies, walked per octant, with
+//                       the v_alignbit kept (shift 0);  2: the frame kernel reads the halves
+//                       as they lie.
+#ifndef RT_OCTANT_NODES
+#define RT_OCTANT_NODES 2
+#endif
+static_assert(RT_OCTANT_NODES >= 0 && RT_OCTANT_NODES <= 2, "RT_OCTANT_NODES: 0, 1 or 2");
+constexpr int kOctantNodes = RT_OCTANT_NODES;
+constexpr int kOctantCopies = kOctantNodes ? 8 : 1;
+// node slots a scene may have: the traversal loads a wide node at the 32-bit byte offset
+// (ref << 6) (rt_kernels.hip load_node8), so reference slots + kOctantCopies x culling slots
+// stay below 2^26 (about 22 M triangles with eight copies); a larger scene is refused
+// (accel_build.cpp accel_slots_error)
 constexpr size_t kMaxNodeSlots = size_t(1) << 26;
 constexpr int kWideSlots = 8;
 enum : int32_t { kSlotValid = 1, kSlotLeafy = 1 << 8, kSlotPair = 1 << 16 };
@@ -277,6 +300,9 @@ struct RenderParams {
   // every triangle's v0 coordinate is 0 or in [2^-26, 2^48] (quot_coord_ok): the triangle
   // test may take the shared-reciprocal quotient path (rt_kernels.hip, tri_quotients)
   int quot_ok;
+  // node slots between the culling tree's octant copies (0: there are none); the root of octant k
+  // is accel_root + k * accel_stride.  (In what was padding: no other field moved.)
+  int accel_stride;
   const struct DevAncestry* anc;
   // camera (rt_camera)
   float cam_e[3], cam_tl[3], cam_su[3], cam_sv[3];

@@ -49,6 +49,7 @@ struct Diag {  // per-wave traversal work (RT_DIAG builds)
   unsigned long long cyc_visit = 0, cyc_load = 0, cyc_flush = 0;
   unsigned long long carry[3] = {};  // mid-walk flushes that carried 0 / 1-16 / 48-63 entries
   unsigned long long defer[kDeferEvents] = {};  // the deferred guard's kDf* counts
+  unsigned long long oct_packets = 0, oct_walks = 0;  // octant_walks: loops entered, sub-walks
 };
 #ifdef RT_DIAG
 // [0, kPhaseEvents): primary events, [kPhaseEvents, 2 kPhaseEvents): shadow events, then the
@@ -880,7 +881,10 @@ __device__ __forceinline__ float half_hi(int w) {
 // so a slot costs 3 alignbit + 6 fma_mix + max3 + min3 + 2 compares instead of a min and a max
 // per axis on top (same values: the entry plane moved down, the exit plane up by |m|).  A
 // skipped axis (SKIP) gets S = 0 and planes -inf / +inf, once per visit.
-template <bool SKIP, bool SHADOW, bool DEEP, bool SPHERES>
+// COHERENT (the frame kernel, RT_OCTANT_NODES 2): the node belongs to the octant copy of every
+// lane in `m` (octant_walks), whose words already hold the entry plane low — the same halves
+// reach the same fma_mix operands with no v_alignbit and no use of sh.
+template <bool SKIP, bool SHADOW, bool DEEP, bool SPHERES, bool COHERENT = false>
 __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode* __restrict__ nodes,
                                            WaveLeafLds& L, int& pending, const LaneRay& r, int& node,
                                            uint64_t& m, uint64_t alive, WaveStack<DEEP>& st,
@@ -895,7 +899,7 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
   const unsigned inner = (unsigned)kinds & ~((unsigned)kinds >> 8) & 0xffu;
   DIAG(dg.nodes++; dg.wide++; dg.node_lanes += __builtin_popcountll(m));
   const float o[3] = {r.o.x, r.o.y, r.o.z}, rc[3] = {r.r.x, r.r.y, r.r.z}, mg[3] = {r.m.x, r.m.y, r.m.z};
-  const int sh[3] = {r.sh0, r.sh1, r.sh2};
+  [[maybe_unused]] const int sh[3] = {r.sh0, r.sh1, r.sh2};
   float S[3], Alo[3], Ahi[3];
 #pragma unroll
   for (int x = 0; x < 3; x++) {
@@ -922,10 +926,10 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
     float n3[3], f3[3];
 #pragma unroll
     for (int x = 0; x < 3; x++) {
-      // this lane's entry plane into the low half
-      const int w = (int)__builtin_amdgcn_alignbit((unsigned)RT_NODE_WORD(8 + 3 * c + x),
-                                                   (unsigned)RT_NODE_WORD(8 + 3 * c + x),
-                                                   (unsigned)sh[x]);
+      // this lane's entry plane into the low half (COHERENT: the copy holds it there)
+      int w = RT_NODE_WORD(8 + 3 * c + x);
+      if (!COHERENT)
+        w = (int)__builtin_amdgcn_alignbit((unsigned)w, (unsigned)w, (unsigned)sh[x]);
       n3[x] = __builtin_fmaf(half_lo(w), S[x], Alo[x]);
       f3[x] = __builtin_fmaf(half_hi(w), S[x], Ahi[x]);
     }
@@ -998,13 +1002,23 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
 // The reference's (t, leaf) for every active ray: leaf < 0 = miss.  FAST: the 8-wide culling
 // tree over reference treelets (the launch takes it only when the scene has one); otherwise
 // the reference tree itself.  CAMERA: all rays share one origin (batch_flush).
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false>
+// OCT != 0 (FAST only; the frame kernel's octant_walks): one sub-walk of a packet — the active
+// lanes share direction-sign octant k and the walk starts at that octant's copy of the culling
+// nodes, accel_root + root_off (root_off = k * accel_stride).  The caller presets every lane's
+// L.key and reads the packet's result from it after the last sub-walk; best_t and
+// best_leaf are not set.  OCT == 2: the copy's plane order is read as it lies (visit_wide COHERENT).
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false, int OCT = 0>
 __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode* __restrict__ nodes,
                                             int* spill, WaveLeafLds& L, const LaneRay& r,
-                                            bool active, float& best_t, int& best_leaf, Diag& dg) {
-  best_t = RT_INF;
-  best_leaf = -1;
-  if (P.root_kind != kRootNode) {  // the root IS the primitive (BVH.h:13-14): its own rule
+                                            bool active, float& best_t, int& best_leaf, Diag& dg,
+                                            int root_off = 0) {
+  static_assert(!OCT || FAST, "octant copies exist of the culling nodes only");
+  if (!OCT) {
+    best_t = RT_INF;
+    best_leaf = -1;
+  }
+  // (a FAST launch has a node root, use_fast)
+  if (!OCT && P.root_kind != kRootNode) {  // the root IS the primitive (BVH.h:13-14): its own rule
     float t;
     if (active && leaf_test<SPHERES>(P.prims, P.root_ref, r, t)) {
       best_t = t;
@@ -1029,8 +1043,8 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   WaveStack<DEEP> st;
   st.lds = spill;
   int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
-  L.key[lane] = kNoHitKey;
-  int node = FAST ? P.accel_root : P.root_ref;
+  if (!OCT) L.key[lane] = kNoHitKey;
+  int node = FAST ? P.accel_root + root_off : P.root_ref;
   for (;;) {
     if (pending >= kBatchFlush) {  // between visits: only the ray and the stack are live
       DIAG(const unsigned long long tf0 = clock_now());
@@ -1043,7 +1057,8 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
       RT_PRIO_VISIT_BEGIN;
       const bool more =
-          visit_wide<SKIP, false, DEEP, SPHERES>(P, nodes, L, pending, r, node, m, ~0ull, st, dg);
+          visit_wide<SKIP, false, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, ~0ull,
+                                                           st, dg);
       RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
@@ -1069,19 +1084,24 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
          dg.ev[kPhFlushIters] += (pending + 63) / 64);
   }
   DIAG(dg.ev[kPhPushes] += st.pushes; dg.ev[kPhPops] += st.pops);
-  const unsigned long long key = L.key[lane];
-  best_t = __uint_as_float((unsigned)(key >> 32));
-  best_leaf = (int)(unsigned)key;
+  if (!OCT) {
+    const unsigned long long key = L.key[lane];
+    best_t = __uint_as_float((unsigned)(key >> 32));
+    best_leaf = (int)(unsigned)key;
+  }
 }
 
 // ------------------------------------------------------------------ shadow (any hit)
 // Occluded iff some leaf the ray may reach has 0 < t < thr — identical to the reference's
 // closest-hit shadow test `0 < t_closest < dist - eps` (HW2/Scene.cpp:123-127), appendix A.7.
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES>
+// OCT != 0: one sub-walk of a packet, as in closest_hit — the caller clears every lane's L.key
+// and reads it after the last sub-walk; the value returned then covers the lanes walked so far.
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, int OCT = 0>
 __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          int* spill, WaveLeafLds& L, const LaneRay& r, bool active,
-                                         float thr, Diag& dg) {
-  if (P.root_kind != kRootNode) {
+                                         float thr, Diag& dg, int root_off = 0) {
+  static_assert(!OCT || FAST, "octant copies exist of the culling nodes only");
+  if (!OCT && P.root_kind != kRootNode) {
     float t;
     return active && leaf_test<SPHERES>(P.prims, P.root_ref, r, t) && t < thr && t > 0.0f;
   }
@@ -1104,10 +1124,12 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
   WaveStack<DEEP> st;
   st.lds = spill;
   int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
-  unsigned long long clear = 0ull;
-  asm volatile("" : "+v"(clear));  // a fresh zero here, not one kept (and spilled) across the walk
-  L.key[lane] = clear;
-  int node = FAST ? P.accel_root : P.root_ref;
+  if (!OCT) {
+    unsigned long long clear = 0ull;
+    asm volatile("" : "+v"(clear));  // a fresh zero here, not one kept (and spilled) across the walk
+    L.key[lane] = clear;
+  }
+  int node = FAST ? P.accel_root + root_off : P.root_ref;
   for (;;) {
     if (pending >= kShadowFlush) {  // between visits; a lane found occluded stops entering nodes
       DIAG(const unsigned long long tf0 = clock_now());
@@ -1123,7 +1145,8 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
       RT_PRIO_VISIT_BEGIN;
       const bool more =
-          visit_wide<SKIP, true, DEEP, SPHERES>(P, nodes, L, pending, r, node, m, alive, st, dg);
+          visit_wide<SKIP, true, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, alive,
+                                                          st, dg);
       RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
@@ -1274,6 +1297,40 @@ __device__ __forceinline__ unsigned long long* counter_row(const RenderParams& P
 __device__ __forceinline__ float hit_t(int2_t rec) { return __int_as_float(rec.y); }
 __device__ __forceinline__ int hit_leaf(int2_t rec) { return rec.x; }
 
+// The frame kernel's walks over the octant copies of the culling nodes (RT_OCTANT_NODES,
+// rt_internal.h).  A lane's octant is the sign of its three reciprocals — per axis exactly the
+// predicate behind LaneRay::sh, so +-0 and skipped axes fall where the per-lane order puts them
+// (a skipped axis has S = 0 and planes at -+inf: either copy gives the same distances).
+__device__ __forceinline__ int lane_octant(const LaneRay& r) {
+  return (int)((__float_as_uint(r.r.x) >> 31) | ((__float_as_uint(r.r.y) >> 31) << 1) |
+               ((__float_as_uint(r.r.z) >> 31) << 2));
+}
+// Calls walk(mine, k) once per octant k present among the `active` lanes, `mine` being this lane's
+// membership: a wave-uniform loop — the first remaining lane's octant, the lanes that share it,
+// their walk, and again without them.  A camera's or a light's rays change sign along a line
+// through the image, so nearly every packet makes one walk.  Each lane takes part in exactly one
+// walk, and the walks leave their results per lane in L.key, so their order does not matter.
+// The octant is recomputed from the ray per walk, not kept in a register across one.
+template <typename F>
+__device__ __forceinline__ void octant_walks(const LaneRay& r, bool active, Diag& dg, F&& walk) {
+  uint64_t rest = ballot(active);
+  DIAG(dg.oct_packets += rest != 0);
+  while (rest) {
+    const int oct = lane_octant(r);
+    const int k = __builtin_amdgcn_readlane(oct, (int)__builtin_ctzll(rest));
+    const bool mine = lane_in(rest) && oct == k;
+    rest &= ~ballot(mine);
+    DIAG(dg.oct_walks++);
+    walk(mine, k);
+  }
+}
+// (A/B builds) RT_OCTANT_NODES 1: the walk keeps its v_alignbit with a shift of 0 — the copy
+// already holds the octant's order — in three VGPRs the compiler cannot fold.
+__device__ __forceinline__ void octant_shifts_zero(LaneRay& r) {
+  r.sh0 = r.sh1 = r.sh2 = 0;
+  asm volatile("" : "+v"(r.sh0), "+v"(r.sh1), "+v"(r.sh2));
+}
+
 // One wave = the 8x8 packet of selected tile `sel` (< num_sel_tiles): closest hit per pixel
 // into its 8-B record.
 #ifndef RT_CAMERA_ORIGIN  // (A/B builds: 0 = the leaf batch fetches the owner's origin here too)
@@ -1295,10 +1352,26 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   int leaf;
   // (CAMERA: every lane's origin is cam_e, so the leaf batch fetches no owner origin)
   constexpr bool kCam = RT_CAMERA_ORIGIN != 0;
-  if (ballot(any_skip))
+  if constexpr (FAST && kOctantNodes != 0) {
+    if (kOctantNodes == 1) octant_shifts_zero(ray);
+    L.key[lane_id()] = kNoHitKey;
+    octant_walks(ray, q.valid, dg, [&](bool mine, int k) {
+      const int off = k * P.accel_stride;
+      if (ballot(mine && any_skip))
+        closest_hit<true, FAST, DEEP, SPHERES, kCam, kOctantNodes>(P, nodes, spill, L, ray, mine, t,
+                                                                   leaf, dg, off);
+      else
+        closest_hit<false, FAST, DEEP, SPHERES, kCam, kOctantNodes>(P, nodes, spill, L, ray, mine, t,
+                                                                    leaf, dg, off);
+    });
+    const unsigned long long key = L.key[lane_id()];
+    t = __uint_as_float((unsigned)(key >> 32));
+    leaf = (int)(unsigned)key;
+  } else if (ballot(any_skip)) {
     closest_hit<true, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
-  else
+  } else {
     closest_hit<false, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+  }
   const RenderParams& Pw = fresh_params(P);  // post-traversal fields: not live across it
   const PacketPixel qw = packet_pixel(Pw, sel, wave_sub(L));  // (recomputed, not kept)
   int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
@@ -1324,6 +1397,8 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     atomicAdd(&g_phase[kPhCycPrimFlush], dg.cyc_flush);
     for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
     for (int k = 0; k < kDeferEvents; k++) atomicAdd(&g_phase[kPhDeferPrim + k], dg.defer[k]);
+    atomicAdd(&g_phase[kPhOctPrimPackets], dg.oct_packets);
+    atomicAdd(&g_phase[kPhOctPrimWalks], dg.oct_walks);
 #endif
   }
 }
@@ -1363,12 +1438,28 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       const V3 ld = ld3(lt.position) - pk;
       const V3 wi = normalize(ld);
       const float dist = length(ld);
-      const LaneRay sr = make_ray(pk + wi * P.eps, wi, P.quot_ok);  // p + eps * w_i
+      LaneRay sr = make_ray(pk + wi * P.eps, wi, P.quot_ok);  // p + eps * w_i
       const float thr = dist - P.eps;
       const bool any_skip = hit && (sr.skip0 || sr.skip1 || sr.skip2);
-      const bool occ = ballot(any_skip)
-                           ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg)
-                           : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg);
+      bool occ;
+      if constexpr (FAST && kOctantNodes != 0) {
+        if (kOctantNodes == 1) octant_shifts_zero(sr);
+        unsigned long long clear = 0ull;
+        asm volatile("" : "+v"(clear));  // (a fresh zero, as in occluded)
+        L.key[lane_l] = clear;
+        octant_walks(sr, hit, dg, [&](bool mine, int k) {
+          const int off = k * P.accel_stride;
+          if (ballot(mine && any_skip))
+            occluded<true, FAST, DEEP, SPHERES, kOctantNodes>(P, nodes, spill, L, sr, mine, thr, dg, off);
+          else
+            occluded<false, FAST, DEEP, SPHERES, kOctantNodes>(P, nodes, spill, L, sr, mine, thr, dg, off);
+        });
+        occ = L.key[fresh_lane()] != 0ull;
+      } else {
+        occ = ballot(any_skip)
+                  ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg)
+                  : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg);
+      }
       bits |= (occ ? 1u : 0u) << (li - 32 * w);
     }
     const RenderParams& Pw = fresh_params(P0);
@@ -1398,6 +1489,8 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       atomicAdd(&g_phase[kPhCycShadFlush], dg.cyc_flush);
       for (int k = 0; k < 3; k++) atomicAdd(&g_phase[kPhCarryZero + k], dg.carry[k]);
       for (int k = 0; k < kDeferEvents; k++) atomicAdd(&g_phase[kPhDeferShad + k], dg.defer[k]);
+      atomicAdd(&g_phase[kPhOctShadPackets], dg.oct_packets);
+      atomicAdd(&g_phase[kPhOctShadWalks], dg.oct_walks);
 #endif
     }
   }

@@ -196,6 +196,11 @@ int rt_host_check_accel_xml(const char* xml_path, int treelet_leaves, long long*
 /* Host-only: builds and checks the culling tree as above, then hist9[v] = its 8-wide nodes with
  * v valid slots (v = 0..8; all zero when the tree is a single treelet). */
 int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long long* hist9);
+/* Host-only: the size rule a scene's node array must pass (the kernels address culling nodes by
+ * 32-bit byte offset, and the culling nodes are stored once per direction-sign octant, DESIGN.md
+ * §3): RT_OK when ref_slots reference node slots and wide_slots culling node slots (one copy) fit,
+ * else RT_E_UNSUPPORTED with the message scene creation fails with in rt_last_error(). */
+int rt_host_accel_slots_check(long long ref_slots, long long wide_slots);
 /* Height of the flattened BVH (levels of internal nodes). */
 int rt_scene_bvh_depth(const rt_scene* scene);
 

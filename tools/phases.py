@@ -88,6 +88,9 @@ def main():
             dv["leaf_tests"] = tests
             dv["survivor_share"] = round(dv["survivors"] / max(1, tests), 5)
             res.setdefault("deferred_guard", {})[kind] = dv
+    if n >= 46:  # the octant loop (rt_internal.h kPhOct*): packets with an active lane, sub-walks
+        res["octant_walks"] = {"primary": dict(zip(["packets", "walks"], v[42:44])),
+                               "shadow": dict(zip(["packets", "walks"], v[44:46]))}
     print(json.dumps(res))
 
 
