@@ -1610,6 +1610,45 @@ int rt_host_accel_slots_check(long long ref_slots, long long wide_slots) {
   return err.empty() ? RT_OK : set_error(RT_E_UNSUPPORTED, err);
 }
 
+int rt_host_packet_div(int divisor, int first, int count, int* quot) {
+  if (divisor < 1 || first < 0 || count < 0 || (long long)first + count > (1ll << 31) || !quot)
+    return set_error(RT_E_INVALID, "rt_host_packet_div: bad argument");
+  const DivMagic m = div_magic(divisor);
+  for (int i = 0; i < count; i++) quot[i] = div_by((int)((long long)first + i), m);
+  return RT_OK;
+}
+
+int rt_host_packet_coords(int tiles_x, int num_sel_tiles, int tile_begin, int tile_step,
+                          int block_deal, int order_regions, int order_stride, int count,
+                          int* out4) {
+  if (tiles_x < 1 || num_sel_tiles < 0 || tile_begin < 0 || tile_step < 1 || order_regions < 1 ||
+      order_stride < 0 || count < 0 || !out4)
+    return set_error(RT_E_INVALID, "rt_host_packet_coords: bad argument");
+  RenderParams P;
+  std::memset(&P, 0, sizeof P);
+  P.tiles_x = tiles_x;
+  P.num_sel_tiles = num_sel_tiles;
+  P.tile_begin = tile_begin;
+  P.tile_step = tile_step;
+  P.block_deal = block_deal ? 1 : 0;
+  P.order_regions = order_regions;
+  P.order_stride = order_stride;
+  P.tile_block = whole_tile_rows(P);
+  const PacketGeom G = packet_geom(P);
+  for (int p = 0; p < count; p++) {
+    // (a wave's tile as dispatch_sel takes it: logical packet p of a launch in block order)
+    int sel = p < G.packets ? packet_sel(P, G, p) : -1;
+    if (sel >= P.num_sel_tiles) sel = -1;
+    int tx = -1, ty = -1;
+    if (sel >= 0) sel_tile(P, G, sel, tx, ty);
+    out4[4 * p] = sel;
+    out4[4 * p + 1] = tx;
+    out4[4 * p + 2] = ty;
+    out4[4 * p + 3] = order_slot(P, G, p);
+  }
+  return G.packets;
+}
+
 int rt_set_traversal(rt_scene* s, int mode) {
   if (!s || (mode != RT_TRAVERSAL_FAST && mode != RT_TRAVERSAL_REFERENCE))
     return set_error(RT_E_INVALID, "rt_set_traversal: bad argument");

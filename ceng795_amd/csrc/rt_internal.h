@@ -52,6 +52,13 @@ enum : int {
   // the frame kernel's octant loop: packets with an active lane and their sub-walks (one per
   // direction-sign octant among the active lanes), primary then shadow (per light)
   kPhOctPrimPackets = kPhDeferShad + 4, kPhOctPrimWalks, kPhOctShadPackets, kPhOctShadWalks,
+  // a packet's time outside its walks: the prologue (kernel entry until the wave has its tile),
+  // then per traversal kind the set-up before the walks (pixel, ray; per light in the shadow
+  // phase), the walks themselves and the tail after them (record / occlusion store, the ray
+  // counters); stamped before the diagnostic atomics, which fall into no section (the phase
+  // totals above still enclose them)
+  kPhCycPrologue, kPhCycPrimSetup, kPhCycPrimWalk, kPhCycPrimTail, kPhCycShadSetup,
+  kPhCycShadWalk, kPhCycShadTail,
   kPhaseSlots
 };
 // Per traversal kind: queued tests whose triangle / sphere test hit in range (the only ones whose
@@ -278,6 +285,50 @@ struct UntileParams {
 constexpr unsigned long long sched_words_for(unsigned long long tiles) { return 10 * tiles + 64; }
 constexpr unsigned long long sched_snap_offset(unsigned long long tiles) { return 9 * tiles + 64; }
 
+// Traversal workgroups (the frame kernel's): kTraceWaves packets, which with
+// RenderParams::tile_block form a kBlockW x kBlockH block of tiles (rt_kernels.hip).
+#ifndef RT_TRACE_WAVES
+#define RT_TRACE_WAVES 2
+#endif
+constexpr int kTraceWaves = RT_TRACE_WAVES;
+static_assert(kTraceWaves == 1 || kTraceWaves == 2 || kTraceWaves == 4, "1, 2 or 4 waves");
+constexpr int kBlockW = kTraceWaves >= 2 ? 2 : 1, kBlockH = kTraceWaves / kBlockW;
+
+// n / d for every 0 <= n < 2^31 as one 32 x 32 -> 64-bit multiply and a shift, the divisor being
+// wave-uniform but known only at launch (the compiler expands such a division into ~28 dependent
+// instructions).  With s = ceil(log2 d), k = 31 + s and mul = ceil(2^k / d) < 2^32:
+// mul d = 2^k + e, 0 <= e < d <= 2^s, so n mul / 2^k = n / d + n e / (d 2^k) and the excess is
+// below 1 / d because n e < 2^31 2^s = 2^k — the floor is the quotient's.
+struct DivMagic {
+  unsigned mul;
+  int shift;  // k: 31 .. 62
+};
+RT_HD inline DivMagic div_magic(int d) {
+  const unsigned long long ud = d < 1 ? 1ull : (unsigned long long)d;
+  int s = 0;
+  while ((1ull << s) < ud) s++;
+  DivMagic m;
+  m.shift = 31 + s;
+  m.mul = (unsigned)(((1ull << m.shift) + ud - 1) / ud);
+  return m;
+}
+RT_HD inline int div_by(int n, DivMagic m) {
+  return (int)(((unsigned long long)(unsigned)n * m.mul) >> m.shift);
+}
+
+// What a traversal launch's index arithmetic divides by, worked out once on the host
+// (packet_geom below, called by order_geometry in rt_kernels.hip) instead of by every wave: an
+// argument of its own of the kernels that use it, so RenderParams keeps its layout.
+struct PacketGeom {
+  DivMagic by_tiles_x;    // a tile's row and column
+  DivMagic by_deal_nbx;   // block deal: blocks per block row (deal_blocks_x)
+  DivMagic by_block_nbx;  // tile_block: workgroup blocks per block row
+  DivMagic by_regions;    // ordered dispatch: a workgroup's region and list entry
+  int block_nbx;          // ceil(tiles_x / kBlockW)
+  int sel_rows;           // the selection's tile rows, num_sel_tiles / tiles_x (tile_block)
+  int packets;            // trace_packets
+};
+
 struct RenderParams {
   const DevNode* nodes;
   const DevLeaf* leaves;  // culling-tree order (DevLeaf), FAST traversal
@@ -354,6 +405,81 @@ struct RenderParams {
   // kCounterRows rows of kCounterWidth u64 (columns: kCnt*)
   unsigned long long* counters;
 };
+
+// ------------------------------------------------------------------ packet index arithmetic
+// Which tile a wave of a traversal launch takes: shared by the kernels and the host (the CPU
+// test runs these very functions, rt_host_packet_coords).  No run-time division on the device:
+// the quotients come from the launch's PacketGeom G.
+
+// RenderParams::tile_block of a launch: its selection is whole tile rows in frame order.
+inline int whole_tile_rows(const RenderParams& P) {
+  return P.tile_step == 1 && !P.block_deal && P.tile_begin % P.tiles_x == 0 &&
+         P.num_sel_tiles % P.tiles_x == 0;
+}
+
+// Logical packets of a traversal launch (with tile_block, padded to whole blocks).  Host side:
+// the device reads G.packets.
+RT_HD inline int trace_packets(const RenderParams& P) {
+  if (!P.tile_block) return P.num_sel_tiles;
+  const int tiles_y = P.num_sel_tiles / P.tiles_x;
+  return ((P.tiles_x + kBlockW - 1) / kBlockW) * ((tiles_y + kBlockH - 1) / kBlockH) * kTraceWaves;
+}
+
+// The PacketGeom of P's tiles_x, num_sel_tiles, tile_block and order_regions.
+RT_HD inline PacketGeom packet_geom(const RenderParams& P) {
+  PacketGeom g;
+  g.block_nbx = (P.tiles_x + kBlockW - 1) / kBlockW;
+  g.by_tiles_x = div_magic(P.tiles_x);
+  g.by_deal_nbx = div_magic(deal_blocks_x(P.tiles_x));
+  g.by_block_nbx = div_magic(g.block_nbx);
+  g.by_regions = div_magic(P.order_regions);
+  g.sel_rows = P.tiles_x > 0 ? P.num_sel_tiles / P.tiles_x : 0;
+  g.packets = P.tiles_x > 0 ? trace_packets(P) : 0;
+  return g;
+}
+
+// Tile (= sel, tile_step 1) of logical packet p; -1 for a padding packet of an edge block.
+// With P.tile_block the workgroup's packets form a kBlockW x kBlockH block of tiles (blocks
+// row-major over the frame) instead of a run along a tile row.
+RT_HD inline int packet_sel(const RenderParams& P, const PacketGeom& G, int p) {
+  if (!P.tile_block) return p;
+  const int w = p % kTraceWaves, b = p / kTraceWaves;
+  const int by = div_by(b, G.by_block_nbx), bx = b - by * G.block_nbx;
+  const int tx = bx * kBlockW + w % kBlockW, ty = by * kBlockH + w / kBlockW;
+  return (tx < P.tiles_x && ty < G.sel_rows) ? ty * P.tiles_x + tx : -1;
+}
+
+// Unit u = the kTraceWaves packets of logical packets u*kTraceWaves .. (a 2x2 tile block in
+// tile_block mode).  Wave w's selected tile, or -1.
+RT_HD inline int unit_sel(const RenderParams& P, const PacketGeom& G, int unit, int w) {
+  const int p = unit * kTraceWaves + w;
+  if (p >= G.packets) return -1;
+  const int sel = packet_sel(P, G, p);
+  return sel < P.num_sel_tiles ? sel : -1;
+}
+
+// Ordered dispatch: workgroup b takes entry b / regions of region b mod regions' list.
+RT_HD inline int order_slot(const RenderParams& P, const PacketGeom& G, int b) {
+  const int i = div_by(b, G.by_regions);
+  return (b - i * P.order_regions) * P.order_stride + i;
+}
+
+// Tile column and row of selected tile `sel` (deal_block_tile's, or tile % and / tiles_x).
+RT_HD inline void sel_tile(const RenderParams& P, const PacketGeom& G, int sel, int& tx,
+                          int& ty) {
+  if (P.block_deal) {  // selected block sel / 4, its tile sel % 4
+    const int d = P.tile_begin + (sel >> 2) * P.tile_step, w = sel & 3;
+    const int nbx = deal_blocks_x(P.tiles_x), by = div_by(d, G.by_deal_nbx);
+    int bx = d - by * nbx + (by - div_by(by, G.by_deal_nbx) * nbx);
+    if (bx >= nbx) bx -= nbx;
+    tx = 2 * bx + (w & 1);
+    ty = 2 * by + (w >> 1);
+  } else {
+    const int tile = P.tile_begin + sel * P.tile_step;
+    ty = div_by(tile, G.by_tiles_x);
+    tx = tile - ty * P.tiles_x;
+  }
+}
 
 // Ray queries (rt_trace_rays_device / rt_occluded_device): one launch over rays
 // [0, n) of `rays` (rt_ray, two 16-B words each).  Wave w traces rays perm[64 w .. 64 w + 63]

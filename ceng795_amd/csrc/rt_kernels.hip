@@ -50,6 +50,7 @@ struct Diag {  // per-wave traversal work (RT_DIAG builds)
   unsigned long long carry[3] = {};  // mid-walk flushes that carried 0 / 1-16 / 48-63 entries
   unsigned long long defer[kDeferEvents] = {};  // the deferred guard's kDf* counts
   unsigned long long oct_packets = 0, oct_walks = 0;  // octant_walks: loops entered, sub-walks
+  unsigned long long cyc_setup = 0, cyc_walk = 0, cyc_tail = 0;  // outside / inside the walks
 };
 #ifdef RT_DIAG
 // [0, kPhaseEvents): primary events, [kPhaseEvents, 2 kPhaseEvents): shadow events, then the
@@ -67,12 +68,7 @@ __device__ __forceinline__ unsigned long long clock_now() {
 // its slowest wave ends, so the finished waves of a 4-wave workgroup hold slots a new workgroup
 // cannot use; with two, half as much sits idle behind a heavy packet (C3: frame 0.335 -> 0.327
 // ms with six in flight, a 1/8 band 0.047 -> 0.045 ms; profiles/r06/ab_trace_waves.json).
-// (A/B builds: 1, 2 or 4.)
-#ifndef RT_TRACE_WAVES
-#define RT_TRACE_WAVES 2
-#endif
-constexpr int kTraceWaves = RT_TRACE_WAVES;
-static_assert(kTraceWaves == 1 || kTraceWaves == 2 || kTraceWaves == 4, "1, 2 or 4 waves");
+// (A/B builds: RT_TRACE_WAVES 1, 2 or 4; kTraceWaves is rt_internal.h's.)
 // A split tile's quadrants take kSplitEntries workgroups of kTraceWaves waves.
 constexpr int kQuadrants = 4, kSplitEntries = kQuadrants / kTraceWaves;
 
@@ -510,6 +506,7 @@ struct WaveLeafLds {
   unsigned long long sv[kSurvivorCap];  // t bits << 32 | queue entry (see kSurvivorCap)
   int sub;  // the wave's quadrant of a split tile, -1: whole packet (trace_frame_kernel)
   unsigned start;  // the packet's start time, low word (trace_frame_kernel; the struct's padding)
+  int tx, ty;  // the packet's tile column and row (sel_tile), worked out once (trace_frame_kernel)
 };
 // 28 waves per CU = 14 two-wave workgroups.  The frame kernel's workgroup holds
 // two of these and 8 B more, and must stay within 11,520 B: 14 of them fit the CU's 160 KiB
@@ -1210,12 +1207,23 @@ __device__ __forceinline__ int pixel_lane(int lane, int sub) {
   return lane < 16 ? ((sub >> 1) * 4 + (lane >> 2)) * kTile + (sub & 1) * 4 + (lane & 3) : -1;
 }
 
-__device__ __forceinline__ PacketPixel packet_pixel(const RenderParams& P, int sel, int sub = -1,
-                                                   int lane = lane_id()) {
+// The pixel of wave lane `lane` in the packet of tile (tx, ty).
+__device__ __forceinline__ PacketPixel tile_pixel(const RenderParams& P, int tx, int ty, int sub,
+                                                 int lane) {
   PacketPixel q;
   const int pl = pixel_lane(lane, sub);
   q.own = pl >= 0;
   q.lane = q.own ? pl : 0;
+  q.px = tx * kTile + (q.lane & 7);
+  const int lr = ty * kTile + (q.lane >> 3);  // logical row
+  q.valid = q.own && q.px < P.width && lr < P.rows;
+  q.py = P.row0 + lr * P.row_stride;
+  return q;
+}
+
+// (the recursive kernel: a packet per selected tile, its tile divided out in place)
+__device__ __forceinline__ PacketPixel packet_pixel(const RenderParams& P, int sel, int sub = -1,
+                                                   int lane = lane_id()) {
   int tx, ty;
   if (P.block_deal) {  // selected block sel / 4, its tile sel % 4
     deal_block_tile(P.tiles_x, P.tile_begin + (sel >> 2) * P.tile_step, sel & 3, tx, ty);
@@ -1224,16 +1232,19 @@ __device__ __forceinline__ PacketPixel packet_pixel(const RenderParams& P, int s
     tx = tile % P.tiles_x;
     ty = tile / P.tiles_x;
   }
-  q.px = tx * kTile + (q.lane & 7);
-  const int lr = ty * kTile + (q.lane >> 3);  // logical row
-  q.valid = q.own && q.px < P.width && lr < P.rows;
-  q.py = P.row0 + lr * P.row_stride;
-  return q;
+  return tile_pixel(P, tx, ty, sub, lane);
 }
 
 // This wave's quadrant (-1: the whole packet), kept in the wave's LDS block instead of a
 // register across the traversals.
 __device__ __forceinline__ int wave_sub(const WaveLeafLds& L) { return uniform(L.sub); }
+
+// The frame kernel's packet: its tile was worked out once, when the wave took it, and waits in
+// the wave's LDS block like the quadrant (every lane reads the same word: a broadcast).
+__device__ __forceinline__ PacketPixel wave_pixel(const RenderParams& P, const WaveLeafLds& L,
+                                                 int lane = lane_id()) {
+  return tile_pixel(P, L.tx, L.ty, wave_sub(L), lane);
+}
 
 // ------------------------------------------------------------------ MSAA sample positions
 // HW2/Scene.cpp:35-44: a std::default_random_engine (libstdc++ minstd_rand0, x <- 16807 x mod
@@ -1340,7 +1351,8 @@ template <bool FAST, bool DEEP, bool SPHERES>
 __device__ __forceinline__ void primary_packet(const RenderParams& P,
                                                const DevNode* __restrict__ nodes, int sel,
                                                int* spill, WaveLeafLds& L) {
-  const PacketPixel q = packet_pixel(P, sel, wave_sub(L));
+  DIAG(const unsigned long long s0 = clock_now());
+  const PacketPixel q = wave_pixel(P, L);
   LaneRay ray = make_ray(ld3(P.cam_e), primary_dir(P, q.px, q.py), P.quot_ok);
   // The camera origin is wave-uniform; left to itself the compiler keeps it in 3 SGPRs and
   // copies it to VGPRs at every node visit (a VALU op takes one SGPR operand, the box
@@ -1352,6 +1364,7 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   int leaf;
   // (CAMERA: every lane's origin is cam_e, so the leaf batch fetches no owner origin)
   constexpr bool kCam = RT_CAMERA_ORIGIN != 0;
+  DIAG(const unsigned long long s1 = clock_now());
   if constexpr (FAST && kOctantNodes != 0) {
     if (kOctantNodes == 1) octant_shifts_zero(ray);
     L.key[lane_id()] = kNoHitKey;
@@ -1372,8 +1385,9 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   } else {
     closest_hit<false, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   }
+  DIAG(const unsigned long long s2 = clock_now());
   const RenderParams& Pw = fresh_params(P);  // post-traversal fields: not live across it
-  const PacketPixel qw = packet_pixel(Pw, sel, wave_sub(L));  // (recomputed, not kept)
+  const PacketPixel qw = wave_pixel(Pw, L);  // (recomputed, not kept)
   int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
   rec.x = qw.valid ? leaf : -2;  // -1 miss, -2 outside the image
   rec.y = __float_as_int(t);
@@ -1385,6 +1399,10 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     atomicAdd(&c[kCntPrimary], nvalid);
     atomicAdd(&c[kCntHits], nhit);
 #ifdef RT_DIAG
+    const unsigned long long s3 = clock_now();  // (lane 0's, past the ray counters)
+    atomicAdd(&g_phase[kPhCycPrimSetup], s1 - s0);
+    atomicAdd(&g_phase[kPhCycPrimWalk], s2 - s1);
+    atomicAdd(&g_phase[kPhCycPrimTail], s3 - s2);
     atomicAdd(&c[kCntPrimNodes], dg.nodes);
     atomicAdd(&c[kCntPrimNodeLanes], dg.node_lanes);
     atomicAdd(&c[kCntPrimLeaves], dg.leaves);
@@ -1424,6 +1442,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       // per light: the pixel's hit record is re-read and its hit point rebuilt, so nothing but
       // the occlusion bits is live across the traversal (register pressure, not traffic: the
       // 8-B record is an L2 hit)
+      DIAG(const unsigned long long s0 = clock_now());
       const RenderParams& P = fresh_params(P0);
       const DevLight& lt = lights[li];
       // the packet's pixel indices recomputed here, not hoisted out of the light loop (where
@@ -1431,9 +1450,14 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       int sel_l = sel;
       asm volatile("" : "+s"(sel_l));
       const int lane_l = fresh_lane();
-      const PacketPixel q = packet_pixel(P, sel_l, wave_sub(L), lane_l);
+      const PacketPixel q = wave_pixel(P, L, lane_l);
       const int2_t rec = P.hits[(size_t)sel_l * (kTile * kTile) + q.lane];
       const bool hit = q.own && hit_leaf(rec) >= 0;
+      if (li == 0 && P.counters) {  // the packet's shadow rays: every light's are these lanes'
+        const unsigned long long nhit = __builtin_popcountll(ballot(hit));
+        if (lane_l == 0)
+          atomicAdd(&counter_row(P, sel_l)[kCntShadow], nhit * (unsigned long long)P.num_lights);
+      }
       const V3 pk = hit ? hit_point(P, q, hit_t(rec)) : v3(0, 0, 0);
       const V3 ld = ld3(lt.position) - pk;
       const V3 wi = normalize(ld);
@@ -1442,6 +1466,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       const float thr = dist - P.eps;
       const bool any_skip = hit && (sr.skip0 || sr.skip1 || sr.skip2);
       bool occ;
+      DIAG(const unsigned long long s1 = clock_now());
       if constexpr (FAST && kOctantNodes != 0) {
         if (kOctantNodes == 1) octant_shifts_zero(sr);
         unsigned long long clear = 0ull;
@@ -1460,23 +1485,24 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
                   ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg)
                   : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg);
       }
+      DIAG(const unsigned long long s2 = clock_now());
       bits |= (occ ? 1u : 0u) << (li - 32 * w);
+      DIAG(dg.cyc_setup += s1 - s0);
+      DIAG(dg.cyc_walk += s2 - s1);
     }
+    DIAG(const unsigned long long s3 = clock_now());
     const RenderParams& Pw = fresh_params(P0);
     int sel_w = sel;
     asm volatile("" : "+s"(sel_w));
     const int pl = pixel_lane(fresh_lane(), wave_sub(L));
     if (pl >= 0) Pw.occ[((size_t)sel_w * (kTile * kTile) + pl) * Pw.occ_words + w] = bits;
+    DIAG(dg.cyc_tail += clock_now() - s3);
   }
+#ifdef RT_DIAG
   const RenderParams& Pc = fresh_params(P0);
   if (Pc.counters) {
-    const int pl = pixel_lane(lane_id(), wave_sub(L));
-    const bool hit = pl >= 0 && hit_leaf(Pc.hits[(size_t)sel * (kTile * kTile) + pl]) >= 0;
-    const unsigned long long nhit = __builtin_popcountll(ballot(hit));
     if (lane_id() == 0) {
       unsigned long long* c = counter_row(Pc, sel);
-      atomicAdd(&c[kCntShadow], nhit * (unsigned long long)Pc.num_lights);
-#ifdef RT_DIAG
       atomicAdd(&c[kCntShadNodes], dg.nodes);
       atomicAdd(&c[kCntShadNodeLanes], dg.node_lanes);
       atomicAdd(&c[kCntShadLeaves], dg.leaves);
@@ -1491,9 +1517,12 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       for (int k = 0; k < kDeferEvents; k++) atomicAdd(&g_phase[kPhDeferShad + k], dg.defer[k]);
       atomicAdd(&g_phase[kPhOctShadPackets], dg.oct_packets);
       atomicAdd(&g_phase[kPhOctShadWalks], dg.oct_walks);
-#endif
+      atomicAdd(&g_phase[kPhCycShadSetup], dg.cyc_setup);
+      atomicAdd(&g_phase[kPhCycShadWalk], dg.cyc_walk);
+      atomicAdd(&g_phase[kPhCycShadTail], dg.cyc_tail);
     }
   }
+#endif
 }
 
 // Local shading of HW2/Scene.cpp:101-138 given the occlusion bits, in the reference's
@@ -1553,8 +1582,8 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
                                             const float* __restrict__ normals,
                                             const DevMaterial* __restrict__ mats,
                                             const DevLight* __restrict__ lights, int sel,
-                                            int sub, float* stage = nullptr) {
-  const PacketPixel q = packet_pixel(P, sel, sub);
+                                            const WaveLeafLds& L, float* stage = nullptr) {
+  const PacketPixel q = wave_pixel(P, L);  // (pair_rows: never a quadrant wave, L.sub is -1)
   const size_t pix = (size_t)sel * (kTile * kTile) + q.lane;
   const int2_t rec = P.hits[pix];
   const bool valid = q.own && hit_leaf(rec) != -2;
@@ -1603,16 +1632,14 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
 // unit, tx even) instead leave their colours in their waves' LDS; the second wave to arrive
 // writes both tiles as 8 rows of 192 B — whole 64-B lines, 16-B stores.  (Same values, same
 // pixels: only who stores them changes.)
-__device__ __forceinline__ void pair_write(const RenderParams& P, WaveLeafLds* lds, int sel,
-                                           int* arrived) {
+__device__ __forceinline__ void pair_write(const RenderParams& P, WaveLeafLds* lds, int* arrived) {
   __threadfence_block();  // this wave's staged colours before its arrival
   int first = 0;
   if (lane_id() == 0) first = atomicAdd(arrived, 1) == 0;
   if (__builtin_amdgcn_readfirstlane(first)) return;  // the partner writes both tiles
   __threadfence_block();
   const int w = (int)threadIdx.x >> 6;
-  const int tile = P.tile_begin + sel - w;  // the unit's left tile
-  const int tx0 = tile % P.tiles_x, ty = tile / P.tiles_x;
+  const int tx0 = uniform(lds[w].tx) - w, ty = uniform(lds[w].ty);  // the unit's left tile
   for (int f = lane_id(); f < 96; f += 64) {  // 8 rows x 12 float4
     const int r = f / 12, k = f % 12;
     const int lr = ty * kTile + r;
@@ -1956,24 +1983,8 @@ __device__ __forceinline__ int packet_index() {
 // its scalar cache.  With P.tile_block the workgroup's packets form a kBlockW x kBlockH block
 // of tiles (blocks row-major over the frame) instead of a run along a tile row: neighbouring
 // rays walk the same nodes, and the cache serves them once.
-constexpr int kBlockW = kTraceWaves >= 2 ? 2 : 1, kBlockH = kTraceWaves / kBlockW;
-
-// Tile (= sel, tile_step 1) of logical packet p; -1 for a padding packet of an edge block.
-__device__ __forceinline__ int packet_sel(const RenderParams& P, int p) {
-  if (!P.tile_block) return p;
-  const int w = p % kTraceWaves, b = p / kTraceWaves;
-  const int nbx = (P.tiles_x + kBlockW - 1) / kBlockW;
-  const int tx = (b % nbx) * kBlockW + w % kBlockW, ty = (b / nbx) * kBlockH + w / kBlockW;
-  const int tiles_y = P.num_sel_tiles / P.tiles_x;  // the selection's tile rows
-  return (tx < P.tiles_x && ty < tiles_y) ? ty * P.tiles_x + tx : -1;
-}
-
-// Logical packets of a traversal launch (with tile_block, padded to whole blocks).
-__host__ __device__ __forceinline__ int trace_packets(const RenderParams& P) {
-  if (!P.tile_block) return P.num_sel_tiles;
-  const int tiles_y = P.num_sel_tiles / P.tiles_x;
-  return ((P.tiles_x + kBlockW - 1) / kBlockW) * ((tiles_y + kBlockH - 1) / kBlockH) * kTraceWaves;
-}
+// (kBlockW, kBlockH, and the packet index arithmetic — packet_sel, unit_sel, order_slot,
+// sel_tile — are rt_internal.h's: the host works out their divisions, the PacketGeom argument.)
 
 // ------------------------------------------------------------------ dispatch order
 // Traversal kernels are LPT-scheduled: a packet's cost varies ~5x over a C3 frame (rays that
@@ -1983,36 +1994,24 @@ __host__ __device__ __forceinline__ int trace_packets(const RenderParams& P) {
 // longest-processing-time schedule.  Orders never change results: every tile is written by
 // exactly one wave.
 //
-// Unit u = the kTraceWaves packets of logical packets u*kTraceWaves .. (a 2x2 tile block in
-// tile_block mode).  Wave w's selected tile, or -1.
-__device__ __forceinline__ int unit_sel(const RenderParams& P, int unit, int w) {
-  const int p = unit * kTraceWaves + w;
-  if (p >= trace_packets(P)) return -1;
-  const int sel = packet_sel(P, p);
-  return sel < P.num_sel_tiles ? sel : -1;
-}
-
 // Selected tile of this wave in a traversal launch, and its quadrant (sub, -1: the whole
 // packet): ordered (block b of the grid takes entry b / regions of region b mod regions' list,
 // heaviest first: a unit, -1 = none, or -2 - (p kSplitEntries + j) = quadrants j kTraceWaves ..
 // of logical packet p's tile, wave k taking quadrant j kTraceWaves + k), else the XCD-remapped
 // block order.
-__device__ __forceinline__ int order_entry(const RenderParams& Q) {
-  const int b = (int)blockIdx.x;
-  return uniform(Q.unit_order[(b % Q.order_regions) * Q.order_stride + b / Q.order_regions]);
-}
-
-__device__ __forceinline__ int dispatch_sel(const RenderParams& Q) {
+__device__ __forceinline__ int dispatch_sel(const RenderParams& Q, const PacketGeom& G, int& sub) {
   const int w = (int)threadIdx.x >> 6;
+  sub = -1;
   if (Q.use_order) {
-    const int e = order_entry(Q);
-    if (e >= 0) return uniform(unit_sel(Q, e, w));
+    const int e = uniform(Q.unit_order[order_slot(Q, G, (int)blockIdx.x)]);
+    if (e >= 0) return uniform(unit_sel(Q, G, e, w));
     if (e == -1) return -1;
+    sub = ((-2 - e) % kSplitEntries) * kTraceWaves + w;
     const int p = (-2 - e) / kSplitEntries;  // the split tile's logical packet
-    return uniform(unit_sel(Q, p / kTraceWaves, p % kTraceWaves));
+    return uniform(unit_sel(Q, G, p / kTraceWaves, p % kTraceWaves));
   }
   const int p = packet_index<kTraceWaves>();
-  const int sel = p < trace_packets(Q) ? packet_sel(Q, p) : -1;
+  const int sel = p < G.packets ? packet_sel(Q, G, p) : -1;
   return sel < Q.num_sel_tiles ? sel : -1;
 }
 
@@ -2038,10 +2037,10 @@ __device__ __forceinline__ int cost_bucket(unsigned c) {  // 8 steps per octave
 // A unit holds its workgroup slot until its slowest packet ends, so it is ranked by its
 // most expensive tile (ranking by the sum measured 14 % worse in a replay of measured
 // per-tile times).
-__device__ __forceinline__ unsigned unit_cost(const RenderParams& P, int u) {
+__device__ __forceinline__ unsigned unit_cost(const RenderParams& P, const PacketGeom& G, int u) {
   unsigned c = 0;
   for (int w = 0; w < kTraceWaves; w++) {
-    const int sel = unit_sel(P, u, w);
+    const int sel = unit_sel(P, G, u, w);
     if (sel >= 0) c = max(c, P.tile_cost[sel]);
   }
   return c;
@@ -2075,7 +2074,7 @@ constexpr int kOrderThreads = 256;
 #endif
 constexpr int kSplitBuckets = RT_SPLIT_BUCKETS;
 constexpr int kMaxSplit = 128;  // tiles split per region at most
-__global__ __launch_bounds__(kOrderThreads) void order_kernel(RenderParams P) {
+__global__ __launch_bounds__(kOrderThreads) void order_kernel(RenderParams P, PacketGeom G) {
   __shared__ int hist[kOrderBuckets];
   __shared__ int split_info[2];  // [0] = split threshold bucket, [1] = units split
   const int tid = (int)threadIdx.x, x = (int)blockIdx.x;
@@ -2084,7 +2083,7 @@ __global__ __launch_bounds__(kOrderThreads) void order_kernel(RenderParams P) {
   for (int i = tid; i < kOrderBuckets; i += kOrderThreads) hist[i] = 0;
   __syncthreads();
   for (int i = tid; i < n; i += kOrderThreads)
-    atomicAdd(&hist[cost_bucket(unit_cost(P, region_unit(P, x, i)))], 1);
+    atomicAdd(&hist[cost_bucket(unit_cost(P, G, region_unit(P, x, i)))], 1);
   __syncthreads();
   if (tid < 64) {  // exclusive offsets, heaviest bucket first: one wave scans the 256 buckets
     const int lane = tid;
@@ -2132,13 +2131,13 @@ __global__ __launch_bounds__(kOrderThreads) void order_kernel(RenderParams P) {
   for (int i = tid; i < n; i += kOrderThreads) {
     const int u = region_unit(P, x, i);
     for (int w = 0; w < kTraceWaves; w++) {  // this frame's costs, kept for rt_tile_costs
-      const int sel = unit_sel(P, u, w);
+      const int sel = unit_sel(P, G, u, w);
       if (sel >= 0) snap[sel] = P.tile_cost[sel];
     }
-    const int r = atomicAdd(&hist[cost_bucket(unit_cost(P, u))], 1);
+    const int r = atomicAdd(&hist[cost_bucket(unit_cost(P, G, u))], 1);
     if (r < nsplit) {  // kSplitEntries entries per tile, -1 for a padding tile of an edge block
       for (int w = 0; w < kTraceWaves; w++) {
-        const int sel = unit_sel(P, u, w);
+        const int sel = unit_sel(P, G, u, w);
         for (int j = 0; j < kSplitEntries; j++)
           out[kQuadrants * r + kSplitEntries * w + j] =
               sel >= 0 ? -2 - ((kTraceWaves * u + w) * kSplitEntries + j) : -1;
@@ -2185,7 +2184,8 @@ __device__ unsigned long long g_timeline[2][kTimelineWaves][3];
 // register state of the three phases apart.  tile_cost: the whole packet's time.
 template <bool FAST, bool DEEP, bool SPHERES>
 __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_frame_kernel(
-    RenderParams P, const DevNode* __restrict__ nodes, const DevLight* __restrict__ lights) {
+    RenderParams P, const DevNode* __restrict__ nodes, const DevLight* __restrict__ lights,
+    PacketGeom G) {
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kTraceWaves];
   int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
@@ -2196,12 +2196,19 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
     __syncthreads();
   }
   TL_BEGIN;
+  DIAG(const unsigned long long cp = clock_now());
   const RenderParams& Q = fresh_params(P);
-  const int sel = dispatch_sel(Q);
+  int sub;
+  const int sel = dispatch_sel(Q, G, sub);
   TL_SEL(sel);
   if (sel >= 0) {
-    const int e = Q.use_order ? order_entry(Q) : -1;
-    L.sub = e <= -2 ? ((-2 - e) % kSplitEntries) * kTraceWaves + ((int)threadIdx.x >> 6) : -1;
+    L.sub = sub;
+    {  // the packet's tile, once: every later phase reads it back (wave_pixel)
+      int tx, ty;
+      sel_tile(Q, G, sel, tx, ty);
+      L.tx = tx;
+      L.ty = ty;
+    }
     // the packet's start time waits in the wave's LDS block (kept in SGPRs across the
     // traversals it spilled; in an array of its own, the slot's address was a VGPR held, and
     // with the carried leaf queue spilled to scratch, across them): its low word, which gives
@@ -2215,11 +2222,11 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
     DIAG(const unsigned long long c2 = clock_now());
     const RenderParams& Ps = fresh_params(P);
     if (Ps.pair_rows) {
-      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, -1,
+      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L,
                            reinterpret_cast<float*>(L.q));
-      pair_write(fresh_params(P), leaf_lds, sel, &pair_arrived);
+      pair_write(fresh_params(P), leaf_lds, &pair_arrived);
     } else {
-      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, wave_sub(L));
+      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L);
     }
 #ifdef RT_DIAG
     const unsigned long long c3 = clock_now();
@@ -2228,6 +2235,7 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
       atomicAdd(&g_phase[kPhCycShadTotal], c2 - c1);
       atomicAdd(&g_phase[kPhCycShade], c3 - c2);
       atomicAdd(&g_phase[kPhCycFrame], c3 - c0);
+      atomicAdd(&g_phase[kPhCycPrologue], c0 - cp);
       atomicAdd(&g_phase[kPhWaves], 1ull);
     }
 #endif
@@ -2303,12 +2311,12 @@ constexpr size_t deep_lds_bytes(int waves) {
 #ifndef RT_ORDER_SPLIT  // (A/B builds: 0 = no heavy-tile split)
 #define RT_ORDER_SPLIT 1
 #endif
-static bool order_geometry(RenderParams& T, int& tblocks, int& per_region) {
+static bool order_geometry(RenderParams& T, PacketGeom& G, int& tblocks, int& per_region) {
   // 2-D blocks of tiles for a selection of whole tile rows: the whole frame, or a row band
   // (dist_tiles.BandPlan: tiles tile_begin .. tile_begin + num_sel_tiles - 1)
-  T.tile_block = T.tile_step == 1 && !T.block_deal && T.tile_begin % T.tiles_x == 0 &&
-                 T.num_sel_tiles % T.tiles_x == 0;
-  tblocks = (trace_packets(T) + kTraceWaves - 1) / kTraceWaves;
+  T.tile_block = whole_tile_rows(T);
+  G = packet_geom(T);  // (order_regions is the caller's: nothing below changes a divisor)
+  tblocks = (G.packets + kTraceWaves - 1) / kTraceWaves;
   per_region = 0;
   T.use_order = 0;
   if (!(T.tile_cost != nullptr && T.unit_order != nullptr && T.order_regions > 0 &&
@@ -2338,10 +2346,11 @@ static bool order_geometry(RenderParams& T, int& tblocks, int& per_region) {
 // unit_order, without split entries.  Returns 1 if the launch is ordered (a list was made).
 int launch_cold_order(RenderParams P, hipStream_t stream) {
   int tblocks = 0, per_region = 0;
-  if (P.num_sel_tiles <= 0 || !order_geometry(P, tblocks, per_region)) return 0;
+  PacketGeom G;
+  if (P.num_sel_tiles <= 0 || !order_geometry(P, G, tblocks, per_region)) return 0;
   P.order_split = 0;
   P.order_stride = per_region;
-  hipLaunchKernelGGL(order_kernel, dim3(P.order_regions), dim3(kOrderThreads), 0, stream, P);
+  hipLaunchKernelGGL(order_kernel, dim3(P.order_regions), dim3(kOrderThreads), 0, stream, P, G);
   return hipGetLastError() == hipSuccess ? 1 : 0;
 }
 
@@ -2363,7 +2372,8 @@ static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* 
   }
   RenderParams T = P;
   int tblocks = 0, per_region = 0;
-  bool ordered = order_geometry(T, tblocks, per_region);
+  PacketGeom G;
+  bool ordered = order_geometry(T, G, tblocks, per_region);
   const size_t tlds = deep_lds_bytes<DEEP>(kTraceWaves);
   int oblocks = ordered ? T.order_regions * T.order_stride : tblocks;
   const RenderParams S = T;
@@ -2386,9 +2396,9 @@ static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* 
                 !T.tile_major && !T.records && T.tiles_x % 2 == 0 && T.width % 16 == 0 &&
                 (reinterpret_cast<uintptr_t>(T.out) & 15) == 0 ? 1 : 0;
   hipLaunchKernelGGL((trace_frame_kernel<FAST, DEEP, SPHERES>), dim3(T.use_order ? oblocks : tblocks),
-                     dim3(kTraceWaves * 64), tlds, stream, T, nodes, lights);
+                     dim3(kTraceWaves * 64), tlds, stream, T, nodes, lights, G);
   mark(marks, 1, stream);
-  if (ordered) hipLaunchKernelGGL(order_kernel, dim3(S.order_regions), dim3(kOrderThreads), 0, stream, S);
+  if (ordered) hipLaunchKernelGGL(order_kernel, dim3(S.order_regions), dim3(kOrderThreads), 0, stream, S, G);
   mark(marks, 2, stream);
   mark(marks, 3, stream);
 }

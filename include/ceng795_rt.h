@@ -201,6 +201,20 @@ int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long l
  * §3): RT_OK when ref_slots reference node slots and wide_slots culling node slots (one copy) fit,
  * else RT_E_UNSUPPORTED with the message scene creation fails with in rt_last_error(). */
 int rt_host_accel_slots_check(long long ref_slots, long long wide_slots);
+/* Host-only, for tests: the frame kernel's index arithmetic, which divides by multiplying with
+ * host-computed constants — the functions the kernel itself runs.
+ * rt_host_packet_div: quot[i] = (first + i) / divisor by that arithmetic, i < count
+ * (divisor >= 1, first + count <= 2^31).
+ * rt_host_packet_coords: for a launch of num_sel_tiles selected units (tiles tile_begin + k
+ * tile_step of a frame tiles_x tiles wide; with block_deal 2x2 blocks in deal order, four tiles
+ * each) and every logical packet p < count: out4[4p] = the selected tile wave p takes in block
+ * order (-1: none), out4[4p+1], out4[4p+2] = its tile column and row, out4[4p+3] = the order-list
+ * word workgroup p reads in an ordered launch of order_regions regions, order_stride words each.
+ * Returns the launch's logical packets, or an error. */
+int rt_host_packet_div(int divisor, int first, int count, int* quot);
+int rt_host_packet_coords(int tiles_x, int num_sel_tiles, int tile_begin, int tile_step,
+                          int block_deal, int order_regions, int order_stride, int count,
+                          int* out4);
 /* Height of the flattened BVH (levels of internal nodes). */
 int rt_scene_bvh_depth(const rt_scene* scene);
 

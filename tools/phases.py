@@ -8,7 +8,9 @@ entered), leafy / pair / inner hits, stack pushes and pops, leaf-batch flushes a
 survive their triangle test, the 64-survivor guard iterations, the guard batches that split an
 iteration's survivors and the survivors the guard rejected.  Cycles (s_memrealtime, 100 MHz, summed over waves): the whole primary / shadow / shading
 phase of each packet, and inside the traversals the node visits (of which the node load: issue
-to data), and the leaf-batch flushes.  The clock reads themselves perturb the timing (an SMEM
+to data), and the leaf-batch flushes; and `sections`: the prologue (kernel entry until the wave
+has its tile; outside `frame`), per traversal kind the set-up before the walks, the walks and the
+tail after them, and what the diagnostic atomics take of each phase total.  The clock reads themselves perturb the timing (an SMEM
 round trip each), so the cycle split is a proportion, not a kernel time.
 
 usage: CENG795_LIB=diag python tools/phases.py <scene.xml> [--frames 3]   (prints one JSON object)
@@ -91,6 +93,20 @@ def main():
     if n >= 46:  # the octant loop (rt_internal.h kPhOct*): packets with an active lane, sub-walks
         res["octant_walks"] = {"primary": dict(zip(["packets", "walks"], v[42:44])),
                                "shadow": dict(zip(["packets", "walks"], v[44:46]))}
+    if n >= 53:  # outside the walks (rt_internal.h kPhCycPrologue ..): stamped before the
+        # diagnostic atomics, which fall into no section
+        names = ["prologue", "prim_setup", "prim_walk", "prim_tail", "shad_setup", "shad_walk",
+                 "shad_tail"]
+        sec = dict(zip(names, v[46:53]))
+        waves = max(1, cyc["waves"])
+        sec["diag_atomics_prim"] = cyc["prim_total"] - sec["prim_setup"] - sec["prim_walk"] - sec["prim_tail"]
+        sec["diag_atomics_shad"] = cyc["shad_total"] - sec["shad_setup"] - sec["shad_walk"] - sec["shad_tail"]
+        # a walk's own overhead: the octant loop, entry and exit, the final flush's bracket
+        sec["prim_walk_outside_visits_flushes"] = sec["prim_walk"] - cyc["prim_visit"] - cyc["prim_flush"]
+        sec["shad_walk_outside_visits_flushes"] = sec["shad_walk"] - cyc["shad_visit"] - cyc["shad_flush"]
+        res["sections"] = {"ticks": sec,
+                           "wave_us": {k: round(x / waves / 100.0, 3) for k, x in sec.items()},
+                           "share_of_frame": {k: round(x / frame, 4) for k, x in sec.items()}}
     print(json.dumps(res))
 
 
