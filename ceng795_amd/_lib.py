@@ -28,6 +28,9 @@ RT_TRAVERSAL_REFERENCE = 1
 RT_QUERY_REORDER = 1  # flags of the ray queries
 RT_QUERY_IN_MEDIUM = 2  # radiance queries only: every ray starts inside a dielectric
 
+RT_FILM_GAUSSIAN = 0  # rt_film_create filters
+RT_FILM_BOX = 1
+
 F3 = C.c_float * 3
 
 
@@ -163,6 +166,25 @@ SIGNATURES = {
                                 C.POINTER(rt_stats)]),
     "rt_set_radiance_scratch_limit": (C.c_int, [C.c_void_p, C.c_size_t]),
     "rt_stream_frame_scratch_bytes": (C.c_longlong, [C.c_void_p, C.c_void_p]),
+    "rt_film_version": (C.c_int, []),
+    "rt_film_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                 C.POINTER(C.c_void_p)]),
+    "rt_film_destroy": (None, [C.c_void_p]),
+    "rt_film_clear_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_film_splat_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                       C.c_void_p]),
+    "rt_film_shade_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                            C.c_int, C.c_int, C.c_void_p]),
+    "rt_film_resolve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_film_clear": (C.c_int, [C.c_void_p]),
+    "rt_film_splat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]),
+    "rt_film_shade_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                     C.c_int, C.POINTER(rt_stats)]),
+    "rt_film_resolve": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_film_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_film_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "rt_film_set_stage_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_film_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 _lib = None

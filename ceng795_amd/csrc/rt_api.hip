@@ -48,6 +48,9 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const DevNode* nodes, bool fast, bool deep, bool spheres,
                            hipStream_t stream);
+hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
+hipError_t launch_film_resolve(const float* pixels, float* out, int width, int height,
+                               hipStream_t stream);
 void write_png(const std::string& path, const float* rgb, int w, int h);
 }  // namespace rt
 
@@ -90,6 +93,8 @@ struct WorkSet {
   DevBuf<float> frames;     // ray-tree frames: recursive scenes' frames and radiance queries
   DevBuf<float> samples;    // MSAA cameras: the sample passes
   DevBuf<unsigned> query;   // queries with RT_QUERY_REORDER: permutation, histogram, totals
+  DevBuf<unsigned> film;    // film splats: per-pixel offsets, scan totals, sample lists (FilmParams)
+  DevBuf<rt_radiance> film_rad;  // rt_film_shade_rays*: the colours between the query and the splat
   void reserve_tiles(const HostScene& h, size_t tiles);  // hits, occ and sched
   // Sizes the set for launch P of camera c, whose num_sel_tiles is final, and points P at it.
   void bind(const rt_scene* s, const rt_camera& c, RenderParams& P);
@@ -116,6 +121,7 @@ struct RenderCtx {
   // records, or n bytes of occlusion flags)
   DevBuf<rt_ray> d_rays;
   DevBuf<rt_ray_hit> d_ray_out;
+  DevBuf<float> d_xy;  // the host film entries: the uploaded positions; the resolved frame
 };
 
 // What the `_device` entries keep for one caller stream.  Owned through a unique_ptr, so its
@@ -2052,6 +2058,316 @@ int rt_write_png(const char* path, const float* rgb, int width, int height) {
   if (!path || !rgb) return set_error(RT_E_INVALID, "rt_write_png: NULL argument");
   return guarded([&] {
     write_png(path, rgb, width, height);
+    return RT_OK;
+  });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ films
+// A film owns its Pixels and its two sample counters; everything a call needs besides lives in
+// the working set of the stream it runs on.
+struct rt_film {
+  rt_scene* s = nullptr;
+  int width = 0, height = 0, filter = RT_FILM_GAUSSIAN;
+  float sigma = 1.0f / 3.0f;
+  DevBuf<float> pixels;                // width * height * 4
+  DevBuf<unsigned long long> counts;   // samples added, samples dropped
+  // rt_film_set_stage_timing: the events around the last timed splat's stages
+  std::mutex mu;
+  bool timing = false, timed = false;
+  Event marks[kFilmStages + 1];
+  size_t pixel_count() const { return (size_t)width * (size_t)height; }
+};
+
+namespace {
+
+Replica& film_replica(rt_film* f) { return *f->s->rep[0]; }
+
+// Argument rules of the splat entries; they need no GPU.
+void check_film_batch(const char* fn, const rt_film* f, const void* xy, const void* other,
+                      long long n) {
+  const std::string name(fn);
+  if (!f) throw std::invalid_argument(name + ": film is NULL");
+  if (n < 0) throw std::invalid_argument(name + ": n < 0");
+  if (n > kFilmMaxSamples)
+    throw std::invalid_argument(name + ": more than 2^28 samples in one call (cut the batch: the "
+                                       "cut decides the order)");
+  if (n > 0 && (!xy || !other)) throw std::invalid_argument(name + ": NULL pointer");
+  if ((uintptr_t)xy % 8 != 0 || (uintptr_t)other % 16 != 0)
+    throw std::invalid_argument(name + ": positions must be 8-byte aligned, colours and rays "
+                                       "16-byte aligned");
+}
+
+void film_clear_on(rt_film* f, hipStream_t stream) {
+  hip_check(hipMemsetAsync(f->pixels.p, 0, f->pixel_count() * 4 * sizeof(float), stream),
+            "clear film");
+  hip_check(hipMemsetAsync(f->counts.p, 0, 2 * sizeof(unsigned long long), stream),
+            "clear film counters");
+}
+
+// One splat of n > 0 samples on `stream` with its working set; rays: the fused entry's (their
+// validity joins the samples'), or null.
+void film_splat_on(rt_film* f, const float* xy, const rt_radiance* rad, const rt_ray* rays,
+                   long long n, WorkSet& ws, hipStream_t stream) {
+  const size_t pixels = f->pixel_count();
+  ws.film.reserve(film_scratch_words(pixels, n), "alloc film scratch");
+  FilmParams F;
+  std::memset(&F, 0, sizeof F);
+  F.pixels = f->pixels.p;
+  F.counts = f->counts.p;
+  F.xy = xy;
+  F.rad = rad;
+  F.rays = rays;
+  F.n = n;
+  F.width = f->width;
+  F.height = f->height;
+  F.filter = f->filter == RT_FILM_BOX ? kFilmBox : kFilmGaussian;
+  F.sigma = f->sigma;
+  F.offs = ws.film.p;
+  F.sums = F.offs + pixels;
+  F.list = F.sums + film_scan_words(pixels);
+  F.longs = F.list + (size_t)n;
+  std::lock_guard<std::mutex> lk(f->mu);
+  const hipEvent_t* marks = nullptr;
+  hipEvent_t ev[kFilmStages + 1];
+  if (f->timing) {
+    for (int k = 0; k <= kFilmStages; k++) {
+      f->marks[k].create();
+      ev[k] = f->marks[k];
+    }
+    marks = ev;
+    f->timed = true;
+  }
+  hip_check(launch_film_splat(F, marks, stream), "film splat launch");
+}
+
+// The fused entry's two halves on `stream`: the radiance query into ws.film_rad, then the splat.
+void film_shade_on(rt_film* f, const rt_ray* rays, const float* xy, long long n, int depth,
+                   int flags, WorkSet& ws, unsigned long long* counters, hipStream_t stream) {
+  ws.film_rad.reserve((size_t)n, "alloc film radiance");
+  enqueue_radiance(f->s, film_replica(f), QueryCall{rays, n, ws.film_rad.p, depth, flags}, ws,
+                   counters, stream);
+  film_splat_on(f, xy, ws.film_rad.p, rays, n, ws, stream);
+}
+
+constexpr int kFilmShadeFlags = RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM;
+
+// A `_device` entry's body on the caller's stream, with that stream's working set.
+template <typename Body>
+int film_device_call(rt_film* f, void* stream, Body&& body) {
+  Replica& r = film_replica(f);
+  DeviceGuard g(r.device);
+  std::unique_lock<std::mutex> lk;
+  StreamScratch* sc = scratch_for(f->s, r, stream, lk);
+  body(sc->work, (hipStream_t)stream);
+  hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_film_version(void) { return 1; }
+
+int rt_film_create(rt_scene* s, int width, int height, int filter, float sigma, rt_film** out) {
+  if (out) *out = nullptr;
+  return guarded([&] {
+    if (!s || !out) throw std::invalid_argument("rt_film_create: NULL argument");
+    if (width < 1 || width > kFilmMaxSide || height < 1 || height > kFilmMaxSide)
+      throw std::invalid_argument("rt_film_create: width and height must be in [1, 32768]");
+    if (filter != RT_FILM_GAUSSIAN && filter != RT_FILM_BOX)
+      throw std::invalid_argument("rt_film_create: unknown filter");
+    if (!std::isfinite(sigma) || sigma < 0.0f)
+      throw std::invalid_argument("rt_film_create: sigma must be finite and >= 0");
+    if (s->multi)
+      throw std::domain_error("rt_film_create: films on multi-device scenes are not supported");
+    auto f = std::make_unique<rt_film>();
+    f->s = s;
+    f->width = width;
+    f->height = height;
+    f->filter = filter;
+    f->sigma = sigma == 0.0f ? 1.0f / 3.0f : sigma;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    f->pixels.reserve(f->pixel_count() * 4, "alloc film");
+    f->counts.reserve(2, "alloc film counters");
+    hip_check(hipMemset(f->pixels.p, 0, f->pixel_count() * 4 * sizeof(float)), "clear film");
+    hip_check(hipMemset(f->counts.p, 0, 2 * sizeof(unsigned long long)), "clear film counters");
+    *out = f.release();
+    return RT_OK;
+  });
+}
+
+void rt_film_destroy(rt_film* f) {
+  if (!f) return;
+  DeviceGuard g(film_replica(f).device, std::nothrow);
+  (void)hipDeviceSynchronize();  // no call on it is still running
+  delete f;
+}
+
+int rt_film_clear_device(rt_film* f, void* stream) {
+  return guarded([&] {
+    if (!f) throw std::invalid_argument("rt_film_clear_device: film is NULL");
+    DeviceGuard g(film_replica(f).device);
+    film_clear_on(f, (hipStream_t)stream);
+    return RT_OK;
+  });
+}
+
+int rt_film_splat_device(rt_film* f, const float* d_xy, const rt_radiance* d_rad, long long n,
+                         void* stream) {
+  return guarded([&]() -> int {
+    check_film_batch("rt_film_splat_device", f, d_xy, d_rad, n);
+    if (n == 0) return RT_OK;
+    return film_device_call(f, stream, [&](WorkSet& ws, hipStream_t st) {
+      film_splat_on(f, d_xy, d_rad, nullptr, n, ws, st);
+    });
+  });
+}
+
+int rt_film_shade_rays_device(rt_film* f, const rt_ray* d_rays, const float* d_xy, long long n,
+                              int depth, int flags, void* stream) {
+  return guarded([&]() -> int {
+    const char* fn = "rt_film_shade_rays_device";
+    check_film_batch(fn, f, d_xy, d_rays, n);
+    if (flags & ~kFilmShadeFlags) throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
+    depth = radiance_depth(fn, f->s, depth);
+    if (n == 0) return RT_OK;
+    return film_device_call(f, stream, [&](WorkSet& ws, hipStream_t st) {
+      film_shade_on(f, d_rays, d_xy, n, depth, flags, ws, film_replica(f).d_counters.p, st);
+    });
+  });
+}
+
+int rt_film_resolve_device(rt_film* f, float* d_rgb, void* stream) {
+  return guarded([&] {
+    if (!f || !d_rgb) throw std::invalid_argument("rt_film_resolve_device: NULL argument");
+    DeviceGuard g(film_replica(f).device);
+    hip_check(launch_film_resolve(f->pixels.p, d_rgb, f->width, f->height, (hipStream_t)stream),
+              "film resolve launch");
+    return RT_OK;
+  });
+}
+
+int rt_film_clear(rt_film* f) {
+  return guarded([&] {
+    if (!f) throw std::invalid_argument("rt_film_clear: film is NULL");
+    DeviceGuard g(film_replica(f).device);
+    CtxLease lease(f->s, 1);
+    film_clear_on(f, lease.x[0]->stream);
+    hip_check(hipStreamSynchronize(lease.x[0]->stream), "synchronize film clear");
+    return RT_OK;
+  });
+}
+
+int rt_film_splat(rt_film* f, const float* xy, const rt_radiance* rad, long long n) {
+  return guarded([&] {
+    check_film_batch("rt_film_splat", f, xy, rad, n);
+    if (n == 0) return RT_OK;
+    DeviceGuard g(film_replica(f).device);
+    CtxLease lease(f->s, 1);
+    RenderCtx* x = lease.x[0];
+    x->d_xy.reserve(2 * (size_t)n, "alloc positions");
+    x->d_ray_out.reserve(((size_t)n + 1) / 2, "alloc colours");
+    rt_radiance* d_rad = reinterpret_cast<rt_radiance*>(x->d_ray_out.p);
+    hip_check(hipMemcpyAsync(x->d_xy.p, xy, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+                             x->stream), "upload positions");
+    hip_check(hipMemcpyAsync(d_rad, rad, (size_t)n * sizeof(rt_radiance), hipMemcpyHostToDevice,
+                             x->stream), "upload colours");
+    film_splat_on(f, x->d_xy.p, d_rad, nullptr, n, x->work, x->stream);
+    hip_check(hipStreamSynchronize(x->stream), "synchronize film splat");
+    return RT_OK;
+  });
+}
+
+int rt_film_shade_rays(rt_film* f, const rt_ray* rays, const float* xy, long long n, int depth,
+                       int flags, rt_stats* stats) {
+  return guarded([&] {
+    const char* fn = "rt_film_shade_rays";
+    check_film_batch(fn, f, xy, rays, n);
+    if (flags & ~kFilmShadeFlags) throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
+    depth = radiance_depth(fn, f->s, depth);
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RT_OK;
+    DeviceGuard g(film_replica(f).device);
+    CtxLease lease(f->s, 1);
+    RenderCtx* x = lease.x[0];
+    x->d_rays.reserve((size_t)n, "alloc rays");
+    x->d_xy.reserve(2 * (size_t)n, "alloc positions");
+    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
+                             x->stream), "upload rays");
+    hip_check(hipMemcpyAsync(x->d_xy.p, xy, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+                             x->stream), "upload positions");
+    CallCounters counted(f->s, lease.x);
+    film_shade_on(f, x->d_rays.p, x->d_xy.p, n, depth, flags, x->work, x->d_cnt.p, x->stream);
+    counted.stop();
+    counted.read(stats);
+    return RT_OK;
+  });
+}
+
+int rt_film_resolve(rt_film* f, float* rgb) {
+  return guarded([&] {
+    if (!f || !rgb) throw std::invalid_argument("rt_film_resolve: NULL argument");
+    DeviceGuard g(film_replica(f).device);
+    CtxLease lease(f->s, 1);
+    RenderCtx* x = lease.x[0];
+    const size_t floats = f->pixel_count() * 3;
+    x->d_xy.reserve(floats, "alloc resolved frame");
+    hip_check(launch_film_resolve(f->pixels.p, x->d_xy.p, f->width, f->height, x->stream),
+              "film resolve launch");
+    hip_check(hipMemcpyAsync(rgb, x->d_xy.p, floats * sizeof(float), hipMemcpyDeviceToHost,
+                             x->stream), "download frame");
+    hip_check(hipStreamSynchronize(x->stream), "synchronize film resolve");
+    return RT_OK;
+  });
+}
+
+int rt_film_read(rt_film* f, float* color_weight4) {
+  return guarded([&] {
+    if (!f || !color_weight4) throw std::invalid_argument("rt_film_read: NULL argument");
+    DeviceGuard g(film_replica(f).device);
+    hip_check(hipDeviceSynchronize(), "synchronize device");
+    hip_check(hipMemcpy(color_weight4, f->pixels.p, f->pixel_count() * 4 * sizeof(float),
+                        hipMemcpyDeviceToHost), "read film");
+    return RT_OK;
+  });
+}
+
+int rt_film_counts(rt_film* f, long long out2[2]) {
+  return guarded([&] {
+    if (!f || !out2) throw std::invalid_argument("rt_film_counts: NULL argument");
+    DeviceGuard g(film_replica(f).device);
+    hip_check(hipDeviceSynchronize(), "synchronize device");
+    unsigned long long c[2];
+    hip_check(hipMemcpy(c, f->counts.p, sizeof c, hipMemcpyDeviceToHost), "read film counters");
+    out2[0] = (long long)c[0];
+    out2[1] = (long long)c[1];
+    return RT_OK;
+  });
+}
+
+int rt_film_set_stage_timing(rt_film* f, int enable) {
+  if (!f) return set_error(RT_E_INVALID, "rt_film_set_stage_timing: film is NULL");
+  std::lock_guard<std::mutex> lk(f->mu);
+  f->timing = enable != 0;
+  return RT_OK;
+}
+
+int rt_film_stage_times(rt_film* f, double ms5[5]) {
+  return guarded([&] {
+    if (!f || !ms5) throw std::invalid_argument("rt_film_stage_times: NULL argument");
+    std::lock_guard<std::mutex> lk(f->mu);
+    if (!f->timed) throw std::invalid_argument("rt_film_stage_times: no splat was timed");
+    DeviceGuard g(film_replica(f).device);
+    hip_check(hipEventSynchronize(f->marks[kFilmStages]), "synchronize film stages");
+    for (int k = 0; k < kFilmStages; k++) {
+      float ms = 0;
+      hip_check(hipEventElapsedTime(&ms, f->marks[k], f->marks[k + 1]), "elapsed");
+      ms5[k] = ms;
+    }
     return RT_OK;
   });
 }

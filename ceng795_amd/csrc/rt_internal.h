@@ -542,6 +542,57 @@ constexpr size_t radiance_frame_bytes(int depth) {
   return sizeof(float) * kRadianceFrameFloats * (size_t)(depth + 1);
 }
 
+#if defined(__HIPCC__)
+// The reference's splat weight (HW2/Scene.cpp:12-14): double exp of a float argument, double
+// division, narrowed.  One definition for the MSAA resolve (rt_kernels.hip) and the films
+// (film_kernels.hip); both files compile with contraction off.
+__device__ __forceinline__ float gaussian_filter(float x, float y, float sigma) {
+  return (float)(exp((double)(-(x * x + y * y) / (2 * sigma * sigma))) /
+                 (2 * M_PI * (double)sigma));
+}
+#endif
+
+// Films (rt_film_*): one splat call over samples [0, n).  A sample is a film
+// position xy[i] and the rgb of rad[i]; its source pixel is (floor x, floor y), and it is valid
+// iff 0 <= x < width and 0 <= y < height (and, in the fused entry, rays[i] is a valid query ray).
+// The call sorts the valid samples by (source pixel, index) — count per pixel, scan, scatter
+// through cursors, order every list — and then one lane per destination pixel adds the samples
+// of its 3x3 neighbourhood's lists in that order.
+constexpr long long kFilmMaxSamples = 1ll << 28;  // per call (32-bit list entries and offsets)
+constexpr int kFilmMaxSide = 32768;               // (float)width is exact, width * height < 2^31
+constexpr int kFilmScanChunk = 2048;              // counters one scan workgroup takes
+constexpr int kFilmShortList = 64;                // longer lists are sorted by a workgroup each
+enum : int { kFilmGaussian = 0, kFilmBox = 1 };
+enum : int { kFilmBin = 0, kFilmScan, kFilmScatter, kFilmOrder, kFilmGather, kFilmStages };
+struct FilmParams {
+  float* pixels;               // width * height Pixels: color[3], weight
+  unsigned long long* counts;  // samples added, samples dropped
+  const float* xy;             // n x 2
+  const void* rad;             // n rt_radiance (t ignored)
+  const void* rays;            // fused entry: n rt_ray, an invalid ray's sample is dropped; or null
+  long long n;
+  int width, height, filter;
+  float sigma;
+  // per-call scratch, film_scratch_words(width * height, n) words:
+  unsigned* offs;   // per pixel: its count, then (scan) its list's start, then (scatter) its end
+  unsigned* sums;   // the scan's chunk totals, film_scan_words(width * height)
+  unsigned* list;   // n sample indices grouped by source pixel
+  unsigned* longs;  // [0]: the number of lists longer than kFilmShortList, then their pixels
+};
+// words the scan of `bins` counters keeps beside them: one total per chunk, level by level
+constexpr size_t film_scan_words(size_t bins) {
+  size_t words = 0;
+  while (true) {
+    bins = (bins + kFilmScanChunk - 1) / kFilmScanChunk;
+    words += bins;
+    if (bins <= 1) return words;
+  }
+}
+constexpr size_t film_long_words(long long n) { return (size_t)(n / (kFilmShortList + 1)) + 2; }
+constexpr size_t film_scratch_words(size_t pixels, long long n) {
+  return pixels + film_scan_words(pixels) + (size_t)n + film_long_words(n);
+}
+
 }  // namespace rt
 
 #endif

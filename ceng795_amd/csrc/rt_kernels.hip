@@ -2407,12 +2407,7 @@ static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* 
 // gathers every contribution the reference adds to it, in the order a single-threaded
 // render_image adds them (source rows, source columns, samples x-major), so the fp32 sums of
 // Pixel::add_color are reproduced exactly; then Pixel::get_color's color / weight.
-__device__ __forceinline__ float gaussian_filter(float x, float y, float sigma) {
-  // HW2/Scene.cpp:12-14: double exp of a float argument, double division, narrowed
-  return (float)(exp((double)(-(x * x + y * y) / (2 * sigma * sigma))) /
-                 (2 * M_PI * (double)sigma));
-}
-
+// (gaussian_filter: rt_internal.h, shared with the films of film_kernels.hip.)
 __global__ __launch_bounds__(256) void msaa_resolve_kernel(MsaaResolveParams M) {
   const int ai = (int)(blockIdx.x * 16 + (threadIdx.x & 15));
   const int aj = M.row_lo + (int)(blockIdx.y * 16 + (threadIdx.x >> 4));

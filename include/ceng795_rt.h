@@ -505,6 +505,80 @@ int rt_set_radiance_scratch_limit(rt_scene* scene, size_t bytes);
  * or a stream the scene holds no scratch for).  For tests of the no-scratch rule above. */
 long long rt_stream_frame_scratch_bytes(rt_scene* scene, void* hip_stream);
 
+/* ---- Films: filtered accumulation of the caller's own samples ---------------------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_FILM / rt_film_version).  The
+ * radiance queries give a colour per ray; a film turns many such samples per pixel into an image
+ * the way Scene::render_image's MSAA branch does (HW2/Scene.cpp:51-63, Pixel::add_color /
+ * get_color), for samples the caller chose: depth of field, area lights, anti-aliasing patterns.
+ * It stays in device memory, takes batch after batch and resolves to a frame.
+ *
+ * A film is width x height Pixels (color[3], weight) on the scene's device.  A sample is a film
+ * position (x, y) in pixel units — pixel (i, j) covers [i, i+1) x [j, j+1); the reference's MSAA
+ * sample of pixel i is x = (float)i + sample_x — plus an rgb.  Its SOURCE PIXEL is
+ * (floor x, floor y).  It is VALID iff 0 <= x < width and 0 <= y < height as fp32 comparisons:
+ * -0.0f is valid and belongs to pixel 0; NaN, +-inf, x == width and -1e-30f are not.  Invalid
+ * samples are dropped and counted and disturb nothing.  (The position decides, not the pixel the
+ * caller had in mind: (float)i + sample_x is i + 1 when sample_x lies within half an ulp of i below
+ * 1 — about 3 samples in 10^5 at i ~ 1000 — and such a sample belongs to pixel i + 1.)
+ *
+ * After one splat call the film holds what a single thread would leave that started from the
+ * film's state before the call, took the call's valid samples sorted by (source row, source
+ * column, index in the batch) and ran Scene.cpp:51-62 for each: for the up to nine pixels
+ * (ai, aj) of the source pixel's 3x3 neighbourhood inside the film,
+ *     w = gaussian_filter(x - ((float)ai + 0.5f), y - ((float)aj + 0.5f), sigma)
+ * (fp32 argument, double exp, double division by 2 pi sigma, narrowed), then Pixel::add_color in
+ * fp32 without contraction: color = color + rgb * w, weight = weight + w.  So the result does not
+ * depend on how a batch is ordered across source pixels, does depend on the order within one, and
+ * two calls cut between source rows equal one call.  Calls add in sequence.
+ *   RT_FILM_GAUSSIAN  sigma 0 means 1.0f / 3.0f, the reference's; the footprint is always 3x3.
+ *   RT_FILM_BOX       w = 1 into the source pixel only (add_color(c, 1) of the NumSamples == 1
+ *                     branch); sigma is ignored.
+ * Resolve is color / weight per channel (IEEE division); a pixel with weight == 0 gives 0 0 0
+ * (Pixel::get_color, HW2/Pixel.h:20).
+ *
+ * width, height in [1, 32768]; sigma finite and >= 0; one call takes at most 2^28 samples (cutting
+ * a call by index changes the order, so the caller cuts); d_xy 8-byte aligned, d_rad / d_rays
+ * 16-byte aligned; n == 0 launches nothing.  Argument errors are RT_E_INVALID before any HIP call;
+ * multi-device scenes are RT_E_UNSUPPORTED.  Destroy films before their scene.
+ *
+ * The `_device` entries are asynchronous on `hip_stream` and use that stream's scratch (the
+ * per-call sort buffers and the fused entry's radiance buffer; rt_release_stream_scratch frees
+ * it).  Calls on ONE film must be ordered by the caller (one stream, or events); different films
+ * on different streams overlap.  The host variants are synchronous: upload, run, download. */
+#define CENG795_RT_HAS_FILM 1
+int rt_film_version(void); /* 1 */
+
+typedef struct rt_film rt_film;
+enum { RT_FILM_GAUSSIAN = 0, RT_FILM_BOX = 1 };
+int  rt_film_create(rt_scene* scene, int width, int height, int filter, float sigma /* 0: 1/3 */,
+                    rt_film** out);
+void rt_film_destroy(rt_film* film); /* NULL ok */
+int  rt_film_clear_device(rt_film* film, void* hip_stream);
+/* d_xy: n x 2 floats; d_rad: n rt_radiance records (t ignored). */
+int  rt_film_splat_device(rt_film* film, const float* d_xy, const rt_radiance* d_rad, long long n,
+                          void* hip_stream);
+/* = rt_shade_rays_device(d_rays, depth, flags) into the stream's scratch, then the splat of those
+ * colours at d_xy; the sample of an invalid ray is dropped (and counted as dropped).  Flags, depth
+ * and ray counters as rt_shade_rays_device. */
+int  rt_film_shade_rays_device(rt_film* film, const rt_ray* d_rays, const float* d_xy, long long n,
+                               int depth, int flags, void* hip_stream);
+int  rt_film_resolve_device(rt_film* film, float* d_rgb /* width*height*3 */, void* hip_stream);
+int  rt_film_clear(rt_film* film);
+int  rt_film_splat(rt_film* film, const float* xy, const rt_radiance* rad, long long n);
+int  rt_film_shade_rays(rt_film* film, const rt_ray* rays, const float* xy, long long n, int depth,
+                        int flags, rt_stats* stats /* nullable: this call's rays, kernel time */);
+int  rt_film_resolve(rt_film* film, float* rgb /* width*height*3 */);
+/* The raw Pixels, width*height*4 floats (for tests and checkpoints); waits for the device. */
+int  rt_film_read(rt_film* film, float* color_weight4);
+/* Samples added and samples dropped since create / clear; waits for the device. */
+int  rt_film_counts(rt_film* film, long long out2[2]);
+/* Per-stage HIP-event times of the film's splats (tools/film_bench.py): while enabled every splat
+ * records events around its stages; rt_film_stage_times waits for the last one and writes its
+ * times in ms (bin, scan, scatter, order, gather).  RT_E_INVALID when no splat was timed. */
+int  rt_film_set_stage_timing(rt_film* film, int enable);
+int  rt_film_stage_times(rt_film* film, double ms5[5]);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 
