@@ -9,6 +9,7 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
     hits = scene.trace_rays(origins, directions)     # closest hit of the caller's own rays
     occ = scene.occluded(origins, directions, tmax)  # is the segment blocked?
     rad = scene.shade_rays(origins, directions)      # Scene::trace_ray of the caller's own rays
+    rad = scene.shade_rays_lit(origins, directions, lights)  # ... with each ray's own light samples
     film = Film(scene, width, height)                # Pixel[w*h] on the GPU for the caller's samples
     film.shade_rays(origins, directions, xy)         # trace, shade and splat (Scene.cpp:51-62)
     image = film.resolve()                           # Pixel::get_color
@@ -16,10 +17,10 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
 Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 """
 from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, RADIANCE_DTYPE,  # noqa: F401
-                    pack_rays, host_leaf_objects)
+                    LIGHT_SAMPLE_DTYPE, pack_rays, host_leaf_objects)
 from .film import Film  # noqa: F401
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
 __all__ = ["Scene", "Film", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_FAST",
-           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "pack_rays",
+           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "LIGHT_SAMPLE_DTYPE", "pack_rays",
            "host_leaf_objects"]

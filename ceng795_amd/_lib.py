@@ -27,6 +27,8 @@ RT_TRAVERSAL_REFERENCE = 1
 
 RT_QUERY_REORDER = 1  # flags of the ray queries
 RT_QUERY_IN_MEDIUM = 2  # radiance queries only: every ray starts inside a dielectric
+RT_QUERY_LIGHTS_SHARED = 4  # the `_lit` entries only: one light list for every ray
+RT_QUERY_NO_SCENE_LIGHTS = 8  # the `_lit` entries only: the scene's own lights stay dark
 
 RT_FILM_GAUSSIAN = 0  # rt_film_create filters
 RT_FILM_BOX = 1
@@ -90,6 +92,11 @@ class rt_ray_hit(C.Structure):
 
 class rt_radiance(C.Structure):
     _fields_ = [("rgb", F3), ("t", C.c_float)]
+
+
+class rt_light_sample(C.Structure):
+    _fields_ = [("position", F3), ("pad0", C.c_float), ("intensity", F3), ("pad1", C.c_float),
+                ("normal", F3), ("pad2", C.c_float)]
 
 
 # name -> (restype, argtypes); mirrors include/ceng795_rt.h one to one
@@ -185,6 +192,15 @@ SIGNATURES = {
     "rt_film_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "rt_film_set_stage_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_film_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rt_light_samples_version": (C.c_int, []),
+    "rt_shade_rays_lit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "rt_shade_rays_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_int, C.POINTER(rt_stats)]),
+    "rt_film_shade_rays_lit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                                C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "rt_film_shade_rays_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_stats)]),
 }
 
 _lib = None

@@ -46,8 +46,8 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
                         bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream);
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
-                           const DevNode* nodes, bool fast, bool deep, bool spheres,
-                           hipStream_t stream);
+                           const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
+                           bool spheres, hipStream_t stream);
 hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
 hipError_t launch_film_resolve(const float* pixels, float* out, int width, int height,
                                hipStream_t stream);
@@ -122,6 +122,7 @@ struct RenderCtx {
   DevBuf<rt_ray> d_rays;
   DevBuf<rt_ray_hit> d_ray_out;
   DevBuf<float> d_xy;  // the host film entries: the uploaded positions; the resolved frame
+  DevBuf<rt_light_sample> d_lit;  // the host `_lit` entries: the uploaded light records
 };
 
 // What the `_device` entries keep for one caller stream.  Owned through a unique_ptr, so its
@@ -1143,12 +1144,36 @@ void check_query_args(const char* fn, const rt_scene* s, const void* rays, long 
   if (s->multi) throw std::domain_error(f + ": ray queries on multi-device scenes are not supported");
 }
 
-// One query call: n rays and their n results in device memory; a radiance query's depth.
+// The caller's light records of a `_lit` entry: n k of them, or k with RT_QUERY_LIGHTS_SHARED.
+struct LightList {
+  const rt_light_sample* lights;
+  int k;
+};
+constexpr int kLitFlags = RT_QUERY_LIGHTS_SHARED | RT_QUERY_NO_SCENE_LIGHTS;
+
+// The `_lit` entries' own argument rules; they need no GPU.
+void check_light_args(const char* fn, const LightList& l, int flags) {
+  const std::string f(fn);
+  const int most = (flags & RT_QUERY_LIGHTS_SHARED) ? kLitMaxShared : kLitMaxPerRay;
+  if (l.k < 0 || l.k > most)
+    throw std::invalid_argument(f + ": k must be in [0, 256] per ray, [0, 65535] shared");
+  if (l.k > 0 && !l.lights) throw std::invalid_argument(f + ": NULL pointer (lights)");
+  if (l.k > 0 && (uintptr_t)l.lights % 16 != 0)
+    throw std::invalid_argument(f + ": lights must be 16-byte aligned");
+}
+
+size_t light_records(const LightList& l, long long n, int flags) {
+  return (flags & RT_QUERY_LIGHTS_SHARED) ? (size_t)l.k : (size_t)n * (size_t)l.k;
+}
+
+// One query call: n rays and their n results in device memory; a radiance query's depth; a lit
+// radiance query's light records in device memory (k == 0: none).
 struct QueryCall {
   const rt_ray* rays;
   long long n;
   void* out;
   int depth, flags;
+  LightList lit{nullptr, 0};
 };
 
 // What the front ends (query_device, query_host) know of a kind of query.  `enqueue` enqueues a
@@ -1224,7 +1249,9 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
   DevBuf<float>& frames = ws.frames;
   RenderParams P = scene_params(s, r);
   P.counters = counters;
+  if (q.flags & RT_QUERY_NO_SCENE_LIGHTS) P.num_lights = 0;
   const bool reorder = (q.flags & RT_QUERY_REORDER) != 0;
+  const bool shared = (q.flags & RT_QUERY_LIGHTS_SHARED) != 0;
   const bool recurse = depth > 0 && s->needs_recursion;
   QueryParams Q = query_params(s, r);
   long long chunk = kQueryMaxLaunch;  // rays per launch
@@ -1249,6 +1276,9 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
     Q.out = static_cast<rt_radiance*>(q.out) + done;
     Q.n = part;
     Q.perm = nullptr;
+    // a ray's records follow its index in this part, whatever chunk or order it is traced in
+    const LitParams lit{q.lit.lights + (shared ? 0 : (size_t)done * (size_t)q.lit.k), q.lit.k,
+                        shared ? 1 : 0};
     if (reorder) {
       carve_reorder(Q, ws, part);
       hip_check(launch_query_sort(Q, stream), "query sort launch");
@@ -1257,8 +1287,8 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
     for (R.first = 0; R.first < part; R.first += chunk) {
       QueryParams C = Q;
       C.n = std::min(part, R.first + chunk);
-      hip_check(launch_radiance(P, C, R, r.d_nodes.p, s->mode != RT_TRAVERSAL_REFERENCE, s->deep,
-                                s->has_spheres, stream),
+      hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
+                                s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres, stream),
                 "radiance query launch");
     }
   }
@@ -1268,12 +1298,17 @@ const QueryKind kClosestHit{sizeof(rt_ray_hit), true, RT_QUERY_REORDER, false, e
 const QueryKind kOcclusion{1, false, RT_QUERY_REORDER, false, enqueue_hits<true>};
 const QueryKind kRadiance{sizeof(rt_radiance), true, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM, true,
                           enqueue_radiance};
+const QueryKind kRadianceLit{sizeof(rt_radiance), true,
+                             RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM | kLitFlags, true,
+                             enqueue_radiance};
 
 // The front end of the `_device` entries: rays and results in device memory, enqueued on the
 // caller's stream with its working set; the ray counts go to the scene's counters.
 int query_device(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ray* d_rays,
-                 long long n, int depth, void* d_out, int flags, void* stream) {
+                 long long n, int depth, void* d_out, int flags, void* stream,
+                 const LightList* lit = nullptr) {
   return guarded([&] {
+    if (lit) check_light_args(fn, *lit, flags);
     check_query_args(fn, s, d_rays, n, d_out, kind.out_aligned, flags, kind.known_flags);
     if (kind.radiance) depth = radiance_depth(fn, s, depth);
     if (n == 0) return RT_OK;
@@ -1281,18 +1316,29 @@ int query_device(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ra
     DeviceGuard g(r.device);
     std::unique_lock<std::mutex> lk;
     StreamScratch* sc = scratch_for(s, r, stream, lk);
-    kind.enqueue(s, r, QueryCall{d_rays, n, d_out, depth, flags}, sc->work, r.d_counters.p,
-                 (hipStream_t)stream);
+    QueryCall q{d_rays, n, d_out, depth, flags};
+    if (lit) q.lit = *lit;
+    kind.enqueue(s, r, q, sc->work, r.d_counters.p, (hipStream_t)stream);
     hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
     return RT_OK;
   });
 }
 
+// The host `_lit` entries' light records, uploaded on the context's stream.
+LightList upload_lights(RenderCtx* x, const LightList& l, long long n, int flags) {
+  const size_t count = light_records(l, n, flags);
+  x->d_lit.reserve(count, "alloc light records");
+  hip_check(hipMemcpyAsync(x->d_lit.p, l.lights, count * sizeof(rt_light_sample),
+                           hipMemcpyHostToDevice, x->stream), "upload light records");
+  return {x->d_lit.p, l.k};
+}
+
 // The front end of the host entries: rays up, the query on a pooled context, results down.  A
 // radiance query reports its own ray counts and kernel time in `stats` (nullable), as rt_render.
 int query_host(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ray* rays, long long n,
-               int depth, void* out, int flags, rt_stats* stats) {
+               int depth, void* out, int flags, rt_stats* stats, const LightList* lit = nullptr) {
   return guarded([&] {
+    if (lit) check_light_args(fn, *lit, flags);
     check_query_args(fn, s, rays, n, out, kind.out_aligned, flags, kind.known_flags);
     if (kind.radiance) depth = radiance_depth(fn, s, depth);
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -1306,7 +1352,8 @@ int query_host(const char* fn, const QueryKind& kind, rt_scene* s, const rt_ray*
     x->d_ray_out.reserve((out_bytes + sizeof(rt_ray_hit) - 1) / sizeof(rt_ray_hit), "alloc results");
     hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
                              x->stream), "upload rays");
-    const QueryCall q{x->d_rays.p, n, x->d_ray_out.p, depth, flags};
+    QueryCall q{x->d_rays.p, n, x->d_ray_out.p, depth, flags};
+    if (lit && lit->k > 0) q.lit = upload_lights(x, *lit, n, flags);
     std::optional<CallCounters> counted;
     if (kind.radiance) counted.emplace(s, lease.x);
     kind.enqueue(s, r, q, x->work, counted ? x->d_cnt.p : nullptr, x->stream);
@@ -1846,6 +1893,23 @@ int rt_shade_rays(rt_scene* s, const rt_ray* rays, long long n, int depth, rt_ra
   return query_host("rt_shade_rays", kRadiance, s, rays, n, depth, out, flags, stats);
 }
 
+int rt_light_samples_version(void) { return 1; }
+
+int rt_shade_rays_lit_device(rt_scene* s, const rt_ray* d_rays, long long n, int depth,
+                             const rt_light_sample* d_lights, int k, rt_radiance* d_out, int flags,
+                             void* stream) {
+  const LightList lit{d_lights, k};
+  return query_device("rt_shade_rays_lit_device", kRadianceLit, s, d_rays, n, depth, d_out, flags,
+                      stream, &lit);
+}
+
+int rt_shade_rays_lit(rt_scene* s, const rt_ray* rays, long long n, int depth,
+                      const rt_light_sample* lights, int k, rt_radiance* out, int flags,
+                      rt_stats* stats) {
+  const LightList lit{lights, k};
+  return query_host("rt_shade_rays_lit", kRadianceLit, s, rays, n, depth, out, flags, stats, &lit);
+}
+
 int rt_set_radiance_scratch_limit(rt_scene* s, size_t bytes) {
   if (!s) return set_error(RT_E_INVALID, "rt_set_radiance_scratch_limit: NULL scene");
   // one wave of rays at the scene's maximum depth must fit (scenes that can recurse)
@@ -2144,9 +2208,10 @@ void film_splat_on(rt_film* f, const float* xy, const rt_radiance* rad, const rt
 
 // The fused entry's two halves on `stream`: the radiance query into ws.film_rad, then the splat.
 void film_shade_on(rt_film* f, const rt_ray* rays, const float* xy, long long n, int depth,
-                   int flags, WorkSet& ws, unsigned long long* counters, hipStream_t stream) {
+                   int flags, WorkSet& ws, unsigned long long* counters, hipStream_t stream,
+                   const LightList& lit = {nullptr, 0}) {
   ws.film_rad.reserve((size_t)n, "alloc film radiance");
-  enqueue_radiance(f->s, film_replica(f), QueryCall{rays, n, ws.film_rad.p, depth, flags}, ws,
+  enqueue_radiance(f->s, film_replica(f), QueryCall{rays, n, ws.film_rad.p, depth, flags, lit}, ws,
                    counters, stream);
   film_splat_on(f, xy, ws.film_rad.p, rays, n, ws, stream);
 }
@@ -2163,6 +2228,53 @@ int film_device_call(rt_film* f, void* stream, Body&& body) {
   body(sc->work, (hipStream_t)stream);
   hip_check(hipEventRecord(sc->done, (hipStream_t)stream), "event record");
   return RT_OK;
+}
+
+// The fused `_device` entries: `lit` null (rt_film_shade_rays_device) or the caller's records.
+int film_shade_device(const char* fn, rt_film* f, const rt_ray* d_rays, const float* d_xy,
+                      long long n, int depth, const LightList* lit, int flags, void* stream) {
+  return guarded([&]() -> int {
+    if (lit) check_light_args(fn, *lit, flags);
+    check_film_batch(fn, f, d_xy, d_rays, n);
+    if (flags & ~(kFilmShadeFlags | (lit ? kLitFlags : 0)))
+      throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
+    depth = radiance_depth(fn, f->s, depth);
+    if (n == 0) return RT_OK;
+    return film_device_call(f, stream, [&](WorkSet& ws, hipStream_t st) {
+      film_shade_on(f, d_rays, d_xy, n, depth, flags, ws, film_replica(f).d_counters.p, st,
+                    lit ? *lit : LightList{nullptr, 0});
+    });
+  });
+}
+
+// The fused host entries, likewise.
+int film_shade_host(const char* fn, rt_film* f, const rt_ray* rays, const float* xy, long long n,
+                    int depth, const LightList* lit, int flags, rt_stats* stats) {
+  return guarded([&] {
+    if (lit) check_light_args(fn, *lit, flags);
+    check_film_batch(fn, f, xy, rays, n);
+    if (flags & ~(kFilmShadeFlags | (lit ? kLitFlags : 0)))
+      throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
+    depth = radiance_depth(fn, f->s, depth);
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return RT_OK;
+    DeviceGuard g(film_replica(f).device);
+    CtxLease lease(f->s, 1);
+    RenderCtx* x = lease.x[0];
+    x->d_rays.reserve((size_t)n, "alloc rays");
+    x->d_xy.reserve(2 * (size_t)n, "alloc positions");
+    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
+                             x->stream), "upload rays");
+    hip_check(hipMemcpyAsync(x->d_xy.p, xy, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+                             x->stream), "upload positions");
+    LightList d_lit{nullptr, 0};
+    if (lit && lit->k > 0) d_lit = upload_lights(x, *lit, n, flags);
+    CallCounters counted(f->s, lease.x);
+    film_shade_on(f, x->d_rays.p, x->d_xy.p, n, depth, flags, x->work, x->d_cnt.p, x->stream, d_lit);
+    counted.stop();
+    counted.read(stats);
+    return RT_OK;
+  });
 }
 
 }  // namespace
@@ -2229,16 +2341,16 @@ int rt_film_splat_device(rt_film* f, const float* d_xy, const rt_radiance* d_rad
 
 int rt_film_shade_rays_device(rt_film* f, const rt_ray* d_rays, const float* d_xy, long long n,
                               int depth, int flags, void* stream) {
-  return guarded([&]() -> int {
-    const char* fn = "rt_film_shade_rays_device";
-    check_film_batch(fn, f, d_xy, d_rays, n);
-    if (flags & ~kFilmShadeFlags) throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
-    depth = radiance_depth(fn, f->s, depth);
-    if (n == 0) return RT_OK;
-    return film_device_call(f, stream, [&](WorkSet& ws, hipStream_t st) {
-      film_shade_on(f, d_rays, d_xy, n, depth, flags, ws, film_replica(f).d_counters.p, st);
-    });
-  });
+  return film_shade_device("rt_film_shade_rays_device", f, d_rays, d_xy, n, depth, nullptr, flags,
+                           stream);
+}
+
+int rt_film_shade_rays_lit_device(rt_film* f, const rt_ray* d_rays, const float* d_xy, long long n,
+                                  int depth, const rt_light_sample* d_lights, int k, int flags,
+                                  void* stream) {
+  const LightList lit{d_lights, k};
+  return film_shade_device("rt_film_shade_rays_lit_device", f, d_rays, d_xy, n, depth, &lit, flags,
+                           stream);
 }
 
 int rt_film_resolve_device(rt_film* f, float* d_rgb, void* stream) {
@@ -2284,28 +2396,13 @@ int rt_film_splat(rt_film* f, const float* xy, const rt_radiance* rad, long long
 
 int rt_film_shade_rays(rt_film* f, const rt_ray* rays, const float* xy, long long n, int depth,
                        int flags, rt_stats* stats) {
-  return guarded([&] {
-    const char* fn = "rt_film_shade_rays";
-    check_film_batch(fn, f, xy, rays, n);
-    if (flags & ~kFilmShadeFlags) throw std::invalid_argument(std::string(fn) + ": unknown flag bit");
-    depth = radiance_depth(fn, f->s, depth);
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n == 0) return RT_OK;
-    DeviceGuard g(film_replica(f).device);
-    CtxLease lease(f->s, 1);
-    RenderCtx* x = lease.x[0];
-    x->d_rays.reserve((size_t)n, "alloc rays");
-    x->d_xy.reserve(2 * (size_t)n, "alloc positions");
-    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
-                             x->stream), "upload rays");
-    hip_check(hipMemcpyAsync(x->d_xy.p, xy, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice,
-                             x->stream), "upload positions");
-    CallCounters counted(f->s, lease.x);
-    film_shade_on(f, x->d_rays.p, x->d_xy.p, n, depth, flags, x->work, x->d_cnt.p, x->stream);
-    counted.stop();
-    counted.read(stats);
-    return RT_OK;
-  });
+  return film_shade_host("rt_film_shade_rays", f, rays, xy, n, depth, nullptr, flags, stats);
+}
+
+int rt_film_shade_rays_lit(rt_film* f, const rt_ray* rays, const float* xy, long long n, int depth,
+                           const rt_light_sample* lights, int k, int flags, rt_stats* stats) {
+  const LightList lit{lights, k};
+  return film_shade_host("rt_film_shade_rays_lit", f, rays, xy, n, depth, &lit, flags, stats);
 }
 
 int rt_film_resolve(rt_film* f, float* rgb) {

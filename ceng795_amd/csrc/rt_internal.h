@@ -542,6 +542,22 @@ constexpr size_t radiance_frame_bytes(int depth) {
   return sizeof(float) * kRadianceFrameFloats * (size_t)(depth + 1);
 }
 
+// The caller's light records of a lit radiance query (rt_shade_rays_lit_device; DESIGN.md
+// §4.14): ray i of the caller's batch owns records [i k, i k + k) of `lights` (rt_light_sample,
+// 48 B each); shared: every ray owns [0, k).  LitArg<LIT> is what the radiance kernel takes:
+// nothing in the instantiations without light records.
+constexpr int kLitMaxPerRay = 256;
+constexpr int kLitMaxShared = 65535;
+struct LitParams {
+  const void* lights;
+  int k;
+  int shared;
+};
+template <bool LIT>
+struct LitArg {};
+template <>
+struct LitArg<true> : LitParams {};
+
 #if defined(__HIPCC__)
 // The reference's splat weight (HW2/Scene.cpp:12-14): double exp of a float argument, double
 // division, narrowed.  One definition for the MSAA resolve (rt_kernels.hip) and the films

@@ -86,6 +86,10 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x) + (a.y * b
 __device__ __forceinline__ float length(V3 a) { return __builtin_sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
 __device__ __forceinline__ V3 normalize(V3 a) { return a / length(a); }
 __device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
+__device__ __forceinline__ bool finite3(V3 a) {  // (a NaN fails the compares)
+  return (__builtin_fabsf(a.x) < RT_INF) & (__builtin_fabsf(a.y) < RT_INF) &
+         (__builtin_fabsf(a.z) < RT_INF);
+}
 
 struct LaneRay {
   V3 o, d;
@@ -1693,13 +1697,19 @@ __device__ __forceinline__ bool refract_ray(V3 dir, V3 n, float idx, V3& out) {
 
 // Local shading of one hit (ambient + point lights with shadow rays), Scene.cpp:107-139.
 // Wave-uniform: every lane calls it; `shade` selects the lanes that shade (hit, !in_medium).
-template <bool FAST, bool DEEP, bool SPHERES>
+// LIT (rt_shade_rays_lit*): after the scene's lights, the lane's own `own_k`
+// light records at `own` (rt_light_sample: three 16-B words each).  A record whose position is
+// not finite is absent; a light no shading lane of the wave has is skipped wave-wide.  A record
+// with a non-zero normal is a sample of an emitter: both terms carry dot(-w_i, normal)
+// (HW3/src/Scene.cpp:207-218), chosen per lane behind a select.
+template <bool FAST, bool DEEP, bool SPHERES, bool LIT = false>
 __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* __restrict__ nodes,
                                           const DevPrim* __restrict__ prims,
                                           const DevMaterial* __restrict__ mats,
                                           const DevLight* __restrict__ lights, int* spill, WaveLeafLds& L,
                                           bool shade, V3 o, V3 p, V3 n, int mat, Diag& dg,
-                                          unsigned long long& shadow_rays) {
+                                          unsigned long long& shadow_rays, const f4* own = nullptr,
+                                          int own_k = 0) {
   V3 color = v3(0.0f, 0.0f, 0.0f);
   const DevMaterial& m = mats[shade ? mat : 0];
   if (shade) color = color + ld3(m.ambient) * ld3(P.ambient);
@@ -1724,6 +1734,41 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
       color = color + ((ld3(m.specular) * I) * pw) / d2;
     }
   }
+  if constexpr (LIT) {
+    for (int j = 0; j < own_k; j++) {
+      f4 a = {0.0f, 0.0f, 0.0f, 0.0f}, b = a, c = a;
+      if (shade) {
+        a = own[3 * j];
+        b = own[3 * j + 1];
+        c = own[3 * j + 2];
+      }
+      const V3 lp = v3(a.x, a.y, a.z);
+      const bool lit = shade && finite3(lp);
+      if (!ballot(lit)) continue;
+      const V3 ld = lit ? lp - p : v3(0.0f, 0.0f, 1.0f);  // (an idle lane: a harmless ray)
+      const V3 wi = normalize(ld);
+      const float dist = length(ld);
+      const LaneRay sr = make_ray(p + wi * P.eps, wi, P.quot_ok);
+      const float thr = dist - P.eps;
+      const bool sskip = ballot(lit && (sr.skip0 || sr.skip1 || sr.skip2)) != 0;
+      const bool occ = sskip ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg)
+                             : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg);
+      shadow_rays += __builtin_popcountll(ballot(lit));
+      if (lit && !occ) {
+        const V3 I = v3(b.x, b.y, b.z), en = v3(c.x, c.y, c.z);
+        const bool point = (en.x == 0.0f) & (en.y == 0.0f) & (en.z == 0.0f);
+        const float ic = dot(v3(-wi.x, -wi.y, -wi.z), en);
+        const float d2 = dist * dist;
+        const V3 kd = ld3(m.diffuse) * I, ks = ld3(m.specular) * I;
+        color = color + ((point ? kd : kd * ic) * dot(n, wi)) / d2;
+        const float cos_s = __builtin_fmaxf(dot(n, normalize(w0 + wi)), 0.0f);
+        // the same (float)pow((double), (double)), out of line: a second inlined copy costs the
+        // lean variants their fourth wave per SIMD
+        const float pw = phong_pow_f64(cos_s, m.phong_exponent);
+        color = color + ((point ? ks : ks * ic) * pw) / d2;
+      }
+    }
+  }
   return color;
 }
 
@@ -1740,7 +1785,8 @@ struct TreeCounts {
 // t_first: Hit_data::t of the lane's first ray, +inf on a miss or an inactive lane.
 // RECURSE = false (depth 0, or a scene without mirror or glass: no material can spawn a ray):
 // closest hit, local shading or the miss rule, and no frame is read or written.
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true>
+// LIT: the lane's own light records join every local shading of its tree (local_color).
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true, bool LIT = false>
 __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          const DevPrim* __restrict__ prims,
                                          const float* __restrict__ normals,
@@ -1748,7 +1794,7 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
                                          const DevLight* __restrict__ lights, int* spill,
                                          WaveLeafLds& L, float* frames, size_t stride, V3 ro, V3 rd,
                                          bool medium, int depth, bool active, float& t_first,
-                                         TreeCounts& cnt) {
+                                         TreeCounts& cnt, const f4* own = nullptr, int own_k = 0) {
   auto frame = [&](int level) {
     return FrameRef{frames + (size_t)level * kFrFields * stride, stride};
   };
@@ -1781,9 +1827,9 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
       n = pr.kind == kPrimTriangle ? ld3(normals + 4 * leaf) : normalize(p - ld3(pr.v0));
       mat = pr.material;
     }
-    const V3 local = local_color<FAST, DEEP, SPHERES>(P, nodes, prims, mats, lights, spill, L,
-                                                      hit && !medium, ray.o, p, n, mat, dg,
-                                                      n_shadow);
+    const V3 local = local_color<FAST, DEEP, SPHERES, LIT>(P, nodes, prims, mats, lights, spill, L,
+                                                           hit && !medium, ray.o, p, n, mat, dg,
+                                                           n_shadow, own, own_k);
     if constexpr (!RECURSE) {  // the one ray of the tree (a miss: Scene.cpp:96-99)
       if (hit)
         out = local;
@@ -2621,10 +2667,6 @@ struct QueryRay {
   bool valid;  // ... and a ray to trace
 };
 
-__device__ __forceinline__ bool finite3(V3 a) {  // (a NaN fails the compares)
-  return (__builtin_fabsf(a.x) < RT_INF) & (__builtin_fabsf(a.y) < RT_INF) &
-         (__builtin_fabsf(a.z) < RT_INF);
-}
 __device__ __forceinline__ bool query_ray_ok(V3 o, V3 d) {
   const bool tiny = (__builtin_fabsf(d.x) < kEps) & (__builtin_fabsf(d.y) < kEps) &
                     (__builtin_fabsf(d.z) < kEps);
@@ -2738,11 +2780,14 @@ static_assert(kFrFields == kRadianceFrameFloats, "frame size the host sizes the 
 #define RT_RADIANCE_OCCUPANCY
 #endif
 constexpr int kRadianceWaves = RT_RADIANCE_WAVES;
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE>
+// LIT (rt_shade_rays_lit_device): the ray's own light records, found by the
+// ray's index in the caller's batch (its result slot), not by its place in the chunk or in the
+// reordered order; shared records sit at index 0 for every ray.  LitArg<false> is empty.
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE, bool LIT = false>
 __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void query_radiance_kernel(
     RenderParams P, QueryParams Q, RadianceParams R, const DevNode* __restrict__ nodes,
     const DevPrim* __restrict__ prims, const float* __restrict__ normals,
-    const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights) {
+    const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights, LitArg<LIT> lit) {
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
   const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;  // in the chunk
@@ -2754,9 +2799,16 @@ __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void que
   const unsigned long long n_primary = __builtin_popcountll(ballot(q.valid));
   float t;
   TreeCounts cnt;
-  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE>(
+  const f4* own = nullptr;
+  int own_k = 0;
+  if constexpr (LIT) {
+    const long long ray = q.in && !lit.shared ? query_slot(Q, i) : 0;
+    own = reinterpret_cast<const f4*>(lit.lights) + 3 * (size_t)ray * (size_t)lit.k;
+    own_k = lit.k;
+  }
+  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE, LIT>(
       P, nodes, prims, normals, mats, lights, spill, L, RECURSE ? R.frames + slot : nullptr,
-      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt);
+      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, own, own_k);
   if (i < Q.n) {
     // Pixel::add_color(color, 1) onto a zeroed pixel; an invalid ray: (0, 0, 0, +inf)
     const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
@@ -2978,19 +3030,32 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
 // permutation, or null), at most R.lanes of them.  R.frames == nullptr picks the variant that
 // cannot recurse.
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
-                           const DevNode* nodes, bool fast, bool deep, bool spheres,
-                           hipStream_t stream) {
+                           const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
+                           bool spheres, hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
   const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
     constexpr bool F = decltype(fa)::value, D = decltype(de)::value, S = decltype(sp)::value;
     const size_t lds = deep_lds_bytes<D>(kRadianceWaves);
-    if (R.frames == nullptr)  // (no RECURSE)
-      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, false>), grid, dim3(kRadianceWaves * 64), lds,
-                         stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights);
-    else
-      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, true>), grid, dim3(kRadianceWaves * 64), lds,
-                         stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights);
+    auto launch = [&](auto re, auto li, auto arg) {
+      constexpr bool RE = decltype(re)::value, LI = decltype(li)::value;
+      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, RE, LI>), grid, dim3(kRadianceWaves * 64),
+                         lds, stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights, arg);
+    };
+    using T = std::true_type;
+    using N = std::false_type;
+    if (lit) {  // (caller light records: rt_shade_rays_lit*)
+      LitArg<true> arg;
+      static_cast<LitParams&>(arg) = *lit;
+      if (R.frames == nullptr)  // (no RECURSE)
+        launch(N{}, T{}, arg);
+      else
+        launch(T{}, T{}, arg);
+    } else if (R.frames == nullptr) {
+      launch(N{}, N{}, LitArg<false>{});
+    } else {
+      launch(T{}, N{}, LitArg<false>{});
+    }
   });
   return hipGetLastError();
 }

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .scene import RADIANCE_DTYPE, Scene, _aligned, pack_rays
+from .scene import RADIANCE_DTYPE, Scene, _aligned, pack_lights, pack_rays
 
 FILTERS = {"gaussian": _lib.RT_FILM_GAUSSIAN, "box": _lib.RT_FILM_BOX}
 STAGES = ("bin", "scan", "scatter", "order", "gather")
@@ -103,6 +103,21 @@ class Film:
                                        Scene._radiance_flags(in_medium, reorder), C.byref(st)))
         return st if stats else None
 
+    def shade_rays_lit(self, origins, directions, xy, lights, *, shared: bool = False,
+                       scene_lights: bool = True, depth: Optional[int] = None,
+                       in_medium: bool = False, reorder: bool = False, stats: bool = False):
+        """``Scene.shade_rays_lit`` of the rays (``lights``: (n, k) LIGHT_SAMPLE_DTYPE records,
+        or (k,) with ``shared``), splatted at ``xy`` without leaving the GPU."""
+        rays = pack_rays(origins, directions)
+        pos = _positions(xy, len(rays))
+        lit, k = pack_lights(lights, len(rays), shared)
+        st = _lib.rt_stats()
+        check(lib().rt_film_shade_rays_lit(
+            self._h, rays.ctypes.data, pos.ctypes.data, len(rays),
+            -1 if depth is None else int(depth), lit.ctypes.data, k,
+            Scene._lit_flags(in_medium, reorder, shared, scene_lights), C.byref(st)))
+        return st if stats else None
+
     def resolve(self) -> np.ndarray:
         """The frame: (height, width, 3) float32, ``color / weight``; 0 where no sample reached."""
         out = np.zeros((self.height, self.width, 3), np.float32)
@@ -140,6 +155,17 @@ class Film:
                                               -1 if depth is None else int(depth),
                                               Scene._radiance_flags(in_medium, reorder),
                                               C.c_void_p(stream)))
+
+    def shade_rays_lit_device(self, rays_ptr: int, xy_ptr: int, n: int, lights_ptr: int, k: int, *,
+                              shared: bool = False, scene_lights: bool = True,
+                              depth: Optional[int] = None, in_medium: bool = False,
+                              reorder: bool = False, stream: int = 0) -> None:
+        """rt_film_shade_rays_lit_device: as shade_rays_device, with the rays' n x k (shared: k)
+        rt_light_sample records in device memory at ``lights_ptr``."""
+        check(lib().rt_film_shade_rays_lit_device(
+            self._h, C.c_void_p(rays_ptr), C.c_void_p(xy_ptr), n,
+            -1 if depth is None else int(depth), C.c_void_p(lights_ptr), int(k),
+            Scene._lit_flags(in_medium, reorder, shared, scene_lights), C.c_void_p(stream)))
 
     def resolve_device(self, out_ptr: int, *, stream: int = 0) -> None:
         """rt_film_resolve_device: width*height*3 floats at ``out_ptr``."""

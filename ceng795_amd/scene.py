@@ -21,6 +21,10 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("material", np.i
                       ("leaf", np.int32), ("normal", np.float32, 3), ("pad", np.int32)])
 # rt_radiance, 16 bytes
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
+# rt_light_sample, 48 bytes: a non-finite position = no light; normal 0 0 0 = a point light
+LIGHT_SAMPLE_DTYPE = np.dtype([("position", np.float32, 3), ("pad0", np.float32),
+                               ("intensity", np.float32, 3), ("pad1", np.float32),
+                               ("normal", np.float32, 3), ("pad2", np.float32)])
 
 
 def _aligned(n: int, dtype) -> np.ndarray:
@@ -42,6 +46,22 @@ def pack_rays(origins, directions, tmax=None) -> np.ndarray:
     if tmax is not None:
         rays["tmax"] = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
     return rays
+
+
+def pack_lights(lights, n: int, shared: bool):
+    """The caller's LIGHT_SAMPLE_DTYPE records, shape (n, k) or shared (k,), as a 16-byte aligned
+    array and k."""
+    a = np.asarray(lights)
+    if a.dtype != LIGHT_SAMPLE_DTYPE:
+        raise ValueError("lights must be a LIGHT_SAMPLE_DTYPE array")
+    if shared:
+        if a.ndim != 1:
+            raise ValueError("shared lights must have shape (k,)")
+    elif a.ndim != 2 or a.shape[0] != n:
+        raise ValueError("lights must have shape (n, k), one row per ray")
+    out = _aligned(a.size, LIGHT_SAMPLE_DTYPE)
+    out[...] = a.reshape(-1)
+    return out, int(a.shape[-1])
 
 
 @dataclass
@@ -294,6 +314,43 @@ class Scene:
                                          -1 if depth is None else int(depth), C.c_void_p(out_ptr),
                                          self._radiance_flags(in_medium, reorder),
                                          C.c_void_p(stream)))
+
+    @staticmethod
+    def _lit_flags(in_medium: bool, reorder: bool, shared: bool, scene_lights: bool) -> int:
+        return (Scene._radiance_flags(in_medium, reorder) |
+                (_lib.RT_QUERY_LIGHTS_SHARED if shared else 0) |
+                (0 if scene_lights else _lib.RT_QUERY_NO_SCENE_LIGHTS))
+
+    def shade_rays_lit(self, origins, directions, lights, *, shared: bool = False,
+                       scene_lights: bool = True, depth: Optional[int] = None,
+                       in_medium: bool = False, reorder: bool = False, stats: bool = False):
+        """``shade_rays`` with each ray's own light samples (rt_shade_rays_lit): ``lights`` is a
+        LIGHT_SAMPLE_DTYPE array of shape (n, k), row i lighting ray i's whole tree after the
+        scene's point lights — or, with ``shared``, of shape (k,) for every ray.  A record with
+        a non-finite ``position`` is no light; ``normal`` 0 0 0 is a point light, any other
+        normal an emitter sample whose terms carry dot(-w_i, normal).  ``scene_lights=False``
+        leaves the scene's own lights out."""
+        rays = pack_rays(origins, directions)
+        lit, k = pack_lights(lights, len(rays), shared)
+        out = _aligned(len(rays), RADIANCE_DTYPE)
+        st = _lib.rt_stats()
+        check(lib().rt_shade_rays_lit(self._h, rays.ctypes.data, len(rays),
+                                      -1 if depth is None else int(depth), lit.ctypes.data, k,
+                                      out.ctypes.data,
+                                      self._lit_flags(in_medium, reorder, shared, scene_lights),
+                                      C.byref(st)))
+        return (out, st) if stats else out
+
+    def shade_rays_lit_device(self, rays_ptr: int, n: int, lights_ptr: int, k: int, out_ptr: int, *,
+                              shared: bool = False, scene_lights: bool = True,
+                              depth: Optional[int] = None, in_medium: bool = False,
+                              reorder: bool = False, stream: int = 0) -> None:
+        """rt_shade_rays_lit_device: n rt_ray records and their n x k (shared: k)
+        rt_light_sample records in device memory, asynchronously on HIP stream ``stream``."""
+        check(lib().rt_shade_rays_lit_device(
+            self._h, C.c_void_p(rays_ptr), n, -1 if depth is None else int(depth),
+            C.c_void_p(lights_ptr), int(k), C.c_void_p(out_ptr),
+            self._lit_flags(in_medium, reorder, shared, scene_lights), C.c_void_p(stream)))
 
     def set_radiance_scratch_limit(self, nbytes: int) -> None:
         """Bytes of ray-tree frames one chunk of a recursing radiance query may hold (0: the

@@ -579,6 +579,66 @@ int  rt_film_counts(rt_film* film, long long out2[2]);
 int  rt_film_set_stage_timing(rt_film* film, int enable);
 int  rt_film_stage_times(rt_film* film, double ms5[5]);
 
+/* ---- Light samples: radiance queries and films shaded with the caller's own lights -----------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_LIGHT_SAMPLES /
+ * rt_light_samples_version).  The scene's point lights are fixed when the scene is made; an area
+ * light is a new point on the emitter for every ray (HW3/src/Scene.cpp:177-220 draws one per
+ * shading call, shades it as a point light and applies the emitter's cosine).  The caller draws
+ * the points; these entries are rt_shade_rays* / rt_film_shade_rays* with each ray's own light
+ * records added to the light loop.
+ *
+ *   value     ray i's result is rt_shade_rays' result on a scene whose light list is L_i: the
+ *             scene's point lights in their order (none with RT_QUERY_NO_SCENE_LIGHTS), followed
+ *             by the ACTIVE records of lights[i k .. i k + k) in their order — with
+ *             RT_QUERY_LIGHTS_SHARED by those of lights[0 .. k), for every ray.  The whole ray
+ *             tree uses L_i, at every bounce.  (A deliberate departure: the reference draws a new
+ *             point on the light at every shading call; here it is one per ray tree.  A caller who
+ *             wants a fresh draw per bounce does the bounce itself and comes back in at depth - 1.)
+ *             Everything else is rt_shade_rays' contract as it stands: t, depth, the miss rule,
+ *             RT_QUERY_IN_MEDIUM, RT_QUERY_REORDER, invalid rays, independence of n / position /
+ *             neighbours, streams, scratch, chunks under the scratch limit.
+ *   active    a record is INACTIVE iff a component of `position` is not finite; it is skipped as if
+ *             absent: no shadow ray, no count.  Rays with fewer than k lights pad with a NaN
+ *             position.
+ *   point     `normal` +-0 in all three components: exactly the scene's point-light term
+ *             (HW2/Scene.cpp:113-138) in the same operation order.
+ *   emitter   any other `normal`, used as given (not normalised): ic = dot(-w_i, normal), and each
+ *             of the two contributions carries it as HW3/src/Scene.cpp:207-218 associates it,
+ *             (((kd * I) * ic) * cos) / d^2  and  (((ks * I) * ic) * pw) / d^2, in fp32 without
+ *             contraction, pw the same fp64 pow.  No clamp: a sample seen from behind its emitter
+ *             subtracts light, as in the reference.  HW3's has_diffuse / has_specular skips are
+ *             not taken over: HW2's loop has none, and its shadow-ray count is the one counted.
+ *   counters  one shadow ray per shading lane and active light of L_i; the rest as rt_shade_rays*.
+ *   k         0 .. 256 per ray, 0 .. 65535 shared.  k == 0 ignores `lights` and, without the two
+ *             flags below, is rt_shade_rays bit for bit.  lights: 16-byte aligned, n k records (k
+ *             shared); NULL with k > 0, a misaligned pointer or k out of range is RT_E_INVALID
+ *             before any HIP call.  Multi-device scenes: RT_E_UNSUPPORTED.
+ *
+ * rt_shade_rays*, rt_film_shade_rays*, rt_trace_rays* and rt_occluded* refuse the two new flag bits
+ * like any unknown one. */
+#define CENG795_RT_HAS_LIGHT_SAMPLES 1
+int rt_light_samples_version(void); /* 1 */
+
+typedef struct rt_light_sample {          /* 48 B */
+  float position[3];  float pad0;
+  float intensity[3]; float pad1;
+  float normal[3];    float pad2;          /* 0 0 0: a point light */
+} rt_light_sample;
+enum { RT_QUERY_LIGHTS_SHARED = 4, RT_QUERY_NO_SCENE_LIGHTS = 8 };
+
+int rt_shade_rays_lit_device(rt_scene* scene, const rt_ray* d_rays, long long n, int depth,
+                             const rt_light_sample* d_lights, int k,
+                             rt_radiance* d_out, int flags, void* hip_stream);
+int rt_shade_rays_lit(rt_scene* scene, const rt_ray* rays, long long n, int depth,
+                      const rt_light_sample* lights, int k,
+                      rt_radiance* out, int flags, rt_stats* stats);
+int rt_film_shade_rays_lit_device(rt_film* film, const rt_ray* d_rays, const float* d_xy, long long n,
+                                  int depth, const rt_light_sample* d_lights, int k,
+                                  int flags, void* hip_stream);
+int rt_film_shade_rays_lit(rt_film* film, const rt_ray* rays, const float* xy, long long n, int depth,
+                           const rt_light_sample* lights, int k, int flags, rt_stats* stats);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 

@@ -13,7 +13,13 @@ shading.  Writes profiles/ray_query.json, keyed to the sha256 of the library tha
 the frame kernel's whole work for the caller's rays), every case checked bit for bit against the
 tile-order result and the frame in the same run; writes profiles/radiance_query.json.
 
+--radiance --lights: what the caller's own light records cost (rt_shade_rays_lit_device; DESIGN.md
+§4.14).  Camera 0's rays in tile order through four cases — LIGHT_CASES below — of which the
+first three do the same work through three paths; every case checked bit for bit against the
+first; writes profiles/radiance_lights.json.  --dry-run (needs no GPU) writes the case list only.
+
 usage: ray_query_bench.py [--calls 50] [--warmup 3] [--n 708] [--out PATH] [--check] [--radiance]
+                          [--lights] [--dry-run]
 """
 from __future__ import annotations
 
@@ -72,6 +78,17 @@ def quartiles(ms):
     return {"ms_q1": float(q[0]), "ms_median": float(q[1]), "ms_q3": float(q[2])}
 
 
+# --radiance --lights: name -> (what runs, light records per ray, shared, scene lights)
+LIGHT_CASES = {
+    "a_plain": ("rt_shade_rays_device: the scene's one light", 0, False, True),
+    "b_shared": ("RT_QUERY_NO_SCENE_LIGHTS, the scene's light as one shared record", 1, True, False),
+    "c_per_ray": ("RT_QUERY_NO_SCENE_LIGHTS, the scene's light as each ray's own record, k = 1",
+                  1, False, False),
+    "d_per_ray_k4": ("RT_QUERY_NO_SCENE_LIGHTS, k = 4 per-ray records of which one is active "
+                     "(slot i % 4 of ray i), the rest NaN", 4, False, False),
+}
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--calls", type=int, default=50)
@@ -84,12 +101,23 @@ def main(argv=None) -> int:
                    help="default: profiles/ray_query.json (profiles/radiance_query.json)")
     p.add_argument("--radiance", action="store_true",
                    help="radiance queries (rt_shade_rays_device) instead of hits and occlusion")
+    p.add_argument("--lights", action="store_true",
+                   help="with --radiance: the cost of caller light records (LIGHT_CASES)")
+    p.add_argument("--dry-run", action="store_true",
+                   help="with --radiance --lights: write the case list and stop (no GPU)")
     p.add_argument("--check", action="store_true",
                    help="also compare every case's results with the row-major ones, bit for bit")
     a = p.parse_args(argv)
+    if a.lights and not a.radiance:
+        p.error("--lights goes with --radiance")
+    if a.dry_run and not a.lights:
+        p.error("--dry-run goes with --radiance --lights")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles",
+                             "radiance_lights.json" if a.lights else
                              "radiance_query.json" if a.radiance else "ray_query.json")
+    if a.lights:
+        return lights_main(a)
     if a.radiance:
         return radiance_main(a)
 
@@ -304,6 +332,108 @@ def radiance_main(a) -> int:
         json.dump(result, f, indent=1)
         f.write("\n")
     print(json.dumps(result))
+    return 0 if all(checks.values()) else 1
+
+
+def write_result(path: str, result: dict) -> None:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
+def lights_main(a) -> int:
+    """LIGHT_CASES on camera 0's rays in tile order, alternated within every round."""
+    spec = gen_scene.heightfield_scene(a.n, a.width, a.height, name="c3.png")
+    assert len(spec.lights) == 1
+    result = {"scene": f"C3: height field {a.n}, camera 0 {a.width}x{a.height}",
+              "rays": a.width * a.height, "order": "tile_8x8", "calls": a.calls,
+              "warmup": a.warmup,
+              "timing": "device events around each call; cases alternated within every round",
+              "case_list": {k: {"what": v[0], "records_per_ray": v[1], "shared": v[2],
+                                "scene_lights": v[3],
+                                "light_bytes": 48 * v[1] * (1 if v[2] else a.width * a.height)}
+                            for k, v in LIGHT_CASES.items()}}
+    if a.dry_run:
+        result["dry_run"] = True
+        write_result(a.out, result)
+        return 0
+
+    import torch
+    import ceng795_amd
+    from ceng795_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU")
+    with tempfile.TemporaryDirectory() as d:
+        xml = os.path.join(d, "c3.xml")
+        with open(xml, "w") as f:
+            f.write(spec.to_xml())
+        scene = ceng795_amd.Scene(xml, device=0)
+    cam = scene.camera(0)
+    o, dirs = primary_rays(cam)
+    n = len(dirs)
+    idx = orders(cam.width, cam.height, a.seed)["tile_8x8"]
+    r = ceng795_amd.pack_rays(o[idx], dirs[idx])
+    rays = torch.from_numpy(r.view(np.uint8).reshape(-1)).cuda()
+    pos, inten = (np.array(v, np.float32) for v in spec.lights[0])
+    lights = {}
+    for name, (_, k, shared, _) in LIGHT_CASES.items():
+        if k == 0:
+            lights[name] = torch.zeros(48, dtype=torch.uint8, device="cuda")
+            continue
+        rec = np.zeros((1 if shared else n, k), ceng795_amd.LIGHT_SAMPLE_DTYPE)
+        rec["position"] = np.nan
+        slot = np.arange(len(rec)) % k
+        rec["position"][np.arange(len(rec)), slot] = pos
+        rec["intensity"][np.arange(len(rec)), slot] = inten
+        lights[name] = torch.from_numpy(rec.view(np.uint8).reshape(-1)).cuda()
+    rad = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(name):
+        _, k, shared, scene_lights = LIGHT_CASES[name]
+        if k == 0:
+            scene.shade_rays_device(rays.data_ptr(), n, rad.data_ptr(), stream=stream)
+        else:
+            scene.shade_rays_lit_device(rays.data_ptr(), n, lights[name].data_ptr(), k,
+                                        rad.data_ptr(), shared=shared, scene_lights=scene_lights,
+                                        stream=stream)
+
+    checks, want = {}, None
+    for name in LIGHT_CASES:
+        rad.zero_()
+        run(name)
+        torch.cuda.synchronize()
+        out = rad.cpu().numpy().copy()
+        if want is None:
+            want = out
+        checks[name] = bool(np.array_equal(out, want))
+    times = {c: [] for c in LIGHT_CASES}
+    for rnd in range(a.warmup + a.calls):
+        marks = []
+        for c in LIGHT_CASES:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(c)
+            e1.record()
+            marks.append((c, e0, e1))
+        torch.cuda.synchronize()
+        if rnd >= a.warmup:
+            for c, e0, e1 in marks:
+                times[c].append(e0.elapsed_time(e1))
+    result.update({"lib_sha256": file_sha256(_lib.LIB_PATH),
+                   "device": torch.cuda.get_device_name(0), "cases": {}})
+    for name, ms in times.items():
+        q = quartiles(ms)
+        q["mrays_per_s"] = n / q["ms_median"] / 1e3
+        result["cases"][name] = q
+    c = result["cases"]
+    result["ratios"] = {f"{k}_over_a_plain": c[k]["ms_median"] / c["a_plain"]["ms_median"]
+                        for k in LIGHT_CASES if k != "a_plain"}
+    result["bit_identical_to_a_plain"] = checks
+    scene.close()
+    write_result(a.out, result)
     return 0 if all(checks.values()) else 1
 
 
