@@ -198,6 +198,39 @@ float float_down(double x) {
   return f;
 }
 
+// a + b in double with its rounding error: s = fl(a + b) and s + e = a + b exactly (Knuth's
+// TwoSum; round to nearest, no overflow).
+void two_sum(double a, double b, double& s, double& e) {
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+
+// A double <= a + b (down) or >= a + b (up), the exact sum when it is one.  A guard plane minus
+// the margin needs more than 53 bits once the margin's fixed 2^-100 is no longer absorbed
+// (coordinates below 2^-29): rounded to nearest it can land inside the box it must contain.
+double add_down(double a, double b) {
+  double s, e;
+  two_sum(a, b, s, e);
+  return e < 0.0 ? std::nextafter(s, -INFINITY) : s;
+}
+
+double add_up(double a, double b) {
+  double s, e;
+  two_sum(a, b, s, e);
+  return e > 0.0 ? std::nextafter(s, INFINITY) : s;
+}
+
+// a + b <= c + d, decided exactly: with s = fl(x + y) and s + e = x + y, two sums that round to
+// different s are ordered as those (rounding is monotone, and equal sums round alike), and two
+// that round to the same s are ordered by their errors.
+bool sum_le(double a, double b, double c, double d) {
+  double s1, e1, s2, e2;
+  two_sum(a, b, s1, e1);
+  two_sum(c, d, s2, e2);
+  return s1 != s2 ? s1 < s2 : e1 <= e2;
+}
+
 struct Slot {
   int ref;  // BNode index (inner) or ~item (treelet)
   Box box;  // exact union of the guard boxes below (a treelet's guard box)
@@ -205,19 +238,21 @@ struct Slot {
 
 // Writes one wide node's header and slot boxes: origin = the inflated union's lower corner
 // (rounded down to fp32), per-axis power-of-two scale with the largest offset <= 32768, each
-// plane rounded outward to fp16 after the margin is applied.
+// plane rounded outward to fp16 after the margin is applied.  Every step rounds outward
+// (add_down / add_up, float_down, half_dir), so the decoded box o + h 2^k contains the guard
+// boxes with the margin in exact arithmetic, which is what check_accel decides.
 void encode_node(DevNode8& W, const Slot* sl, int n, const double* margin) {
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int k = 0; k < n; k++)
     for (int a = 0; a < 3; a++) {
-      lo[a] = std::min(lo[a], (double)sl[k].box.lo[a] - margin[a]);
-      hi[a] = std::max(hi[a], (double)sl[k].box.hi[a] + margin[a]);
+      lo[a] = std::min(lo[a], add_down((double)sl[k].box.lo[a], -margin[a]));
+      hi[a] = std::max(hi[a], add_up((double)sl[k].box.hi[a], margin[a]));
     }
   W.scale = 0;
   int ka[3];
   for (int a = 0; a < 3; a++) {
     W.origin[a] = float_down(lo[a]);
-    const double ext = hi[a] - (double)W.origin[a];
+    const double ext = add_up(hi[a], -(double)W.origin[a]);
     int k = (int)std::ceil(std::log2(std::max(ext, 1e-300) / 32768.0));
     k = std::min(std::max(k, -120), 120);
     while (std::ldexp(ext, -k) > 32768.0) k++;  // (log2 rounding)
@@ -232,19 +267,27 @@ void encode_node(DevNode8& W, const Slot* sl, int n, const double* margin) {
         continue;
       }
       const double o = (double)W.origin[a];
-      const uint16_t l = half_dir(std::ldexp((double)sl[c].box.lo[a] - margin[a] - o, -ka[a]), false);
-      const uint16_t h = half_dir(std::ldexp((double)sl[c].box.hi[a] + margin[a] - o, -ka[a]), true);
+      const double pl = add_down(add_down((double)sl[c].box.lo[a], -margin[a]), -o);
+      const double ph = add_up(add_up((double)sl[c].box.hi[a], margin[a]), -o);
+      const uint16_t l = half_dir(std::ldexp(pl, -ka[a]), false);
+      const uint16_t h = half_dir(std::ldexp(ph, -ka[a]), true);
       W.box[c][a] = (uint32_t)l | ((uint32_t)h << 16);
     }
 }
 
-// The decoded box of slot c (for the invariant check).
+// The decoded box of slot c (for the invariant check) as plane offsets h 2^k from the node's
+// origin: origin + offset need not fit a double, so the check keeps the two apart (sum_le).
 void decode_slot(const DevNode8& W, int c, double* lo, double* hi) {
   for (int a = 0; a < 3; a++) {
     const int k = (int)(int8_t)(uint8_t)((W.scale >> (8 * a)) & 255);
-    lo[a] = (double)W.origin[a] + std::ldexp(half_value((uint16_t)(W.box[c][a] & 0xffff)), k);
-    hi[a] = (double)W.origin[a] + std::ldexp(half_value((uint16_t)(W.box[c][a] >> 16)), k);
+    lo[a] = std::ldexp(half_value((uint16_t)(W.box[c][a] & 0xffff)), k);
+    hi[a] = std::ldexp(half_value((uint16_t)(W.box[c][a] >> 16)), k);
   }
+}
+
+// origin + lo <= glo - margin and origin + hi >= ghi + margin, exactly.
+bool holds_with_margin(double origin, double lo, double hi, double glo, double ghi, double margin) {
+  return sum_le(origin, lo, glo, -margin) && sum_le(ghi, margin, origin, hi);
 }
 
 // SAH cost model of the wide collapse: visiting a wide node costs kNodeCost (one scalar fetch
@@ -634,7 +677,7 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
           return "leaf pair " + std::to_string(l - 1) + " is not one node's two leaves";
         if (q == 0 && pair && s.nodes[h].child[0] != ~l) return "leaf pair does not start its holder";
         for (int a = 0; a < 3; a++)  // the slot box holds the guard box with the margin
-          if (!(lo[a] <= (double)g[a] - mg[a] && hi[a] >= (double)g[a + 3] + mg[a]))
+          if (!holds_with_margin(W.origin[a], lo[a], hi[a], g[a], g[a + 3], mg[a]))
             return "slot box does not hold its guard box with the margin";
       }
     }
@@ -662,7 +705,7 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
         for (int a = 0; a < 3; a++) {
           glo[a] = ulo[ci + a];
           ghi[a] = uhi[ci + a];
-          if (!(lo[a] <= glo[a] - mg[a] && hi[a] >= ghi[a] + mg[a]))
+          if (!holds_with_margin(W.origin[a], lo[a], hi[a], glo[a], ghi[a], mg[a]))
             return "culling box does not hold the guard boxes below it with the margin";
         }
       }

@@ -322,6 +322,8 @@ void adopt_tree(const rt_scene_desc& d, HostScene& s, const std::vector<LeafSour
     dn.axis = (depth - 1) % 3;
     const float* b = kAll;
     if (c >= 0) {
+      if (c >= nn) fail("bvh child " + std::to_string(c) + " of node " + std::to_string(node) +
+                        " is past bvh_num_nodes");
       if (c != next_node) fail("bvh nodes are not numbered in DFS preorder (node " +
                                std::to_string(node) + " child " + std::to_string(c) + ")");
       next_node++;
@@ -330,6 +332,8 @@ void adopt_tree(const rt_scene_desc& d, HostScene& s, const std::vector<LeafSour
       s.depth = std::max(s.depth, depth + 1);
       st.push_back({c, 0, depth + 1});  // invalidates f
     } else {
+      if (~c >= nl) fail("bvh leaf " + std::to_string(~c) + " of node " + std::to_string(node) +
+                         " is past bvh_num_leaves");
       if (~c != next_leaf) fail("bvh leaves are not numbered in DFS order (leaf " +
                                 std::to_string(~c) + ")");
       next_leaf++;

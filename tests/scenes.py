@@ -65,12 +65,67 @@ SPLIT = {
     "taller": (lambda: G.soup_scene(13, 64, 1080), "8x135 tiles: C3's tile rows, 8 tiles across"),
 }
 
+# Scenes far from the origin and off unit scale (tests/placed.py): base x placement.  The fast
+# traversal's margins scale with the root box's largest coordinate, and
+# the reference's own absolute constants meet a resized scene on other branches.
+import placed as P  # noqa: E402
+
+PLACED_BASES = {
+    "soup": (lambda: G.soup_scene(1, 48, 48), "three cameras, four lights, spheres, a flat wall"),
+    "hf": (lambda: G.heightfield_scene(32, 48, 48), "shared edges, equal-t ties"),
+    "depth3": (lambda: G.soup_scene(4, 32, 32, depth=3, mirror=True, glass=True),
+               "mirror + dielectric recursion"),
+    "msaa": (lambda: G.soup_scene(8, 24, 24, num_samples=4), "NumSamples 4"),
+}
+PLACEMENTS = {  # name -> (scale, offset)
+    "s2m20": (2.0 ** -20, (0, 0, 0)),
+    "s2p20": (2.0 ** 20, (0, 0, 0)),
+    "s2m30": (2.0 ** -30, (0, 0, 0)),
+    # the fixed 2^-100 of the culling margin is no longer absorbed in double from here down
+    "s2m31": (2.0 ** -31, (0, 0, 0)),
+    "s2m32": (2.0 ** -32, (0, 0, 0)),
+    "s2m34": (2.0 ** -34, (0, 0, 0)),
+    "small": (3.7e-3, (0.5, -0.25, 1.0)),
+    "t4k": (1.0, (4096.0, -8192.0, 16384.0)),
+    # the margin (0.4 .. 2.7 units) exceeds most primitives: the guard tests decide
+    "t1e5": (1.0, (1e5, 3e5, -7e5)),
+    "ty1e6": (1.0, (0.0, 1e6, 0.0)),  # one axis only: margins are per axis
+    "big": (1234.5, (-9e6, 2e6, 5e6)),
+}
+POWER_OF_TWO = ("s2m20", "s2p20", "s2m30", "s2m31", "s2m32", "s2m34")
+MSAA_PLACEMENTS = ("small", "t1e5")
+# combinations left out: the reference's own frame is not finite there (NaN payloads need not
+# agree between x86 and gfx950, so a bit comparison would say nothing)
+PLACED_LEFT_OUT = {("depth3", "s2p20"), ("depth3", "big")}
+
+
+def _placed_entry(base, placement):
+    scale, offset = PLACEMENTS[placement]
+    return (lambda: P.placed(PLACED_BASES[base][0](), scale, offset),
+            f"{PLACED_BASES[base][1]}; scale {scale!r}, offset {offset!r}")
+
+
+PLACED = {f"{b}@{p}": _placed_entry(b, p)
+          for b in PLACED_BASES for p in PLACEMENTS
+          if (b != "msaa" or p in MSAA_PLACEMENTS) and (b, p) not in PLACED_LEFT_OUT}
+
+
+# the bases themselves, unplaced, as the frames a placement is compared with
+PLACED_BASE_SCENES = {f"{b}@base": PLACED_BASES[b] for b in PLACED_BASES}
+
+
+def placed_parts(name: str):
+    """(base, placement) of a PLACED name such as "soup@t1e5" ("soup@base": the base itself)."""
+    base, placement = name.split("@")
+    return base, placement
+
+
 SMALL = ["c1", "hf_small", "hf_side", "soup1", "soup2", "soup3", "single_sphere",
          "single_triangle", "graze_plane", "graze_hf"]
 
 
 def write(name: str, directory: str) -> str:
-    table = {**CATALOGUE, **RECURSIVE, **MSAA, **SPLIT}
+    table = {**CATALOGUE, **RECURSIVE, **MSAA, **SPLIT, **PLACED, **PLACED_BASE_SCENES}
     path = os.path.join(directory, f"{name}.xml")
     if not os.path.exists(path):
         text = table[name][0]().to_xml()

@@ -378,6 +378,18 @@ def test_prebuilt_tree_is_validated(scene_dir, tmp_path):
     bad[k] += 1
     refused(bad, boxes, objs, "preorder")
     refused(children[:-2], boxes[:-6], objs, "internal nodes")
+    # an inner child that continues the preorder numbering past bvh_num_nodes, and a leaf index
+    # past bvh_num_leaves: refused before the walk reads or writes past the node arrays
+    three = desc_xml.Desc(xml)
+    three.d.num_meshes = 1
+    three.arrays["mesh_face_count"][0] = 3
+    chain_boxes = list(boxes[:12])
+    three.set_tree([1, -1, 2, -2], chain_boxes, [0, 1, 2])
+    rc = L.rt_host_dump_bvh_desc(C.byref(three.d), str(tmp_path / "bad.txt").encode())
+    assert rc == _lib.RT_E_INVALID and "past bvh_num_nodes" in L.rt_last_error().decode()
+    three.set_tree([1, -4, -1, -2], chain_boxes, [0, 1, 2])  # (valid: [1, -3, -1, -2])
+    rc = L.rt_host_dump_bvh_desc(C.byref(three.d), str(tmp_path / "bad.txt").encode())
+    assert rc == _lib.RT_E_INVALID and "past bvh_num_leaves" in L.rt_last_error().decode()
 
 
 def test_bench_efficiency_check_names_every_prediction_above_one():

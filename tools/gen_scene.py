@@ -24,6 +24,7 @@ from __future__ import annotations
 import argparse
 import math
 import random
+import struct
 import sys
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -31,13 +32,17 @@ from typing import List, Optional, Sequence, Tuple
 Vec = Tuple[float, float, float]
 
 
-def _v(v: Sequence[float]) -> str:
-    return " ".join(_num(x) for x in v)
+def _v(v: Sequence[float], fmt: Optional[str] = None) -> str:
+    return " ".join(_num(x, fmt) for x in v)
 
 
-def _num(x) -> str:
+def _num(x, fmt: Optional[str] = None) -> str:
+    """fmt None: the shortest text of the double.  Otherwise fmt (a %-format such as "%.9g") of
+    the value rounded to fp32, the precision the loaders keep."""
     if isinstance(x, int):
         return str(x)
+    if fmt is not None:
+        return fmt % struct.unpack("f", struct.pack("f", float(x)))[0]
     s = repr(float(x))
     return s[:-2] if s.endswith(".0") else s
 
@@ -79,23 +84,32 @@ class SceneSpec:
     background: Optional[Vec] = (0, 0, 0)
     shadow_eps: Optional[float] = 1e-3
     max_depth: Optional[int] = 0
+    # None: numbers as their shortest double text (every catalogue scene); "%.9g": as fp32
+    # values, for scenes whose coordinates a fixed number of decimals would erase
+    number_format: Optional[str] = None
 
     def to_xml(self) -> str:
+        def vec(v):
+            return _v(v, self.number_format)
+
+        def num(x):
+            return _num(x, self.number_format)
+
         out = ["<Scene>"]
         if self.background is not None:
-            out.append(f"  <BackgroundColor>{_v(self.background)}</BackgroundColor>")
+            out.append(f"  <BackgroundColor>{vec(self.background)}</BackgroundColor>")
         if self.shadow_eps is not None:
-            out.append(f"  <ShadowRayEpsilon>{_num(self.shadow_eps)}</ShadowRayEpsilon>")
+            out.append(f"  <ShadowRayEpsilon>{num(self.shadow_eps)}</ShadowRayEpsilon>")
         if self.max_depth is not None:
             out.append(f"  <MaxRecursionDepth>{self.max_depth}</MaxRecursionDepth>")
         out.append("  <Cameras>")
         for i, c in enumerate(self.cameras):
             out.append(f'    <Camera id="{i + 1}">')
-            out.append(f"      <Position>{_v(c.position)}</Position>")
-            out.append(f"      <Gaze>{_v(c.gaze)}</Gaze>")
-            out.append(f"      <Up>{_v(c.up)}</Up>")
-            out.append(f"      <NearPlane>{_v(c.near_plane)}</NearPlane>")
-            out.append(f"      <NearDistance>{_num(c.near_distance)}</NearDistance>")
+            out.append(f"      <Position>{vec(c.position)}</Position>")
+            out.append(f"      <Gaze>{vec(c.gaze)}</Gaze>")
+            out.append(f"      <Up>{vec(c.up)}</Up>")
+            out.append(f"      <NearPlane>{vec(c.near_plane)}</NearPlane>")
+            out.append(f"      <NearDistance>{num(c.near_distance)}</NearDistance>")
             out.append(f"      <ImageResolution>{c.width} {c.height}</ImageResolution>")
             if c.num_samples is not None:
                 out.append(f"      <NumSamples>{c.num_samples}</NumSamples>")
@@ -103,27 +117,27 @@ class SceneSpec:
             out.append("    </Camera>")
         out.append("  </Cameras>")
         out.append("  <Lights>")
-        out.append(f"    <AmbientLight>{_v(self.ambient)}</AmbientLight>")
+        out.append(f"    <AmbientLight>{vec(self.ambient)}</AmbientLight>")
         for i, (p, inten) in enumerate(self.lights):
             out.append(f'    <PointLight id="{i + 1}">')
-            out.append(f"      <Position>{_v(p)}</Position>")
-            out.append(f"      <Intensity>{_v(inten)}</Intensity>")
+            out.append(f"      <Position>{vec(p)}</Position>")
+            out.append(f"      <Intensity>{vec(inten)}</Intensity>")
             out.append("    </PointLight>")
         out.append("  </Lights>")
         out.append("  <Materials>")
         for i, m in enumerate(self.materials):
             out.append(f'    <Material id="{i + 1}">')
-            out.append(f"      <AmbientReflectance>{_v(m.ambient)}</AmbientReflectance>")
-            out.append(f"      <DiffuseReflectance>{_v(m.diffuse)}</DiffuseReflectance>")
-            out.append(f"      <SpecularReflectance>{_v(m.specular)}</SpecularReflectance>")
+            out.append(f"      <AmbientReflectance>{vec(m.ambient)}</AmbientReflectance>")
+            out.append(f"      <DiffuseReflectance>{vec(m.diffuse)}</DiffuseReflectance>")
+            out.append(f"      <SpecularReflectance>{vec(m.specular)}</SpecularReflectance>")
             if m.mirror is not None:
-                out.append(f"      <MirrorReflectance>{_v(m.mirror)}</MirrorReflectance>")
+                out.append(f"      <MirrorReflectance>{vec(m.mirror)}</MirrorReflectance>")
             if m.phong is not None:
-                out.append(f"      <PhongExponent>{_num(m.phong)}</PhongExponent>")
+                out.append(f"      <PhongExponent>{num(m.phong)}</PhongExponent>")
             if m.transparency is not None:
-                out.append(f"      <Transparency>{_v(m.transparency)}</Transparency>")
+                out.append(f"      <Transparency>{vec(m.transparency)}</Transparency>")
             if m.refraction_index is not None:
-                out.append(f"      <RefractionIndex>{_num(m.refraction_index)}</RefractionIndex>")
+                out.append(f"      <RefractionIndex>{num(m.refraction_index)}</RefractionIndex>")
             out.append("    </Material>")
         out.append("  </Materials>")
         out.append("  <VertexData>")
@@ -146,7 +160,7 @@ class SceneSpec:
             out.append(f'    <Sphere id="{i + 1}">')
             out.append(f"      <Material>{mat}</Material>")
             out.append(f"      <Center>{c}</Center>")
-            out.append(f"      <Radius>{_num(r)}</Radius>")
+            out.append(f"      <Radius>{num(r)}</Radius>")
             out.append("    </Sphere>")
         out.append("  </Objects>")
         out.append("</Scene>")
