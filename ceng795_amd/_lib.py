@@ -158,6 +158,8 @@ SIGNATURES = {
     "rt_debug_frame_occupancy": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "rt_debug_quotient_check": (C.c_int, [C.c_int, C.c_ulonglong, C.c_longlong,
                                           C.POINTER(C.c_longlong)]),
+    "rt_debug_quotient_check_mode": (C.c_int, [C.c_int, C.c_int, C.c_ulonglong, C.c_longlong,
+                                               C.POINTER(C.c_longlong)]),
     "rt_ray_query_version": (C.c_int, []),
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
                                        C.c_void_p]),

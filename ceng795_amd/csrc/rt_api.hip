@@ -35,8 +35,8 @@ hipError_t launch_resolve_rows(const RenderParams& P, const unsigned* rec, int r
 hipError_t launch_resolve(const RenderParams& P, const UntileParams& U, bool spheres,
                           hipStream_t stream);
 unsigned long long read_reset_exact_fallbacks();
-hipError_t launch_quot_check(unsigned long long seed, long long count, unsigned long long* counts,
-                             hipStream_t stream);
+hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,
+                             unsigned long long* counts, hipStream_t stream);
 bool diag_build();
 long long read_reset_timeline(unsigned long long* out, long long max_values);
 long long read_reset_phases(unsigned long long* out, long long max_values);
@@ -2032,22 +2032,34 @@ int rt_debug_frame_occupancy(int device, int* out4) {
   });
 }
 
-int rt_debug_quotient_check(int device, unsigned long long seed, long long count,
-                            long long* out2) {
-  if (!out2 || count < 0) return set_error(RT_E_INVALID, "rt_debug_quotient_check: bad argument");
+int rt_debug_quotient_check_mode(int device, int mode, unsigned long long seed, long long count,
+                                 long long* out4) {
+  if (!out4 || count < 0 || mode < 0 || mode > 1)
+    return set_error(RT_E_INVALID, "rt_debug_quotient_check: bad argument");
   return guarded([&] {
     DeviceGuard g(device);
     DevBuf<unsigned long long> buf;
-    buf.reserve(2, "alloc");
+    buf.reserve(4, "alloc");
     unsigned long long* d = buf.p;
-    hip_check(hipMemset(d, 0, 2 * sizeof *d), "clear");
-    hip_check(launch_quot_check(seed, count, d, nullptr), "quotient check launch");
-    unsigned long long h[2];
+    hip_check(hipMemset(d, 0, 4 * sizeof *d), "clear");
+    hip_check(launch_quot_check(mode, seed, count, d, nullptr), "quotient check launch");
+    unsigned long long h[4];
     hip_check(hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost), "read");
-    out2[0] = (long long)h[0];
-    out2[1] = (long long)h[1];
+    for (int k = 0; k < 4; k++) out4[k] = (long long)h[k];
     return RT_OK;
   });
+}
+
+int rt_debug_quotient_check(int device, unsigned long long seed, long long count,
+                            long long* out2) {
+  if (!out2) return set_error(RT_E_INVALID, "rt_debug_quotient_check: bad argument");
+  long long out4[4];
+  const int rc = rt_debug_quotient_check_mode(device, 0, seed, count, out4);
+  if (rc == RT_OK) {
+    out2[0] = out4[0];
+    out2[1] = out4[1];
+  }
+  return rc;
 }
 
 int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt_stats* stats) {

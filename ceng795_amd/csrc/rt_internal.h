@@ -59,6 +59,9 @@ enum : int {
   // totals above still enclose them)
   kPhCycPrologue, kPhCycPrimSetup, kPhCycPrimWalk, kPhCycPrimTail, kPhCycShadSetup,
   kPhCycShadWalk, kPhCycShadTail,
+  // the shading phase (kPhCycShade) in three: until the hit record is back, the dependent
+  // normal -> material loads, and the arithmetic with the colour store
+  kPhCycShadeRecord, kPhCycShadeLoads, kPhCycShadeMath,
   kPhaseSlots
 };
 // Per traversal kind: queued tests whose triangle / sphere test hit in range (the only ones whose

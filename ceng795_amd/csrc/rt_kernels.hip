@@ -268,6 +268,66 @@ __device__ __forceinline__ V3 tri_quotients(V3 n, float det, bool quot) {
   return n / det;
 }
 
+// The same sharing for the divisions outside the walks (round 13): the three quotients of a
+// normalize by its length, and a light's six diffuse and specular terms by d2.  The operand
+// range is tri_quotients': divisor in [2^-40, 2^40], numerators 0 or in [2^-49, 2^49]; the
+// range is tested per vector here, and any lane outside it takes `/`.
+#ifndef RT_HANDOVER  // (the switches are described with the frame kernel's phases, below)
+#define RT_HANDOVER 15
+#endif
+constexpr bool kShareRcp = (RT_HANDOVER & 8) != 0;
+__device__ __forceinline__ bool quot_divisor_ok(float d) {
+  const float ad = __builtin_fabsf(d);
+  return (ad >= 0x1p-40f) & (ad <= 0x1p40f);
+}
+__device__ __forceinline__ float refined_rcp(float d) {
+  const float y = __builtin_amdgcn_rcpf(d);
+  return __builtin_fmaf(__builtin_fmaf(-d, y, 1.0f), y, y);
+}
+// A normalize's components are at most its length (times 1 + 2^-22), so only the smallest
+// magnitude is tested; a vector with a zero component takes `/`.
+__device__ __forceinline__ bool normalize_in_range(V3 a, float len) {
+  const float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)),
+                                   __builtin_fabsf(a.z));
+  return (lo >= 0x1p-49f) & quot_divisor_ok(len);
+}
+// Any three numerators: 2 * bits - 1 drops the sign and wraps a zero to the top, so one unsigned
+// minimum tests "0 or >= 2^-49"; the maximum magnitude tests the upper end (and fails an inf).
+__device__ __forceinline__ bool numerators_in_range(V3 n) {
+  const unsigned ux = (__float_as_uint(n.x) << 1) - 1u, uy = (__float_as_uint(n.y) << 1) - 1u,
+                 uz = (__float_as_uint(n.z) << 1) - 1u;
+  const unsigned lo = min(min(ux, uy), uz);
+  const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(n.x), __builtin_fabsf(n.y)),
+                                   __builtin_fabsf(n.z));
+  return (lo >= (0x27000000u << 1) - 1u) & (hi <= 0x1p49f);  // 0x27000000: 2^-49
+}
+// a / length(a).  dead: a lane whose result nobody reads counts as in range, so that it does not
+// send its wave through the `/` path as well.
+__device__ __forceinline__ V3 normalize_shared(V3 a, bool dead = false) {
+  const float len = length(a);
+  const bool in_range = normalize_in_range(a, len);
+  if (kShareRcp && (dead | in_range)) {
+    const float y1 = refined_rcp(len);
+    return v3(quot_step(a.x, len, y1), quot_step(a.y, len, y1), quot_step(a.z, len, y1));
+  }
+  return a / len;
+}
+__device__ __forceinline__ bool light_terms_in_range(V3 a, V3 b, float d2) {
+  const bool da = numerators_in_range(a), db = numerators_in_range(b), dd = quot_divisor_ok(d2);
+  return da & db & dd;
+}
+// a / d2 and b / d2
+__device__ __forceinline__ void light_quotients(V3 a, V3 b, float d2, V3& qa, V3& qb) {
+  if (kShareRcp && light_terms_in_range(a, b, d2)) {
+    const float y1 = refined_rcp(d2);
+    qa = v3(quot_step(a.x, d2, y1), quot_step(a.y, d2, y1), quot_step(a.z, d2, y1));
+    qb = v3(quot_step(b.x, d2, y1), quot_step(b.y, d2, y1), quot_step(b.z, d2, y1));
+  } else {
+    qa = a / d2;
+    qb = b / d2;
+  }
+}
+
 // Branch-free: every value is computed and the reference's early exits (Triangle.cpp:46-62)
 // become one predicate with the same comparisons (a NaN fails them as there).  With det == 0
 // the quotients are inf/NaN and unused.
@@ -684,6 +744,31 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
 #endif
 static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADOW >= 0 &&
               RT_DEFER_SHADOW <= 2, "deferred-guard modes");
+
+// What the frame kernel's phases hand to each other instead of rebuilding it (round 13, DESIGN.md
+// §4.3).  A/B builds: -DRT_HANDOVER=<bits>; every value handed over is the expression the later
+// phase evaluated itself, so the frames are the same bits with any setting.
+//   1  the hit point p = e + d * t, computed where the primary walk ends and parked in LDS
+//   2  the last light's normalize(light - p) taken from its shadow ray
+//   4  the occlusion word kept in a register when there is one (occ_words == 1)
+//   8  the three quotients of a normalize, and of a light's terms by d2, share one reciprocal
+//      (kShareRcp, with tri_quotients above)
+// The parked point waits in words of the wave's LDS block that are idle from the end of the
+// primary walk on: sv (x, y), which only a deferred-guard walk uses and which that walk drains
+// before it ends, and the junk words past the queue (z), which only the primary walk's pushes
+// write.  A shadow walk with a deferred guard would use sv: those builds rebuild the point.
+constexpr bool kParkPoint = (RT_HANDOVER & 1) != 0 && RT_DEFER_SHADOW == 0;
+constexpr bool kHandLight = (RT_HANDOVER & 2) != 0;
+constexpr bool kOccRegister = (RT_HANDOVER & 4) != 0;
+__device__ __forceinline__ void park_point(WaveLeafLds& L, int lane, V3 p) {
+  L.sv[lane] = ((unsigned long long)__float_as_uint(p.y) << 32) | __float_as_uint(p.x);
+  L.q[kBatchCap + lane] = __float_as_uint(p.z);
+}
+__device__ __forceinline__ V3 parked_point(const WaveLeafLds& L, int lane) {
+  const unsigned long long xy = L.sv[lane];
+  return v3(__uint_as_float((unsigned)xy), __uint_as_float((unsigned)(xy >> 32)),
+            __uint_as_float(L.q[kBatchCap + lane]));
+}
 
 // Stage 2: the guard decision of the first ns (<= kSurvivorCap) waiting survivors, one per lane,
 // and their commit.
@@ -1189,10 +1274,10 @@ __device__ __forceinline__ const RenderParams& fresh_params(const RenderParams& 
 
 // ------------------------------------------------------------------ render kernels
 // Three phases per packet (trace_frame_kernel): the primary phase finds each pixel's closest
-// hit and writes an 8-byte {t, leaf} record; the shadow phase rebuilds the hit point from it
-// and traces the point-light shadow rays into occlusion bits; the shading phase runs the
-// point-light loop.  Going through the records keeps each phase's live state small
-// (occupancy is what hides the dependent node loads).
+// hit and writes an 8-byte {t, leaf} record; the shadow phase traces the point-light shadow rays
+// from the hit point into occlusion bits; the shading phase runs the point-light loop.  Going
+// through the records (and, for the hit point, the wave's LDS block) keeps each phase's live state
+// small (occupancy is what hides the dependent node loads).
 //
 // A packet is normally one wave's 64 lanes = the tile's 8x8 pixels.  A heavy tile can instead
 // be split over four waves (sub = 0..3: wave `sub` takes quadrant `sub` of the tile, 4x4 pixels
@@ -1390,6 +1475,9 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     closest_hit<false, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   }
   DIAG(const unsigned long long s2 = clock_now());
+  // hit_point's e + d * t while d and t are in registers; the later phases read it back (a miss
+  // parks inf or NaN, which nobody reads)
+  if constexpr (kParkPoint) park_point(L, lane_id(), ray.o + ray.d * t);
   const RenderParams& Pw = fresh_params(P);  // post-traversal fields: not live across it
   const PacketPixel qw = wave_pixel(Pw, L);  // (recomputed, not kept)
   int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
@@ -1431,21 +1519,28 @@ __device__ __forceinline__ V3 hit_point(const RenderParams& P, const PacketPixel
   return ld3(P.cam_e) + primary_dir(P, q.px, q.py) * t;  // Ray::point_at = o + t*d
 }
 
+// What the shadow phase leaves in registers for the shading phase (nothing of it is live across
+// a walk that follows: `wi` and `bits` are each written after their walk).
+struct ShadowHand {
+  V3 wi = {0.0f, 0.0f, 0.0f};  // the last light's normalize(light - p)
+  unsigned bits = 0;           // the last occlusion word (the only one when occ_words == 1)
+};
+
 // Shadow rays of HW2/Scene.cpp:113-127: one bit per point light, set when the light is
 // occluded for this pixel's primary hit.
 template <bool FAST, bool DEEP, bool SPHERES>
 __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
                                               const DevNode* __restrict__ nodes,
                                               const DevLight* __restrict__ lights, int sel,
-                                              int* spill, WaveLeafLds& L) {
+                                              int* spill, WaveLeafLds& L, ShadowHand& hand) {
   Diag dg;
   for (int w = 0; w < P0.occ_words; w++) {
     unsigned bits = 0;
     const int lend = min(P0.num_lights, 32 * (w + 1));
     for (int li = 32 * w; li < lend; li++) {
-      // per light: the pixel's hit record is re-read and its hit point rebuilt, so nothing but
-      // the occlusion bits is live across the traversal (register pressure, not traffic: the
-      // 8-B record is an L2 hit)
+      // per light: the pixel's hit record is re-read and its hit point read back from the wave's
+      // LDS block (park_point), so nothing but the occlusion bits is live across the traversal
+      // (register pressure, not traffic: the 8-B record is an L2 hit)
       DIAG(const unsigned long long s0 = clock_now());
       const RenderParams& P = fresh_params(P0);
       const DevLight& lt = lights[li];
@@ -1462,9 +1557,10 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
         if (lane_l == 0)
           atomicAdd(&counter_row(P, sel_l)[kCntShadow], nhit * (unsigned long long)P.num_lights);
       }
-      const V3 pk = hit ? hit_point(P, q, hit_t(rec)) : v3(0, 0, 0);
+      V3 pk = v3(0, 0, 0);
+      if (hit) pk = kParkPoint ? parked_point(L, lane_l) : hit_point(P, q, hit_t(rec));
       const V3 ld = ld3(lt.position) - pk;
-      const V3 wi = normalize(ld);
+      const V3 wi = normalize_shared(ld, !hit);  // (a lane without a hit traces no shadow ray)
       const float dist = length(ld);
       LaneRay sr = make_ray(pk + wi * P.eps, wi, P.quot_ok);  // p + eps * w_i
       const float thr = dist - P.eps;
@@ -1491,6 +1587,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       }
       DIAG(const unsigned long long s2 = clock_now());
       bits |= (occ ? 1u : 0u) << (li - 32 * w);
+      if constexpr (kHandLight) hand.wi = sr.d;  // (the last light's is the one that stays)
       DIAG(dg.cyc_setup += s1 - s0);
       DIAG(dg.cyc_walk += s2 - s1);
     }
@@ -1499,7 +1596,10 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
     int sel_w = sel;
     asm volatile("" : "+s"(sel_w));
     const int pl = pixel_lane(fresh_lane(), wave_sub(L));
-    if (pl >= 0) Pw.occ[((size_t)sel_w * (kTile * kTile) + pl) * Pw.occ_words + w] = bits;
+    // a lone occlusion word goes to the shading in a register; nothing else reads P.occ
+    hand.bits = bits;
+    if (pl >= 0 && !(kOccRegister && Pw.occ_words == 1))
+      Pw.occ[((size_t)sel_w * (kTile * kTile) + pl) * Pw.occ_words + w] = bits;
     DIAG(dg.cyc_tail += clock_now() - s3);
   }
 #ifdef RT_DIAG
@@ -1554,28 +1654,40 @@ __device__ __forceinline__ V3 shade_hit(const RenderParams& P, const DevPrim* __
                                         const float* __restrict__ normals,
                                         const DevMaterial* __restrict__ mats,
                                         const DevLight* __restrict__ lights, int leaf, V3 p,
-                                        Occ occluded) {
+                                        Occ occluded, int hand_li = -1,
+                                        V3 hand_wi = {0.0f, 0.0f, 0.0f},
+                                        unsigned long long* loads_done = nullptr) {
+  (void)loads_done;  // (RT_DIAG: the time at which the normal and the material are back)
   V3 color = v3(0.0f, 0.0f, 0.0f);
   const V3 e = ld3(P.cam_e);
   const float4 nm = *reinterpret_cast<const float4*>(normals + 4 * leaf);
   const bool tri = !SPHERES || prims[leaf].kind == kPrimTriangle;
-  const V3 n = tri ? v3(nm.x, nm.y, nm.z) : normalize(p - ld3(prims[leaf].v0));
+  const V3 n = tri ? v3(nm.x, nm.y, nm.z) : normalize_shared(p - ld3(prims[leaf].v0));
   const DevMaterial& m = mats[__float_as_int(nm.w)];
-  const V3 w0 = normalize(e - p);  // (ray.o - intersection_point).normalize()
+#ifdef RT_DIAG
+  if (loads_done) {  // every material field now, so that the stamp closes the dependent loads
+    float a = m.ambient[0], d = m.diffuse[0], sp = m.specular[0], ph = m.phong_exponent;
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(d), "+v"(sp), "+v"(ph) : : "memory");
+    *loads_done = clock_now();
+  }
+#endif
+  const V3 w0 = normalize_shared(e - p);  // (ray.o - intersection_point).normalize()
   color = color + ld3(m.ambient) * ld3(P.ambient);
   for (int li = 0; li < P.num_lights; li++) {
     if (occluded(li)) continue;
     const DevLight& Lt = lights[li];
     const V3 ld = ld3(Lt.position) - p;
-    const V3 wi = normalize(ld);
+    // hand_li (wave-uniform, the frame kernel's last light): the caller holds normalize(ld)
+    const V3 wi = li == hand_li ? hand_wi : normalize_shared(ld);
     const float dist = length(ld);
     const V3 I = ld3(Lt.intensity);
     const float d2 = dist * dist;
     const float cos_d = dot(n, wi);
-    color = color + ((ld3(m.diffuse) * I) * cos_d) / d2;
-    const float cos_s = __builtin_fmaxf(dot(n, normalize(w0 + wi)), 0.0f);
+    const float cos_s = __builtin_fmaxf(dot(n, normalize_shared(w0 + wi)), 0.0f);
     const float pw = phong_pow(cos_s, m.phong_exponent);
-    color = color + ((ld3(m.specular) * I) * pw) / d2;
+    V3 diff, spec;  // added in the reference's order: diffuse, then specular
+    light_quotients((ld3(m.diffuse) * I) * cos_d, (ld3(m.specular) * I) * pw, d2, diff, spec);
+    color = (color + diff) + spec;
   }
   return color;
 }
@@ -1586,19 +1698,30 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
                                             const float* __restrict__ normals,
                                             const DevMaterial* __restrict__ mats,
                                             const DevLight* __restrict__ lights, int sel,
-                                            const WaveLeafLds& L, float* stage = nullptr) {
+                                            const WaveLeafLds& L, const ShadowHand& hand,
+                                            float* stage = nullptr) {
   const PacketPixel q = wave_pixel(P, L);  // (pair_rows: never a quadrant wave, L.sub is -1)
   const size_t pix = (size_t)sel * (kTile * kTile) + q.lane;
-  const int2_t rec = P.hits[pix];
+  DIAG(const unsigned long long s0 = clock_now());
+  int2_t rec = P.hits[pix];
+#ifdef RT_DIAG
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec.x), "+v"(rec.y) : : "memory");
+  const unsigned long long s1 = clock_now();
+  unsigned long long s2 = s1;
+#endif
   const bool valid = q.own && hit_leaf(rec) != -2;
   const bool hit = q.own && hit_leaf(rec) >= 0;
+  // a lone occlusion word is the shadow phase's register (0 without lights: no shadow phase)
+  const bool occ_reg = kOccRegister && P.occ_words == 1;
   if (P.records) {  // RT_TILE_RECORDS: the pixel record instead of its colour (rt_resolve_*)
     if (!q.own || (!P.tile_major && !valid)) return;
     unsigned r = kRecOutside;
-    if (hit)
-      r = (unsigned)hit_leaf(rec) | ((P.occ[pix * P.occ_words] & kRecLightMask) << kRecLightShift);
-    else if (valid)
+    if (hit) {
+      const unsigned bits = occ_reg ? hand.bits : P.occ[pix * P.occ_words];
+      r = (unsigned)hit_leaf(rec) | ((bits & kRecLightMask) << kRecLightShift);
+    } else if (valid) {
       r = kRecMiss;
+    }
     unsigned* o = reinterpret_cast<unsigned*>(P.out);
     o[P.tile_major ? pix : (size_t)q.py * P.width + q.px] = r;  // tile-major, or row-major
     return;
@@ -1606,9 +1729,18 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
   V3 color = v3(0.0f, 0.0f, 0.0f);
   if (hit) {
     const unsigned* occ = P.occ + pix * P.occ_words;
-    color = shade_hit<SPHERES>(P, prims, normals, mats, lights, hit_leaf(rec),
-                               hit_point(P, q, hit_t(rec)),
-                               [&](int li) { return ((occ[li >> 5] >> (li & 31)) & 1u) != 0; });
+    const V3 p = kParkPoint ? parked_point(L, lane_id()) : hit_point(P, q, hit_t(rec));
+    color = shade_hit<SPHERES>(
+        P, prims, normals, mats, lights, hit_leaf(rec), p,
+        [&](int li) {
+          const unsigned word = occ_reg ? hand.bits : occ[li >> 5];
+          return ((word >> (li & 31)) & 1u) != 0;
+        },
+        kHandLight ? P.num_lights - 1 : -1, hand.wi
+#ifdef RT_DIAG
+        , &s2
+#endif
+    );
   } else if (valid) {
     color = ld3(P.background);  // primary miss: max_recursion_depth == depth
   }
@@ -1629,6 +1761,20 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
     float* o = P.out + 3 * pix;
     o[0] = o[1] = o[2] = 0.0f;
   }
+#ifdef RT_DIAG
+  {  // the wave's latest material return closes its loads (a lane without a hit has none)
+    unsigned long long s3 = clock_now();
+    for (int o = 32; o; o >>= 1) {
+      const unsigned long long other = __shfl_xor(s2, o, 64);
+      s2 = other > s2 ? other : s2;
+    }
+    if (lane_id() == 0) {
+      atomicAdd(&g_phase[kPhCycShadeRecord], s1 - s0);
+      atomicAdd(&g_phase[kPhCycShadeLoads], s2 - s1);
+      atomicAdd(&g_phase[kPhCycShadeMath], s3 - s2);
+    }
+  }
+#endif
 }
 
 // pair_rows (rt_render into pinned host memory): the frame kernel's stores cross PCIe, where a
@@ -2225,9 +2371,11 @@ __device__ unsigned long long g_timeline[2][kTimelineWaves][3];
 // One launch per frame: each wave runs its packet's primary traversal, its shadow rays and its
 // shading back to back, so a frame is one kernel with one tail (round 4 chained primary ->
 // order -> shadow -> shade kernels, each with its own tail: a 1/8 share of a C3 frame then took
-// 0.16 ms one at a time).  The hit record and occlusion bits still go through the
-// stream's scratch (the same lane writes, then reads them: program order), which keeps the
-// register state of the three phases apart.  tile_cost: the whole packet's time.
+// 0.16 ms one at a time).  The hit record, and the occlusion bits of a scene with
+// more than 32 lights, still go through the stream's scratch (the same lane writes, then reads
+// them: program order), which keeps the register state of the three phases apart; the hit point
+// waits in the wave's LDS block, and the last light's direction and a lone occlusion word stay in
+// registers from the last shadow walk on (RT_HANDOVER).  tile_cost: the whole packet's time.
 template <bool FAST, bool DEEP, bool SPHERES>
 __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_frame_kernel(
     RenderParams P, const DevNode* __restrict__ nodes, const DevLight* __restrict__ lights,
@@ -2263,16 +2411,17 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
     DIAG(const unsigned long long c0 = clock_now());
     primary_packet<FAST, DEEP, SPHERES>(Q, nodes, sel, spill, L);
     DIAG(const unsigned long long c1 = clock_now());
+    ShadowHand hand;
     if (fresh_params(P).num_lights > 0)
-      shadow_packet<FAST, DEEP, SPHERES>(fresh_params(P), nodes, lights, sel, spill, L);
+      shadow_packet<FAST, DEEP, SPHERES>(fresh_params(P), nodes, lights, sel, spill, L, hand);
     DIAG(const unsigned long long c2 = clock_now());
     const RenderParams& Ps = fresh_params(P);
     if (Ps.pair_rows) {
-      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L,
+      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L, hand,
                            reinterpret_cast<float*>(L.q));
       pair_write(fresh_params(P), leaf_lds, &pair_arrived);
     } else {
-      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L);
+      shade_pixel<SPHERES>(Ps, Ps.prims, Ps.normals, Ps.materials, lights, sel, L, hand);
     }
 #ifdef RT_DIAG
     const unsigned long long c3 = clock_now();
@@ -3099,9 +3248,68 @@ __global__ __launch_bounds__(256) void quot_check_kernel(unsigned long long seed
   atomicAdd(&counts[1], n);
 }
 
-hipError_t launch_quot_check(unsigned long long seed, long long count, unsigned long long* counts,
-                             hipStream_t stream) {
-  hipLaunchKernelGGL(quot_check_kernel, dim3(2048), dim3(256), 0, stream, seed, count, counts);
+// Mode 1: normalize_shared and light_quotients against `/` on random vectors.  A case is a vector
+// a, six numerators and a divisor d2.  Exponents: a scale drawn from [-60, 60] (so lengths and
+// divisors fall outside [2^-40, 2^40] as well as inside) minus 0..7 per component; one component
+// in eight is zero, one in eight lies below 2^-49, a quarter of the mantissas are all ones (less
+// 0..3).  counts[0] += cases with a quotient that differs from `/` in any bit, counts[1] += cases,
+// counts[2] += helper calls that took the shared reciprocal, counts[3] += calls that took `/`.
+__device__ __forceinline__ float quot_check_operand(unsigned long long h, int scale) {
+  int e = scale - (int)(h & 7);
+  if (((h >> 3) & 7) == 0) e = -50 - (int)((h >> 6) % 70);  // below 2^-49, down to 2^-119
+  unsigned m = (unsigned)(h >> 16) & 0x7fffffu;
+  if (((h >> 40) & 3) == 0) m = 0x7fffffu - (unsigned)((h >> 42) & 3);
+  float x = __uint_as_float(((unsigned)(e + 127) << 23) | m);
+  if (((h >> 44) & 7) == 0) x = 0.0f;
+  return (h >> 47) & 1 ? -x : x;
+}
+__device__ __forceinline__ bool same_bits(V3 a, V3 b) {
+  return __float_as_uint(a.x) == __float_as_uint(b.x) &&
+         __float_as_uint(a.y) == __float_as_uint(b.y) &&
+         __float_as_uint(a.z) == __float_as_uint(b.z);
+}
+__global__ __launch_bounds__(256) void quot_check_vec_kernel(unsigned long long seed,
+                                                             long long count,
+                                                             unsigned long long* counts) {
+  unsigned long long bad = 0, n = 0, shared = 0, plain = 0;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    unsigned long long h = mix64(seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1));
+    const int sa = (int)(h % 121) - 60, sn = (int)((h >> 8) % 121) - 60,
+              sd = (int)((h >> 16) % 121) - 60;
+    float v[9];
+    for (int k = 0; k < 9; k++) {
+      h = mix64(h ^ 0xD1B54A32D192ED03ull);
+      v[k] = quot_check_operand(h, k < 3 ? sa : sn);
+    }
+    h = mix64(h ^ 0xD1B54A32D192ED03ull);
+    unsigned md = (unsigned)(h >> 16) & 0x7fffffu;
+    if (((h >> 40) & 3) == 0) md = 0x7fffffu - (unsigned)((h >> 42) & 3);
+    const float d2 = __uint_as_float(((unsigned)(sd + 127) << 23) | md);
+    const V3 a = v3(v[0], v[1], v[2]), b = v3(v[3], v[4], v[5]), c = v3(v[6], v[7], v[8]);
+    const float len = length(a);
+    const bool ra = normalize_in_range(a, len), rl = light_terms_in_range(b, c, d2);
+    V3 qb, qc;
+    light_quotients(b, c, d2, qb, qc);
+    const bool oa = same_bits(normalize_shared(a), a / len), ob = same_bits(qb, b / d2),
+               oc = same_bits(qc, c / d2);
+    bad += !(oa & ob & oc);
+    shared += (unsigned)ra + (unsigned)rl;
+    plain += (unsigned)!ra + (unsigned)!rl;
+    n++;
+  }
+  atomicAdd(&counts[0], bad);
+  atomicAdd(&counts[1], n);
+  atomicAdd(&counts[2], kShareRcp ? shared : 0ull);
+  atomicAdd(&counts[3], kShareRcp ? plain : shared + plain);
+}
+
+hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,
+                             unsigned long long* counts, hipStream_t stream) {
+  if (mode == 0)
+    hipLaunchKernelGGL(quot_check_kernel, dim3(2048), dim3(256), 0, stream, seed, count, counts);
+  else
+    hipLaunchKernelGGL(quot_check_vec_kernel, dim3(2048), dim3(256), 0, stream, seed, count,
+                       counts);
   return hipGetLastError();
 }
 

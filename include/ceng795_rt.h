@@ -382,6 +382,16 @@ int rt_debug_frame_occupancy(int device, int* out4);
 int rt_debug_quotient_check(int device, unsigned long long seed, long long count,
                             long long* out2);
 
+/* The same check with a mode.  Mode 0 is rt_debug_quotient_check (out4[2], out4[3] stay 0).
+ * Mode 1 checks the shading's forms of the shared reciprocal (normalize_shared, light_quotients)
+ * on `count` seeded random cases, each a vector to normalise and six numerators over one divisor,
+ * with zero components, components below 2^-49, lengths and divisors outside [2^-40, 2^40] and
+ * all-ones mantissas among them: out4[0] = cases with a quotient that differs from IEEE division
+ * in any bit (must be 0), out4[1] = cases run, out4[2] = helper calls that took the shared
+ * reciprocal, out4[3] = calls that took `/`. */
+int rt_debug_quotient_check_mode(int device, int mode, unsigned long long seed, long long count,
+                                 long long* out4);
+
 /* ---- Ray queries: closest hit and occlusion for the caller's own rays -------------------------
  *
  * New symbols within ABI 7 (test for them with CENG795_RT_HAS_RAY_QUERY / rt_ray_query_version).

@@ -10,7 +10,8 @@ iteration's survivors and the survivors the guard rejected.  Cycles (s_memrealti
 phase of each packet, and inside the traversals the node visits (of which the node load: issue
 to data), and the leaf-batch flushes; and `sections`: the prologue (kernel entry until the wave
 has its tile; outside `frame`), per traversal kind the set-up before the walks, the walks and the
-tail after them, and what the diagnostic atomics take of each phase total.  The clock reads themselves perturb the timing (an SMEM
+tail after them, what the diagnostic atomics take of each phase total, and the shading phase in
+three (until the hit record is back, the dependent normal -> material loads, the arithmetic).  The clock reads themselves perturb the timing (an SMEM
 round trip each), so the cycle split is a proportion, not a kernel time.
 
 usage: CENG795_LIB=diag python tools/phases.py <scene.xml> [--frames 3]   (prints one JSON object)
@@ -104,6 +105,9 @@ def main():
         # a walk's own overhead: the octant loop, entry and exit, the final flush's bracket
         sec["prim_walk_outside_visits_flushes"] = sec["prim_walk"] - cyc["prim_visit"] - cyc["prim_flush"]
         sec["shad_walk_outside_visits_flushes"] = sec["shad_walk"] - cyc["shad_visit"] - cyc["shad_flush"]
+        if n >= 56:  # the shading phase in three (rt_internal.h kPhCycShadeRecord ..): until the
+            # hit record is back, the dependent normal -> material loads, the arithmetic
+            sec.update(zip(["shade_record", "shade_loads", "shade_math"], v[53:56]))
         res["sections"] = {"ticks": sec,
                            "wave_us": {k: round(x / waves / 100.0, 3) for k, x in sec.items()},
                            "share_of_frame": {k: round(x / frame, 4) for k, x in sec.items()}}
