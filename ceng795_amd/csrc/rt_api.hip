@@ -87,7 +87,7 @@ constexpr size_t kRadianceDefaultLimit = size_t(256) << 20;
 // What the launches on one stream (a pooled context's or a caller's) need besides their inputs
 // and outputs; they run one after the other, so they share it.  The buffers only grow.
 struct WorkSet {
-  DevBuf<rt::int2_t> hits;  // per pixel of the selected tiles: the primary hit
+  DevBuf<rt::int2_t> hits;  // kHitRecords builds: per pixel of the selected tiles, the primary hit
   DevBuf<unsigned> occ;     // per pixel: the lights' occlusion bits
   DevBuf<unsigned> sched;   // tile costs, unit order lists, cost snapshot (rt_internal.h)
   DevBuf<float> frames;     // ray-tree frames: recursive scenes' frames and radiance queries
@@ -773,7 +773,8 @@ struct CtxLease {
 
 void WorkSet::reserve_tiles(const HostScene& h, size_t tiles) {
   const size_t lanes = (size_t)kTile * kTile * tiles;
-  hits.reserve(lanes, "alloc hit records");
+  // (the shipped frame kernel keeps the hit in the wave's LDS: hits stays empty, P.hits null)
+  if (kHitRecords) hits.reserve(lanes, "alloc hit records");
   occ.reserve((size_t)occ_words(h) * lanes, "alloc occlusion bits");
   sched.reserve((size_t)sched_words_for(tiles), "alloc tile schedule");
 }

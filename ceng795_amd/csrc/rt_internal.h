@@ -332,6 +332,20 @@ struct PacketGeom {
   int packets;            // trace_packets
 };
 
+// What the frame kernel's phases hand to each other (RT_HANDOVER) and the shadow walk's guard
+// mode (RT_DEFER_SHADOW) are described where they are used, in rt_kernels.hip; their defaults
+// stand here because the host needs one consequence: whether a launch still carries the primary
+// hit records through RenderParams::hits.  It does not when the leaf stays in the wave's LDS key
+// (16), which takes the parked hit point (1) and a shadow walk that leaves the point's words alone.
+#ifndef RT_HANDOVER
+#define RT_HANDOVER (15 | 16 | 128)
+#endif
+#ifndef RT_DEFER_SHADOW
+#define RT_DEFER_SHADOW 0
+#endif
+constexpr bool kLeafInKey = (RT_HANDOVER & 17) == 17 && RT_DEFER_SHADOW == 0;
+constexpr bool kHitRecords = !kLeafInKey;
+
 struct RenderParams {
   const DevNode* nodes;
   const DevLeaf* leaves;  // culling-tree order (DevLeaf), FAST traversal
@@ -375,7 +389,9 @@ struct RenderParams {
   unsigned msaa_mul[2];
   unsigned long long msaa_seed;
   float* out;
-  int2_t* hits;   // num_sel_tiles * 64 records {t bits, leaf}: trace_primary -> shadow, shade
+  // kHitRecords builds only (else null, the slot kept so that no other field moves):
+  // num_sel_tiles * 64 records {t bits, leaf}, primary phase -> shadow, shade
+  int2_t* hits;
   unsigned* occ;  // num_sel_tiles * 64 * occ_words light-occlusion bits: trace_shadow -> shade
   int occ_words;  // ceil(num_lights / 32)
   // heavy-first dispatch (null: off).  tile_cost[sel] holds each selected

@@ -272,9 +272,8 @@ __device__ __forceinline__ V3 tri_quotients(V3 n, float det, bool quot) {
 // normalize by its length, and a light's six diffuse and specular terms by d2.  The operand
 // range is tri_quotients': divisor in [2^-40, 2^40], numerators 0 or in [2^-49, 2^49]; the
 // range is tested per vector here, and any lane outside it takes `/`.
-#ifndef RT_HANDOVER  // (the switches are described with the frame kernel's phases, below)
-#define RT_HANDOVER 15
-#endif
+// (RT_HANDOVER: the switches are described with the frame kernel's phases, below; its default is
+// rt_internal.h's)
 constexpr bool kShareRcp = (RT_HANDOVER & 8) != 0;
 __device__ __forceinline__ bool quot_divisor_ok(float d) {
   const float ad = __builtin_fabsf(d);
@@ -580,6 +579,25 @@ static_assert(2 * sizeof(WaveLeafLds) + 8 <= 11520, "WaveLeafLds: 14 workgroups 
 
 constexpr unsigned long long kNoHitKey = (0x7f800000ull << 32) | 0xffffffffull;  // (+inf, -1)
 
+// The two 32-bit words of a lane's key: [0] the leaf of a closest-hit key, [1] its t bits.
+typedef unsigned __attribute__((may_alias)) key_word_t;
+__device__ __forceinline__ key_word_t* key_words(WaveLeafLds& L, int lane) {
+  return reinterpret_cast<key_word_t*>(&L.key[lane]);
+}
+__device__ __forceinline__ const key_word_t* key_words(const WaveLeafLds& L, int lane) {
+  return reinterpret_cast<const key_word_t*>(&L.key[lane]);
+}
+// A shadow walk's commit: the owner's any-hit flag (any writer: same value).  HIGH: the flag is
+// the key's high word alone, and the low word — the frame kernel's primary leaf, kLeafInKey — is
+// left as it is (occluded KEEP).
+template <bool HIGH>
+__device__ __forceinline__ void set_shadow_flag(WaveLeafLds& L, int src) {
+  if constexpr (HIGH)
+    key_words(L, src)[1] = 1u;
+  else
+    L.key[src] = 1ull;
+}
+
 // This lane's index computed afresh (asm-opaque), so that it is not kept live (and spilled)
 // across a traversal: the shadow phase's light loop.
 __device__ __forceinline__ int fresh_lane() {
@@ -649,7 +667,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // WHOLE: only the whole 64-entry batches run (every lane of an iteration holds an entry); returns
 // the number of entries run, n & ~63 (else n rounded up).
 template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP = true, bool CAMERA = false,
-          bool WHOLE = false>
+          bool WHOLE = false, bool HIGH = false>
 __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L, int n,
                                            const LaneRay& r, float thr, Diag& dg) {
   const int lane = lane_id();
@@ -709,7 +727,7 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
       leaf = idx;
     }
     if (SHADOW) {
-      if (valid & hit & (t > 0.0f) & (t < othr)) L.key[src] = 1ull;  // any writer: same value
+      if (valid & hit & (t > 0.0f) & (t < othr)) set_shadow_flag<HIGH>(L, src);
     } else if (valid & hit & (t > 0.0f) & (t < RT_INF)) {
       atomicMin(&L.key[src], ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)leaf);
     }
@@ -739,9 +757,7 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
 #ifndef RT_DEFER_PRIMARY
 #define RT_DEFER_PRIMARY 2
 #endif
-#ifndef RT_DEFER_SHADOW
-#define RT_DEFER_SHADOW 0
-#endif
+// (RT_DEFER_SHADOW's default, 0, is rt_internal.h's)
 static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADOW >= 0 &&
               RT_DEFER_SHADOW <= 2, "deferred-guard modes");
 
@@ -753,6 +769,16 @@ static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADO
 //   4  the occlusion word kept in a register when there is one (occ_words == 1)
 //   8  the three quotients of a normalize, and of a light's terms by d2, share one reciprocal
 //      (kShareRcp, with tri_quotients above)
+//  16  the primary hit's leaf stays where the walk left it, in the low word of the lane's L.key
+//      (-1 a miss, -2 a lane outside the image or the packet), and no hit record goes through
+//      memory: the shadow walks keep their any-hit flag in the key's high word (occluded KEEP),
+//      which the parked point (1) has made free — without it the record's t is still needed,
+//      and the record path stays
+//      (32 was the material read with scalar loads when the packet's hit lanes agree on it:
+//      measured neutral, not kept)
+//  64  the last light's length(light - p) handed over with its direction (2): off in the shipped
+//      build — alone it measured inside the run-to-run range, DESIGN.md §4.3
+// 128  a walk lowers its priority where it leaves the visit loop, not between two visits
 // The parked point waits in words of the wave's LDS block that are idle from the end of the
 // primary walk on: sv (x, y), which only a deferred-guard walk uses and which that walk drains
 // before it ends, and the junk words past the queue (z), which only the primary walk's pushes
@@ -760,6 +786,9 @@ static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADO
 constexpr bool kParkPoint = (RT_HANDOVER & 1) != 0 && RT_DEFER_SHADOW == 0;
 constexpr bool kHandLight = (RT_HANDOVER & 2) != 0;
 constexpr bool kOccRegister = (RT_HANDOVER & 4) != 0;
+static_assert(kLeafInKey == ((RT_HANDOVER & 16) != 0 && kParkPoint), "rt_internal.h: kLeafInKey");
+constexpr bool kHandDist = (RT_HANDOVER & 64) != 0 && kHandLight;
+constexpr bool kPrioAtExit = (RT_HANDOVER & 128) != 0;
 __device__ __forceinline__ void park_point(WaveLeafLds& L, int lane, V3 p) {
   L.sv[lane] = ((unsigned long long)__float_as_uint(p.y) << 32) | __float_as_uint(p.x);
   L.q[kBatchCap + lane] = __float_as_uint(p.z);
@@ -772,7 +801,7 @@ __device__ __forceinline__ V3 parked_point(const WaveLeafLds& L, int lane) {
 
 // Stage 2: the guard decision of the first ns (<= kSurvivorCap) waiting survivors, one per lane,
 // and their commit.
-template <bool SHADOW, bool SKIP, bool CAMERA>
+template <bool SHADOW, bool SKIP, bool CAMERA, bool HIGH = false>
 __device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& L, int ns,
                                             const LaneRay& r, Diag& dg) {
   const int lane = lane_id();
@@ -810,7 +839,7 @@ __device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& 
   DIAG(dg.defer[kDfGuardIters]++;
        dg.defer[kDfRejected] += __builtin_popcountll(ballot(valid & !ok)));
   if (SHADOW) {
-    if (ok) L.key[src] = 1ull;  // any writer: same value
+    if (ok) set_shadow_flag<HIGH>(L, src);
   } else if (ok) {
     atomicMin(&L.key[src], (s & 0xffffffff00000000ull) | (unsigned)leaf);
   }
@@ -819,7 +848,8 @@ __device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& 
 // Stage 1 over the n queued tests (WHOLE: the whole 64-entry batches only, as batch_flush), the
 // guard batches that fill up on the way, and with DRAIN the survivors still waiting at the end.
 // ns: survivors waiting, in and out.  Returns the number of queue entries run.
-template <bool SHADOW, bool SPHERES, bool SKIP, bool CAMERA, bool WHOLE, bool DRAIN>
+template <bool SHADOW, bool SPHERES, bool SKIP, bool CAMERA, bool WHOLE, bool DRAIN,
+          bool HIGH = false>
 __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveLeafLds& L, int n,
                                                     int& nsurv, const LaneRay& r, float thr,
                                                     Diag& dg) {
@@ -871,7 +901,7 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
       }
     }
     if (ns >= kSurvivorCap || !more) {
-      guard_batch<SHADOW, SKIP, CAMERA>(P, L, ns < kSurvivorCap ? ns : kSurvivorCap, r, dg);
+      guard_batch<SHADOW, SKIP, CAMERA, HIGH>(P, L, ns < kSurvivorCap ? ns : kSurvivorCap, r, dg);
       DIAG(dg.defer[kDfSplitDrains] += ns > kSurvivorCap);
       ns = ns > kSurvivorCap ? ns - kSurvivorCap : 0;
       if (late) L.sv[rank - kSurvivorCap] = rec;  // the buffer is empty again
@@ -882,14 +912,15 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
 }
 
 // The leaf batches of one flush, by the walk's mode (RT_DEFER_*): see above.
-template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA, bool WHOLE>
+template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA, bool WHOLE,
+          bool HIGH = false>
 __device__ __forceinline__ int leaf_batches(const RenderParams& P, WaveLeafLds& L, int n, int& ns,
                                             const LaneRay& r, float thr, Diag& dg) {
   constexpr int mode = !CULL ? 0 : (SHADOW ? RT_DEFER_SHADOW : RT_DEFER_PRIMARY);
   if constexpr (mode == 0)
-    return batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, WHOLE>(P, L, n, r, thr, dg);
+    return batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, WHOLE, HIGH>(P, L, n, r, thr, dg);
   else
-    return batch_flush_deferred<SHADOW, SPHERES, SKIP, CAMERA, WHOLE, !WHOLE || mode == 1>(
+    return batch_flush_deferred<SHADOW, SPHERES, SKIP, CAMERA, WHOLE, !WHOLE || mode == 1, HIGH>(
         P, L, n, ns, r, thr, dg);
 }
 
@@ -900,10 +931,11 @@ __device__ __forceinline__ int leaf_batches(const RenderParams& P, WaveLeafLds& 
 // lane whose occluding test is carried stays `alive` until the next flush.
 // (The lane index is computed afresh, as in the shadow phase's light loop, so that no address
 // derived from it is kept live across the walk: the kernel sits at its 72-VGPR budget.)
-template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA = false>
+template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA = false, bool HIGH = false>
 __device__ __forceinline__ void leaf_flush_full(const RenderParams& P, WaveLeafLds& L, int& n,
                                                 int& ns, const LaneRay& r, float thr, Diag& dg) {
-  const int full = leaf_batches<SHADOW, SPHERES, CULL, SKIP, CAMERA, true>(P, L, n, ns, r, thr, dg);
+  const int full =
+      leaf_batches<SHADOW, SPHERES, CULL, SKIP, CAMERA, true, HIGH>(P, L, n, ns, r, thr, dg);
   const int rem = n - full;
   const int lane = fresh_lane();
   if (lane < rem) L.q[lane] = L.q[full + lane];
@@ -1131,21 +1163,28 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
   if (!OCT) L.key[lane] = kNoHitKey;
   int node = FAST ? P.accel_root + root_off : P.root_ref;
+  // (the frame kernel's walks: the visits' priority is set once and after each flush, and lowered
+  // where the walk leaves the loop — no s_setprio pair between two visits that no flush separates)
+  constexpr bool kAtExit = kPrioAtExit && OCT != 0;
+  if (kAtExit) RT_PRIO_VISIT_BEGIN;
   for (;;) {
     if (pending >= kBatchFlush) {  // between visits: only the ray and the stack are live
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
       leaf_flush_full<false, SPHERES, FAST, SKIP, CAMERA>(P, L, pending, waiting, r, 0.0f, dg);
-      RT_PRIO_FLUSH_END;
+      if (kAtExit)
+        RT_PRIO_VISIT_BEGIN;
+      else
+        RT_PRIO_FLUSH_END;
       DIAG(dg.cyc_flush += clock_now() - tf0);
     }
     if constexpr (FAST) {
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
-      RT_PRIO_VISIT_BEGIN;
+      if (!kAtExit) RT_PRIO_VISIT_BEGIN;
       const bool more =
           visit_wide<SKIP, false, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, ~0ull,
                                                            st, dg);
-      RT_PRIO_VISIT_END;
+      if (!kAtExit) RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
     } else {
@@ -1161,6 +1200,7 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
       if (!advance(st, N.child[0], N.child[1], m0, m1, t0, t1, node, m, ~0ull)) break;
     }
   }
+  if (kAtExit) RT_PRIO_VISIT_END;
   if (pending | waiting) {  // the last tests, and the survivors still waiting for their guard
     DIAG(const unsigned long long tf0 = clock_now());
     RT_PRIO_FLUSH_BEGIN;
@@ -1182,7 +1222,9 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
 // closest-hit shadow test `0 < t_closest < dist - eps` (HW2/Scene.cpp:123-127), appendix A.7.
 // OCT != 0: one sub-walk of a packet, as in closest_hit — the caller clears every lane's L.key
 // and reads it after the last sub-walk; the value returned then covers the lanes walked so far.
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, int OCT = 0>
+// KEEP (the frame kernel, kLeafInKey): the flag is the key's high word alone — cleared, tested and
+// returned — and the low word, the lane's primary leaf, is left as it is.
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, int OCT = 0, bool KEEP = false>
 __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          int* spill, WaveLeafLds& L, const LaneRay& r, bool active,
                                          float thr, Diag& dg, int root_off = 0) {
@@ -1213,27 +1255,35 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
   if (!OCT) {
     unsigned long long clear = 0ull;
     asm volatile("" : "+v"(clear));  // a fresh zero here, not one kept (and spilled) across the walk
-    L.key[lane] = clear;
+    if (KEEP)
+      key_words(L, lane)[1] = (unsigned)clear;
+    else
+      L.key[lane] = clear;
   }
   int node = FAST ? P.accel_root + root_off : P.root_ref;
+  constexpr bool kAtExit = kPrioAtExit && OCT != 0;  // (as in closest_hit)
+  if (kAtExit) RT_PRIO_VISIT_BEGIN;
   for (;;) {
     if (pending >= kShadowFlush) {  // between visits; a lane found occluded stops entering nodes
       DIAG(const unsigned long long tf0 = clock_now());
       RT_PRIO_FLUSH_BEGIN;
-      leaf_flush_full<true, SPHERES, FAST, SKIP>(P, L, pending, waiting, r, thr, dg);
-      RT_PRIO_FLUSH_END;
+      leaf_flush_full<true, SPHERES, FAST, SKIP, false, KEEP>(P, L, pending, waiting, r, thr, dg);
+      if (kAtExit)
+        RT_PRIO_VISIT_BEGIN;
+      else
+        RT_PRIO_FLUSH_END;
       DIAG(dg.cyc_flush += clock_now() - tf0);
-      alive &= ~ballot(L.key[lane] != 0ull);
+      alive &= ~ballot(KEEP ? key_words(L, lane)[1] != 0u : L.key[lane] != 0ull);
       m &= alive;
       if (!m && !st.pop_live(node, m, alive)) break;
     }
     if constexpr (FAST) {
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
-      RT_PRIO_VISIT_BEGIN;
+      if (!kAtExit) RT_PRIO_VISIT_BEGIN;
       const bool more =
           visit_wide<SKIP, true, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, alive,
                                                           st, dg);
-      RT_PRIO_VISIT_END;
+      if (!kAtExit) RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
     } else {
@@ -1248,16 +1298,17 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
       if (!advance(st, N.child[0], N.child[1], m0, m1, t0, t1, node, m, alive)) break;
     }
   }
+  if (kAtExit) RT_PRIO_VISIT_END;
   if (pending | waiting) {
     DIAG(const unsigned long long tf0 = clock_now());
     RT_PRIO_FLUSH_BEGIN;
-    leaf_batches<true, SPHERES, FAST, SKIP, false, false>(P, L, pending, waiting, r, thr, dg);
+    leaf_batches<true, SPHERES, FAST, SKIP, false, false, KEEP>(P, L, pending, waiting, r, thr, dg);
     RT_PRIO_FLUSH_END;
     DIAG(dg.cyc_flush += clock_now() - tf0; dg.ev[kPhFlushes] += pending != 0;
          dg.ev[kPhFlushIters] += (pending + 63) / 64);
   }
   DIAG(dg.ev[kPhPushes] += st.pushes; dg.ev[kPhPops] += st.pops);
-  return L.key[lane] != 0ull;
+  return KEEP ? key_words(L, lane)[1] != 0u : L.key[lane] != 0ull;
 }
 
 // The kernel's RenderParams (its FIRST argument, so at offset 0 of the kernarg segment) read
@@ -1274,10 +1325,11 @@ __device__ __forceinline__ const RenderParams& fresh_params(const RenderParams& 
 
 // ------------------------------------------------------------------ render kernels
 // Three phases per packet (trace_frame_kernel): the primary phase finds each pixel's closest
-// hit and writes an 8-byte {t, leaf} record; the shadow phase traces the point-light shadow rays
-// from the hit point into occlusion bits; the shading phase runs the point-light loop.  Going
-// through the records (and, for the hit point, the wave's LDS block) keeps each phase's live state
-// small (occupancy is what hides the dependent node loads).
+// hit and leaves its leaf and its point in the wave's LDS block (a kHitRecords build: an 8-byte
+// {t, leaf} record in memory); the shadow phase traces the point-light shadow rays from the hit
+// point into occlusion bits; the shading phase runs the point-light loop.  Going through LDS (or
+// the records) keeps each phase's live state small (occupancy is what hides the dependent node
+// loads).
 //
 // A packet is normally one wave's 64 lanes = the tile's 8x8 pixels.  A heavy tile can instead
 // be split over four waves (sub = 0..3: wave `sub` takes quadrant `sub` of the tile, 4x4 pixels
@@ -1483,7 +1535,14 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
   rec.x = qw.valid ? leaf : -2;  // -1 miss, -2 outside the image
   rec.y = __float_as_int(t);
-  if (qw.own) Pw.hits[(size_t)sel * (kTile * kTile) + qw.lane] = rec;
+  if constexpr (kLeafInKey) {
+    // The later phases read the leaf from the low word of this lane's key.  Written by every
+    // lane: a walk that found nothing to enter (or a root primitive) never set the key, and a
+    // lane outside the image, or of a quadrant wave outside the packet, holds -2.
+    key_words(L, lane_id())[0] = (unsigned)rec.x;
+  } else if (qw.own) {
+    Pw.hits[(size_t)sel * (kTile * kTile) + qw.lane] = rec;
+  }
   const unsigned long long nvalid = __builtin_popcountll(ballot(qw.valid));  // (all lanes)
   const unsigned long long nhit = __builtin_popcountll(ballot(qw.valid && leaf >= 0));
   if (Pw.counters && lane_id() == 0) {  // spread over kCounterSlots rows: no hot address
@@ -1520,9 +1579,11 @@ __device__ __forceinline__ V3 hit_point(const RenderParams& P, const PacketPixel
 }
 
 // What the shadow phase leaves in registers for the shading phase (nothing of it is live across
-// a walk that follows: `wi` and `bits` are each written after their walk).
+// a walk that follows: `wi`, `dist` and `bits` are each written after their walk; `dist`, which
+// the walk itself does not use, is live through its own light's walk).
 struct ShadowHand {
   V3 wi = {0.0f, 0.0f, 0.0f};  // the last light's normalize(light - p)
+  float dist = 0.0f;           // ... and its length(light - p) (kHandDist)
   unsigned bits = 0;           // the last occlusion word (the only one when occ_words == 1)
 };
 
@@ -1549,16 +1610,22 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       int sel_l = sel;
       asm volatile("" : "+s"(sel_l));
       const int lane_l = fresh_lane();
-      const PacketPixel q = wave_pixel(P, L, lane_l);
-      const int2_t rec = P.hits[(size_t)sel_l * (kTile * kTile) + q.lane];
-      const bool hit = q.own && hit_leaf(rec) >= 0;
+      bool hit;
+      V3 pk = v3(0, 0, 0);
+      if constexpr (kLeafInKey) {  // the leaf in the lane's key: -1 a miss, -2 no pixel of the frame
+        hit = (int)key_words(L, lane_l)[0] >= 0;
+        if (hit) pk = parked_point(L, lane_l);
+      } else {
+        const PacketPixel q = wave_pixel(P, L, lane_l);
+        const int2_t rec = P.hits[(size_t)sel_l * (kTile * kTile) + q.lane];
+        hit = q.own && hit_leaf(rec) >= 0;
+        if (hit) pk = kParkPoint ? parked_point(L, lane_l) : hit_point(P, q, hit_t(rec));
+      }
       if (li == 0 && P.counters) {  // the packet's shadow rays: every light's are these lanes'
         const unsigned long long nhit = __builtin_popcountll(ballot(hit));
         if (lane_l == 0)
           atomicAdd(&counter_row(P, sel_l)[kCntShadow], nhit * (unsigned long long)P.num_lights);
       }
-      V3 pk = v3(0, 0, 0);
-      if (hit) pk = kParkPoint ? parked_point(L, lane_l) : hit_point(P, q, hit_t(rec));
       const V3 ld = ld3(lt.position) - pk;
       const V3 wi = normalize_shared(ld, !hit);  // (a lane without a hit traces no shadow ray)
       const float dist = length(ld);
@@ -1571,23 +1638,30 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
         if (kOctantNodes == 1) octant_shifts_zero(sr);
         unsigned long long clear = 0ull;
         asm volatile("" : "+v"(clear));  // (a fresh zero, as in occluded)
-        L.key[lane_l] = clear;
+        if constexpr (kLeafInKey)  // the flag word only: the leaf below it stays for the shading
+          key_words(L, lane_l)[1] = (unsigned)clear;
+        else
+          L.key[lane_l] = clear;
         octant_walks(sr, hit, dg, [&](bool mine, int k) {
           const int off = k * P.accel_stride;
           if (ballot(mine && any_skip))
-            occluded<true, FAST, DEEP, SPHERES, kOctantNodes>(P, nodes, spill, L, sr, mine, thr, dg, off);
+            occluded<true, FAST, DEEP, SPHERES, kOctantNodes, kLeafInKey>(P, nodes, spill, L, sr,
+                                                                          mine, thr, dg, off);
           else
-            occluded<false, FAST, DEEP, SPHERES, kOctantNodes>(P, nodes, spill, L, sr, mine, thr, dg, off);
+            occluded<false, FAST, DEEP, SPHERES, kOctantNodes, kLeafInKey>(P, nodes, spill, L, sr,
+                                                                           mine, thr, dg, off);
         });
-        occ = L.key[fresh_lane()] != 0ull;
+        occ = kLeafInKey ? key_words(L, fresh_lane())[1] != 0u : L.key[fresh_lane()] != 0ull;
       } else {
-        occ = ballot(any_skip)
-                  ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg)
-                  : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, hit, thr, dg);
+        occ = ballot(any_skip) ? occluded<true, FAST, DEEP, SPHERES, 0, kLeafInKey>(
+                                     P, nodes, spill, L, sr, hit, thr, dg)
+                               : occluded<false, FAST, DEEP, SPHERES, 0, kLeafInKey>(
+                                     P, nodes, spill, L, sr, hit, thr, dg);
       }
       DIAG(const unsigned long long s2 = clock_now());
       bits |= (occ ? 1u : 0u) << (li - 32 * w);
       if constexpr (kHandLight) hand.wi = sr.d;  // (the last light's is the one that stays)
+      if constexpr (kHandDist) hand.dist = dist;
       DIAG(dg.cyc_setup += s1 - s0);
       DIAG(dg.cyc_walk += s2 - s1);
     }
@@ -1655,7 +1729,7 @@ __device__ __forceinline__ V3 shade_hit(const RenderParams& P, const DevPrim* __
                                         const DevMaterial* __restrict__ mats,
                                         const DevLight* __restrict__ lights, int leaf, V3 p,
                                         Occ occluded, int hand_li = -1,
-                                        V3 hand_wi = {0.0f, 0.0f, 0.0f},
+                                        V3 hand_wi = {0.0f, 0.0f, 0.0f}, float hand_dist = 0.0f,
                                         unsigned long long* loads_done = nullptr) {
   (void)loads_done;  // (RT_DIAG: the time at which the normal and the material are back)
   V3 color = v3(0.0f, 0.0f, 0.0f);
@@ -1677,9 +1751,10 @@ __device__ __forceinline__ V3 shade_hit(const RenderParams& P, const DevPrim* __
     if (occluded(li)) continue;
     const DevLight& Lt = lights[li];
     const V3 ld = ld3(Lt.position) - p;
-    // hand_li (wave-uniform, the frame kernel's last light): the caller holds normalize(ld)
+    // hand_li (wave-uniform, the frame kernel's last light): the caller holds normalize(ld),
+    // and with kHandDist length(ld)
     const V3 wi = li == hand_li ? hand_wi : normalize_shared(ld);
-    const float dist = length(ld);
+    const float dist = kHandDist && li == hand_li ? hand_dist : length(ld);
     const V3 I = ld3(Lt.intensity);
     const float d2 = dist * dist;
     const float cos_d = dot(n, wi);
@@ -1703,7 +1778,13 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
   const PacketPixel q = wave_pixel(P, L);  // (pair_rows: never a quadrant wave, L.sub is -1)
   const size_t pix = (size_t)sel * (kTile * kTile) + q.lane;
   DIAG(const unsigned long long s0 = clock_now());
-  int2_t rec = P.hits[pix];
+  int2_t rec;
+  if constexpr (kLeafInKey) {  // the leaf waits in the lane's key; t went into the parked point
+    rec.x = (int)key_words(L, lane_id())[0];
+    rec.y = 0;
+  } else {
+    rec = P.hits[pix];
+  }
 #ifdef RT_DIAG
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec.x), "+v"(rec.y) : : "memory");
   const unsigned long long s1 = clock_now();
@@ -1736,7 +1817,7 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
           const unsigned word = occ_reg ? hand.bits : occ[li >> 5];
           return ((word >> (li & 31)) & 1u) != 0;
         },
-        kHandLight ? P.num_lights - 1 : -1, hand.wi
+        kHandLight ? P.num_lights - 1 : -1, hand.wi, hand.dist
 #ifdef RT_DIAG
         , &s2
 #endif
@@ -2371,11 +2452,12 @@ __device__ unsigned long long g_timeline[2][kTimelineWaves][3];
 // One launch per frame: each wave runs its packet's primary traversal, its shadow rays and its
 // shading back to back, so a frame is one kernel with one tail (round 4 chained primary ->
 // order -> shadow -> shade kernels, each with its own tail: a 1/8 share of a C3 frame then took
-// 0.16 ms one at a time).  The hit record, and the occlusion bits of a scene with
-// more than 32 lights, still go through the stream's scratch (the same lane writes, then reads
-// them: program order), which keeps the register state of the three phases apart; the hit point
-// waits in the wave's LDS block, and the last light's direction and a lone occlusion word stay in
-// registers from the last shadow walk on (RT_HANDOVER).  tile_cost: the whole packet's time.
+// 0.16 ms one at a time).  The occlusion bits of a scene with more than 32 lights
+// still go through the stream's scratch (the same lane writes, then reads them: program order),
+// which keeps the register state of the three phases apart; the hit's leaf and point wait in the
+// wave's LDS block (a lane is the same pixel's in every phase, in a quadrant wave too), and the
+// last light's direction and a lone occlusion word stay in registers from the last shadow walk on
+// (RT_HANDOVER).  tile_cost: the whole packet's time.
 template <bool FAST, bool DEEP, bool SPHERES>
 __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_frame_kernel(
     RenderParams P, const DevNode* __restrict__ nodes, const DevLight* __restrict__ lights,
