@@ -457,8 +457,6 @@ int collapse_wide(HostScene& s, const SahBuilder& B, int broot, const std::vecto
 // octant k finds its ENTRY plane in the low half of every word, and inner_base points into the
 // same copy.
 void add_octant_copies(HostScene& s, size_t nref, size_t nw) {
-  s.accel_stride = 0;
-  if (kOctantCopies == 1) return;
   s.accel_stride = (int)nw;
   s.nodes.resize(nref + (size_t)kOctantCopies * nw);
   for (int k = 1; k < kOctantCopies; k++)
@@ -615,8 +613,8 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
     int node, depth;
   };
   // copy 0 of the culling nodes: [nref, nref + ncull); the octant copies follow it
-  const size_t ncull = s.accel_stride > 0 ? (size_t)s.accel_stride : s.nodes.size() - (size_t)nref;
-  if ((kOctantCopies > 1) != (s.accel_stride > 0)) return "octant copies and their stride disagree";
+  if (s.accel_stride <= 0) return "octant copies and their stride disagree";
+  const size_t ncull = (size_t)s.accel_stride;
   if (s.nodes.size() != (size_t)nref + (size_t)kOctantCopies * ncull || ncull % 2)
     return "node array is not the reference nodes and " + std::to_string(kOctantCopies) +
            " copies of the culling nodes";

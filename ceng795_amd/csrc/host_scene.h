@@ -44,7 +44,7 @@ struct HostScene {
   int accel_root = -1;   // tagged index into nodes (8-wide nodes follow the reference's), -1 = none
   int accel_depth = 0;   // stack entries a traversal from accel_root can need
   int accel_items = 0;   // treelets
-  int accel_stride = 0;  // node slots from one octant copy of the culling nodes to the next (0: one copy)
+  int accel_stride = 0;  // node slots from one octant copy of the culling nodes to the next (0: no culling tree)
   float accel_box[6] = {0, 0, 0, 0, 0, 0};
   // per-axis outward margin of every culling box: 2^-18 * the largest coordinate magnitude of
   // the scene, its cameras and every ray origin; it lets the kernels cull on
@@ -58,7 +58,7 @@ struct HostScene {
 // Cuts the reference tree into treelets of <= K leaves (K = 1: lone leaves; 2: also leaf
 // pairs; K <= 0: no culling tree) and appends an 8-wide SAH tree over them.  Leaves the
 // reference nodes, leaves and tie-break order untouched.
-// With RT_OCTANT_NODES the culling nodes are stored kOctantCopies times (rt_internal.h).  Throws
+// The culling nodes are stored kOctantCopies times, once per octant (rt_internal.h).  Throws
 // std::domain_error when the node array would pass kMaxNodeSlots.
 void build_accel(HostScene& s, int K);
 // "" when a scene of ref_slots reference node slots and wide_slots culling node slots (one copy)

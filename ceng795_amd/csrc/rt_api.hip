@@ -68,14 +68,8 @@ using namespace rt;
 // which wait for CU slots the render holds: pageable 1.00-1.05 ms unbanded, 0.89 with 2 bands,
 // 0.98 with 4, 1.36 with 8; a high-priority copy stream changed nothing —
 // profiles/r06/host_rate_bands.jsonl.)
-#ifndef RT_DIRECT_PINNED  // (A/B builds)
-#define RT_DIRECT_PINNED 1
-#endif
 #ifndef RT_RENDER_CHUNKS  // (A/B builds)
 #define RT_RENDER_CHUNKS 2
-#endif
-#ifndef RT_PAIR_ROWS  // (A/B builds: 0 = each wave of a directly written frame writes its own tile)
-#define RT_PAIR_ROWS 1
 #endif
 constexpr int kRenderChunks = RT_RENDER_CHUNKS;
 
@@ -87,7 +81,6 @@ constexpr size_t kRadianceDefaultLimit = size_t(256) << 20;
 // What the launches on one stream (a pooled context's or a caller's) need besides their inputs
 // and outputs; they run one after the other, so they share it.  The buffers only grow.
 struct WorkSet {
-  DevBuf<rt::int2_t> hits;  // kHitRecords builds: per pixel of the selected tiles, the primary hit
   DevBuf<unsigned> occ;     // per pixel: the lights' occlusion bits
   DevBuf<unsigned> sched;   // tile costs, unit order lists, cost snapshot (rt_internal.h)
   DevBuf<float> frames;     // ray-tree frames: recursive scenes' frames and radiance queries
@@ -95,7 +88,7 @@ struct WorkSet {
   DevBuf<unsigned> query;   // queries with RT_QUERY_REORDER: permutation, histogram, totals
   DevBuf<unsigned> film;    // film splats: per-pixel offsets, scan totals, sample lists (FilmParams)
   DevBuf<rt_radiance> film_rad;  // rt_film_shade_rays*: the colours between the query and the splat
-  void reserve_tiles(const HostScene& h, size_t tiles);  // hits, occ and sched
+  void reserve_tiles(const HostScene& h, size_t tiles);  // occ and sched
   // Sizes the set for launch P of camera c, whose num_sel_tiles is final, and points P at it.
   void bind(const rt_scene* s, const rt_camera& c, RenderParams& P);
 };
@@ -300,9 +293,6 @@ int untile_vec(const UntileParams& U) {
 // 0.59 unweighted).  A point X projects to the image-plane point tl + su fx - sv fy that
 // e + l (X - e) reaches (Cramer's rule; l > 0: in front of the camera); a primitive with a point
 // not in front is left out.  Only the order depends on it, never a pixel.
-#ifndef RT_COLD_WEIGHT  // (A/B builds: 0 = every primitive counts 1)
-#define RT_COLD_WEIGHT 1
-#endif
 std::vector<unsigned> cold_costs(const HostScene& h, const rt_camera& c) {
   const int tx = (c.width + kTile - 1) / kTile, ty = (c.height + kTile - 1) / kTile;
   std::vector<double> acc((size_t)tx * ty, 1.0);
@@ -339,17 +329,15 @@ std::vector<unsigned> cold_costs(const HostScene& h, const rt_camera& c) {
         pts[2][k] = (double)p.v0[k] - p.a2[k];
       }
       n = 3;
-      if (RT_COLD_WEIGHT) {
-        const double a1[3] = {p.a1[0], p.a1[1], p.a1[2]}, a2[3] = {p.a2[0], p.a2[1], p.a2[2]};
-        double nrm[3];
-        cross(a1, a2, nrm);
-        const double d[3] = {(pts[0][0] + pts[1][0] + pts[2][0]) / 3 - e[0],
-                             (pts[0][1] + pts[1][1] + pts[2][1]) / 3 - e[1],
-                             (pts[0][2] + pts[1][2] + pts[2][2]) / 3 - e[2]};
-        const double len = std::sqrt(dot(nrm, nrm) * dot(d, d));
-        const double cosv = len > 0.0 ? std::fabs(dot(nrm, d)) / len : 1.0;
-        weight = 1.0 / std::max(cosv, 0.05);
-      }
+      const double a1[3] = {p.a1[0], p.a1[1], p.a1[2]}, a2[3] = {p.a2[0], p.a2[1], p.a2[2]};
+      double nrm[3];
+      cross(a1, a2, nrm);
+      const double d[3] = {(pts[0][0] + pts[1][0] + pts[2][0]) / 3 - e[0],
+                           (pts[0][1] + pts[1][1] + pts[2][1]) / 3 - e[1],
+                           (pts[0][2] + pts[1][2] + pts[2][2]) / 3 - e[2]};
+      const double len = std::sqrt(dot(nrm, nrm) * dot(d, d));
+      const double cosv = len > 0.0 ? std::fabs(dot(nrm, d)) / len : 1.0;
+      weight = 1.0 / std::max(cosv, 0.05);
     } else {
       const double rad = std::fabs((double)p.a1[0]);
       for (int m = 0; m < 8; m++)
@@ -386,11 +374,8 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
 // instead of in block order (launch_variant in rt_kernels.hip).
 void seed_cold_orders(const rt_scene* s, Replica& r) {
   const HostScene& h = s->host;
-#ifndef RT_COLD_SEED  // (A/B builds: 0 = cold frames in block order)
-#define RT_COLD_SEED 1
-#endif
   r.d_cold = std::vector<DevBuf<unsigned>>(h.cameras.size());
-  if (!RT_COLD_SEED || s->needs_recursion || h.lights.empty()) return;  // (no warm order either)
+  if (s->needs_recursion || h.lights.empty()) return;  // (no warm order either)
   for (size_t cam = 0; cam < h.cameras.size(); cam++) {
     const rt_camera& c = h.cameras[cam];
     if (c.num_samples > 1) continue;
@@ -773,15 +758,12 @@ struct CtxLease {
 
 void WorkSet::reserve_tiles(const HostScene& h, size_t tiles) {
   const size_t lanes = (size_t)kTile * kTile * tiles;
-  // (the shipped frame kernel keeps the hit in the wave's LDS: hits stays empty, P.hits null)
-  if (kHitRecords) hits.reserve(lanes, "alloc hit records");
   occ.reserve((size_t)occ_words(h) * lanes, "alloc occlusion bits");
   sched.reserve((size_t)sched_words_for(tiles), "alloc tile schedule");
 }
 
 void WorkSet::bind(const rt_scene* s, const rt_camera& c, RenderParams& P) {
   reserve_tiles(s->host, (size_t)std::max(1, P.num_sel_tiles));
-  P.hits = hits.p;
   P.occ = occ.p;
   set_schedule(P, sched.p);
   if (s->needs_recursion) {
@@ -986,8 +968,7 @@ void render_multi_msaa(rt_scene* s, const CtxList& cx, int cam, float* d_frame, 
       if (row < 0 || row >= H) continue;
       RenderParams Q = make_params(s, r, cam, row, 1, 0, 1, 0, dst, nullptr);
       limit_rows(Q, 1);
-      Q.hits = P.hits;  // a halo row shares the band's buffers (it has no more tiles)
-      Q.occ = P.occ;
+      Q.occ = P.occ;  // a halo row shares the band's buffers (it has no more tiles)
       Q.frames = P.frames;
       set_schedule(Q, ws.sched.p);
       enqueue_samples(s, Q, n, ws.samples.p, x->stream, false);
@@ -1409,7 +1390,7 @@ void render_pinned(const HostFrame& f, RenderCtx* x, float* direct, CallCounters
   // block order: the frame is bound by its writes over PCIe, which the heavy-first (cold)
   // order scatters (0.674 -> 0.742 ms per C3 frame, profiles/r06/ab_dropin_cold.jsonl)
   P.tile_cost = nullptr;
-  P.pair_rows = RT_PAIR_ROWS;
+  P.pair_rows = 1;
   enqueue_frame(s, P, 1, nullptr, x->stream, true);
   counted.stop();
 }
@@ -2078,7 +2059,7 @@ int rt_render(rt_scene* s, int cam, int row0, int row_stride, float* out_rgb, rt
     const HostFrame f{s, cam, row0, row_stride, out_rgb};
     const bool one_pass = !s->multi && c.num_samples <= 1;  // one device, pixel-centre camera
     const int chunks = std::min(kRenderChunks, tp.tiles_total / tp.tiles_x);
-    float* direct = one_pass && RT_DIRECT_PINNED ? pinned_device_pointer(out_rgb) : nullptr;
+    float* direct = one_pass ? pinned_device_pointer(out_rgb) : nullptr;
     if (direct)
       render_pinned(f, lease.x[0], direct, counted);
     else if (one_pass && chunks > 1)

@@ -98,23 +98,15 @@ static_assert(sizeof(DevNode) == 64, "node must be one 64-byte scalar load");
 // exact decision (the treelet's guard box) is taken per ray in the leaf batch.  An invalid
 // slot holds NaN planes, which every slab test rejects.
 constexpr int32_t kWideTag = 1 << 30;
-// The culling nodes exist once per direction-sign octant (RT_OCTANT_NODES):
+// The culling nodes exist once per direction-sign octant (round 11, §4.3):
 // copy k = (1/d_x < 0) | (1/d_y < 0) << 1 | (1/d_z < 0) << 2 follows copy k - 1 at a stride of
 // HostScene::accel_stride node slots (RenderParams::accel_stride).  In copy k the slot words
 // box[c][x] of every axis x whose bit of k is set have their halves swapped — the ENTRY plane of
 // a ray of octant k is the low half of every word — and inner_base points into the same copy, so
 // a walk that starts at accel_root + k * stride stays in copy k.  leaf_base, kinds, offs and the
-// leaf records are the same in every copy.
-//   RT_OCTANT_NODES  0: no copies, the frame kernel orders the planes per lane (v_alignbit) like
-//                       every other kernel;  1 (A/B builds): the copies, walked per octant, with
-//                       the v_alignbit kept (shift 0);  2: the frame kernel reads the halves
-//                       as they lie.
-#ifndef RT_OCTANT_NODES
-#define RT_OCTANT_NODES 2
-#endif
-static_assert(RT_OCTANT_NODES >= 0 && RT_OCTANT_NODES <= 2, "RT_OCTANT_NODES: 0, 1 or 2");
-constexpr int kOctantNodes = RT_OCTANT_NODES;
-constexpr int kOctantCopies = kOctantNodes ? 8 : 1;
+// leaf records are the same in every copy.  The frame kernel walks a packet per octant and reads
+// the halves as they lie; every other kernel walks copy 0 and orders the planes per lane.
+constexpr int kOctantCopies = 8;
 // node slots a scene may have: the traversal loads a wide node at the 32-bit byte offset
 // (ref << 6) (rt_kernels.hip load_node8), so reference slots + kOctantCopies x culling slots
 // stay below 2^26 (about 22 M triangles with eight copies); a larger scene is refused
@@ -197,14 +189,6 @@ struct DevLight {
   float intensity[3];
   float pad[2];
 };
-
-// Primary-hit record, 8 B per pixel: x = DFS leaf index (-1 miss, -2 outside the image),
-// y = the bits of t.  As one little-endian u64 it is the key (t bits << 32) | leaf whose
-// minimum is the reference's (t, DFS leaf) rule (rt_kernels.hip, batch_flush).
-struct alignas(8) int2_t {
-  int32_t x, y;
-};
-
 
 enum RootKind : int32_t { kRootNode = 0, kRootTriangle = 1, kRootSphere = 2 };
 
@@ -332,20 +316,6 @@ struct PacketGeom {
   int packets;            // trace_packets
 };
 
-// What the frame kernel's phases hand to each other (RT_HANDOVER) and the shadow walk's guard
-// mode (RT_DEFER_SHADOW) are described where they are used, in rt_kernels.hip; their defaults
-// stand here because the host needs one consequence: whether a launch still carries the primary
-// hit records through RenderParams::hits.  It does not when the leaf stays in the wave's LDS key
-// (16), which takes the parked hit point (1) and a shadow walk that leaves the point's words alone.
-#ifndef RT_HANDOVER
-#define RT_HANDOVER (15 | 16 | 128)
-#endif
-#ifndef RT_DEFER_SHADOW
-#define RT_DEFER_SHADOW 0
-#endif
-constexpr bool kLeafInKey = (RT_HANDOVER & 17) == 17 && RT_DEFER_SHADOW == 0;
-constexpr bool kHitRecords = !kLeafInKey;
-
 struct RenderParams {
   const DevNode* nodes;
   const DevLeaf* leaves;  // culling-tree order (DevLeaf), FAST traversal
@@ -389,9 +359,7 @@ struct RenderParams {
   unsigned msaa_mul[2];
   unsigned long long msaa_seed;
   float* out;
-  // kHitRecords builds only (else null, the slot kept so that no other field moves):
-  // num_sel_tiles * 64 records {t bits, leaf}, primary phase -> shadow, shade
-  int2_t* hits;
+  void* reserved;  // always null (was the hit records; kept so that no other field moves)
   unsigned* occ;  // num_sel_tiles * 64 * occ_words light-occlusion bits: trace_shadow -> shade
   int occ_words;  // ceil(num_lights / 32)
   // heavy-first dispatch (null: off).  tile_cost[sel] holds each selected

@@ -272,9 +272,6 @@ __device__ __forceinline__ V3 tri_quotients(V3 n, float det, bool quot) {
 // normalize by its length, and a light's six diffuse and specular terms by d2.  The operand
 // range is tri_quotients': divisor in [2^-40, 2^40], numerators 0 or in [2^-49, 2^49]; the
 // range is tested per vector here, and any lane outside it takes `/`.
-// (RT_HANDOVER: the switches are described with the frame kernel's phases, below; its default is
-// rt_internal.h's)
-constexpr bool kShareRcp = (RT_HANDOVER & 8) != 0;
 __device__ __forceinline__ bool quot_divisor_ok(float d) {
   const float ad = __builtin_fabsf(d);
   return (ad >= 0x1p-40f) & (ad <= 0x1p40f);
@@ -305,7 +302,7 @@ __device__ __forceinline__ bool numerators_in_range(V3 n) {
 __device__ __forceinline__ V3 normalize_shared(V3 a, bool dead = false) {
   const float len = length(a);
   const bool in_range = normalize_in_range(a, len);
-  if (kShareRcp && (dead | in_range)) {
+  if (dead | in_range) {
     const float y1 = refined_rcp(len);
     return v3(quot_step(a.x, len, y1), quot_step(a.y, len, y1), quot_step(a.z, len, y1));
   }
@@ -317,7 +314,7 @@ __device__ __forceinline__ bool light_terms_in_range(V3 a, V3 b, float d2) {
 }
 // a / d2 and b / d2
 __device__ __forceinline__ void light_quotients(V3 a, V3 b, float d2, V3& qa, V3& qb) {
-  if (kShareRcp && light_terms_in_range(a, b, d2)) {
+  if (light_terms_in_range(a, b, d2)) {
     const float y1 = refined_rcp(d2);
     qa = v3(quot_step(a.x, d2, y1), quot_step(a.y, d2, y1), quot_step(a.z, d2, y1));
     qb = v3(quot_step(b.x, d2, y1), quot_step(b.y, d2, y1), quot_step(b.z, d2, y1));
@@ -588,8 +585,8 @@ __device__ __forceinline__ const key_word_t* key_words(const WaveLeafLds& L, int
   return reinterpret_cast<const key_word_t*>(&L.key[lane]);
 }
 // A shadow walk's commit: the owner's any-hit flag (any writer: same value).  HIGH: the flag is
-// the key's high word alone, and the low word — the frame kernel's primary leaf, kLeafInKey — is
-// left as it is (occluded KEEP).
+// the key's high word alone, and the low word — the frame kernel's primary leaf — is left as it
+// is (occluded KEEP).
 template <bool HIGH>
 __device__ __forceinline__ void set_shadow_flag(WaveLeafLds& L, int src) {
   if constexpr (HIGH)
@@ -670,6 +667,7 @@ template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP = true, bool CAMERA = 
           bool WHOLE = false, bool HIGH = false>
 __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L, int n,
                                            const LaneRay& r, float thr, Diag& dg) {
+  static_assert(!CULL || SHADOW, "a culling primary walk defers its guard (leaf_batches)");
   const int lane = lane_id();
   int base = 0;
   for (; WHOLE ? base + 64 <= n : base < n; base += 64) {
@@ -718,7 +716,7 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
         hit = tri_test(v0, v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), rr, t);
       else
         hit = sphere_test(v0, q1.x, rr, t);
-      DIAG(const bool sv = valid & hit & (t > 0.0f) & (SHADOW ? t < othr : t < RT_INF);
+      DIAG(const bool sv = valid & hit & (t > 0.0f) & (t < othr);
            dg.defer[kDfSurvivors] += __builtin_popcountll(ballot(sv));
            dg.defer[kDfRejected] += __builtin_popcountll(ballot(sv & !ok)));
       hit &= ok;
@@ -743,52 +741,25 @@ __device__ __forceinline__ int batch_flush(const RenderParams& P, WaveLeafLds& L
 // sphere test, and the survivors (hit, 0 < t, t in range) appended, compacted by their ballot,
 // to WaveLeafLds::sv.  Stage 2 (guard_batch), per kSurvivorCap survivors: the guard decision
 // exactly as batch_flush takes it, and the commit for the lanes it accepts.  The committed set
-// {guard ok, hit, in range} is the same, and neither atomicMin nor the any-hit flag depends on
-// the order.  The survivor count `ns` is wave-uniform and lives across the walk like `pending`.
-// Modes (A/B builds set them per walk): 0 the guard first, as batch_flush above; 1 deferred, every
-// flush drains its survivors (the last guard batch of a flush partial); 2 deferred, survivors wait
-// across flushes for a full batch and only the walk's last guard batch is partial (a shadow lane
-// with a waiting survivor stays `alive`, as one with a carried queue entry does).
-// Shipped: the primary walk 2, the shadow walk 0.  C3, same box, five interleaved rounds, frame
-// kernel / six in flight (profiles/r10/ab_defer.json): primary alone 0.3269 -> 0.3168 / 0.3063 ->
-// 0.2969 ms; shadow alone, mode 1 0.3270 / 0.3064 and mode 2 0.3259 / 0.3053, inside the
-// run-to-run range although no C3 shadow test survives — the shadow walk's time is its visits,
-// the batches fill their gaps.
-#ifndef RT_DEFER_PRIMARY
-#define RT_DEFER_PRIMARY 2
-#endif
-// (RT_DEFER_SHADOW's default, 0, is rt_internal.h's)
-static_assert((RT_DEFER_PRIMARY == 0 || RT_DEFER_PRIMARY == 2) && RT_DEFER_SHADOW >= 0 &&
-              RT_DEFER_SHADOW <= 2, "deferred-guard modes");
+// {guard ok, hit, in range} is the same, and atomicMin does not depend on the order.  The
+// survivor count `ns` is wave-uniform and lives across the walk like `pending`: survivors wait
+// across flushes for a full guard batch, and only the walk's last guard batch is partial.
+// The culling tree's primary walk runs this way; its shadow walk and the reference walks take the
+// guard first (batch_flush).  (Round 10 measured both walks in every mode: the primary walk gained
+// 3 %, the shadow walk nothing — DESIGN.md §4.5, profiles/r10/ab_defer.json.)
 
-// What the frame kernel's phases hand to each other instead of rebuilding it (round 13, DESIGN.md
-// §4.3).  A/B builds: -DRT_HANDOVER=<bits>; every value handed over is the expression the later
-// phase evaluated itself, so the frames are the same bits with any setting.
-//   1  the hit point p = e + d * t, computed where the primary walk ends and parked in LDS
-//   2  the last light's normalize(light - p) taken from its shadow ray
-//   4  the occlusion word kept in a register when there is one (occ_words == 1)
-//   8  the three quotients of a normalize, and of a light's terms by d2, share one reciprocal
-//      (kShareRcp, with tri_quotients above)
-//  16  the primary hit's leaf stays where the walk left it, in the low word of the lane's L.key
-//      (-1 a miss, -2 a lane outside the image or the packet), and no hit record goes through
-//      memory: the shadow walks keep their any-hit flag in the key's high word (occluded KEEP),
-//      which the parked point (1) has made free — without it the record's t is still needed,
-//      and the record path stays
-//      (32 was the material read with scalar loads when the packet's hit lanes agree on it:
-//      measured neutral, not kept)
-//  64  the last light's length(light - p) handed over with its direction (2): off in the shipped
-//      build — alone it measured inside the run-to-run range, DESIGN.md §4.3
-// 128  a walk lowers its priority where it leaves the visit loop, not between two visits
+// What the frame kernel's phases hand to each other instead of rebuilding it (rounds 13 and 14,
+// DESIGN.md §4.3); every value handed over is the expression the later phase evaluated itself.
+//   * the hit point p = e + d * t, computed where the primary walk ends and parked in LDS;
+//   * the primary hit's leaf, which stays where the walk left it, in the low word of the lane's
+//     L.key (-1 a miss, -2 a lane outside the image or the packet): the shadow walks keep their
+//     any-hit flag in the key's high word (occluded KEEP), which the parked point has made free;
+//   * the last light's normalize(light - p), taken from its shadow ray (ShadowHand);
+//   * the occlusion word, kept in a register when there is one (occ_words == 1).
 // The parked point waits in words of the wave's LDS block that are idle from the end of the
-// primary walk on: sv (x, y), which only a deferred-guard walk uses and which that walk drains
-// before it ends, and the junk words past the queue (z), which only the primary walk's pushes
-// write.  A shadow walk with a deferred guard would use sv: those builds rebuild the point.
-constexpr bool kParkPoint = (RT_HANDOVER & 1) != 0 && RT_DEFER_SHADOW == 0;
-constexpr bool kHandLight = (RT_HANDOVER & 2) != 0;
-constexpr bool kOccRegister = (RT_HANDOVER & 4) != 0;
-static_assert(kLeafInKey == ((RT_HANDOVER & 16) != 0 && kParkPoint), "rt_internal.h: kLeafInKey");
-constexpr bool kHandDist = (RT_HANDOVER & 64) != 0 && kHandLight;
-constexpr bool kPrioAtExit = (RT_HANDOVER & 128) != 0;
+// primary walk on: sv (x, y), which only the primary walk's deferred guard uses and which that
+// walk drains before it ends, and the junk words past the queue (z), which only the primary
+// walk's pushes write.
 __device__ __forceinline__ void park_point(WaveLeafLds& L, int lane, V3 p) {
   L.sv[lane] = ((unsigned long long)__float_as_uint(p.y) << 32) | __float_as_uint(p.x);
   L.q[kBatchCap + lane] = __float_as_uint(p.z);
@@ -801,7 +772,7 @@ __device__ __forceinline__ V3 parked_point(const WaveLeafLds& L, int lane) {
 
 // Stage 2: the guard decision of the first ns (<= kSurvivorCap) waiting survivors, one per lane,
 // and their commit.
-template <bool SHADOW, bool SKIP, bool CAMERA, bool HIGH = false>
+template <bool SKIP, bool CAMERA>
 __device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& L, int ns,
                                             const LaneRay& r, Diag& dg) {
   const int lane = lane_id();
@@ -838,26 +809,21 @@ __device__ __forceinline__ void guard_batch(const RenderParams& P, WaveLeafLds& 
   }
   DIAG(dg.defer[kDfGuardIters]++;
        dg.defer[kDfRejected] += __builtin_popcountll(ballot(valid & !ok)));
-  if (SHADOW) {
-    if (ok) set_shadow_flag<HIGH>(L, src);
-  } else if (ok) {
-    atomicMin(&L.key[src], (s & 0xffffffff00000000ull) | (unsigned)leaf);
-  }
+  if (ok) atomicMin(&L.key[src], (s & 0xffffffff00000000ull) | (unsigned)leaf);
 }
 
-// Stage 1 over the n queued tests (WHOLE: the whole 64-entry batches only, as batch_flush), the
-// guard batches that fill up on the way, and with DRAIN the survivors still waiting at the end.
+// Stage 1 over the n queued tests and the guard batches that fill up on the way.  WHOLE (a
+// mid-walk flush): the whole 64-entry batches only, as batch_flush, and the survivors still
+// waiting at the end stay; else (the walk's last flush) they are drained.
 // ns: survivors waiting, in and out.  Returns the number of queue entries run.
-template <bool SHADOW, bool SPHERES, bool SKIP, bool CAMERA, bool WHOLE, bool DRAIN,
-          bool HIGH = false>
+template <bool SPHERES, bool SKIP, bool CAMERA, bool WHOLE>
 __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveLeafLds& L, int n,
-                                                    int& nsurv, const LaneRay& r, float thr,
-                                                    Diag& dg) {
+                                                    int& nsurv, const LaneRay& r, Diag& dg) {
   const int lane = lane_id();
   int base = 0, ns = nsurv;
   for (;;) {
     const bool more = WHOLE ? base + 64 <= n : base < n;
-    if (!more && (!DRAIN || ns == 0)) break;
+    if (!more && (WHOLE || ns == 0)) break;
     bool late = false;  // this lane's survivor waits for the full buffer's guard batch
     int rank = 0;
     unsigned long long rec = 0ull;
@@ -875,7 +841,6 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
         rr.quot = __builtin_amdgcn_ds_bpermute(src << 2, (int)r.quot) != 0;
       }
       rr.d = v3(lane_f(src, r.d.x), lane_f(src, r.d.y), lane_f(src, r.d.z));
-      const float othr = SHADOW ? lane_f(src, thr) : 0.0f;
       // (the guard words q1.w and q2.w ride along unused; q[3] is not loaded)
       const f4* q = reinterpret_cast<const f4*>(P.leaves + idx);  // idle lanes: record 0, unused
       const f4 q0 = q[0], q1 = q[1], q2 = q[2];
@@ -886,7 +851,7 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
         hit = tri_test(v0, v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), rr, t);
       else
         hit = sphere_test(v0, q1.x, rr, t);
-      const bool surv = valid & hit & (t > 0.0f) & (SHADOW ? t < othr : t < RT_INF);
+      const bool surv = valid & hit & (t > 0.0f) & (t < RT_INF);
       DIAG(dg.guard += __builtin_popcountll(ballot(valid)));
       base += 64;
       const uint64_t sm = ballot(surv);
@@ -901,7 +866,7 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
       }
     }
     if (ns >= kSurvivorCap || !more) {
-      guard_batch<SHADOW, SKIP, CAMERA, HIGH>(P, L, ns < kSurvivorCap ? ns : kSurvivorCap, r, dg);
+      guard_batch<SKIP, CAMERA>(P, L, ns < kSurvivorCap ? ns : kSurvivorCap, r, dg);
       DIAG(dg.defer[kDfSplitDrains] += ns > kSurvivorCap);
       ns = ns > kSurvivorCap ? ns - kSurvivorCap : 0;
       if (late) L.sv[rank - kSurvivorCap] = rec;  // the buffer is empty again
@@ -911,17 +876,17 @@ __device__ __forceinline__ int batch_flush_deferred(const RenderParams& P, WaveL
   return base;
 }
 
-// The leaf batches of one flush, by the walk's mode (RT_DEFER_*): see above.
+// The leaf batches of one flush: the culling tree's primary walk defers its guard, every other
+// walk takes it first (or, the reference walk, has none).  ns: the primary walk's waiting
+// survivors; a shadow walk passes a counter that stays 0.
 template <bool SHADOW, bool SPHERES, bool CULL, bool SKIP, bool CAMERA, bool WHOLE,
           bool HIGH = false>
 __device__ __forceinline__ int leaf_batches(const RenderParams& P, WaveLeafLds& L, int n, int& ns,
                                             const LaneRay& r, float thr, Diag& dg) {
-  constexpr int mode = !CULL ? 0 : (SHADOW ? RT_DEFER_SHADOW : RT_DEFER_PRIMARY);
-  if constexpr (mode == 0)
-    return batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, WHOLE, HIGH>(P, L, n, r, thr, dg);
+  if constexpr (CULL && !SHADOW)
+    return batch_flush_deferred<SPHERES, SKIP, CAMERA, WHOLE>(P, L, n, ns, r, dg);
   else
-    return batch_flush_deferred<SHADOW, SPHERES, SKIP, CAMERA, WHOLE, !WHOLE || mode == 1, HIGH>(
-        P, L, n, ns, r, thr, dg);
+    return batch_flush<SHADOW, SPHERES, CULL, SKIP, CAMERA, WHOLE, HIGH>(P, L, n, r, thr, dg);
 }
 
 // A mid-walk flush (n >= 64 pending): the whole batches only; the n & 63 left-over entries move
@@ -999,7 +964,7 @@ __device__ __forceinline__ float half_hi(int w) {
 // so a slot costs 3 alignbit + 6 fma_mix + max3 + min3 + 2 compares instead of a min and a max
 // per axis on top (same values: the entry plane moved down, the exit plane up by |m|).  A
 // skipped axis (SKIP) gets S = 0 and planes -inf / +inf, once per visit.
-// COHERENT (the frame kernel, RT_OCTANT_NODES 2): the node belongs to the octant copy of every
+// COHERENT (the frame kernel's octant sub-walks): the node belongs to the octant copy of every
 // lane in `m` (octant_walks), whose words already hold the entry plane low — the same halves
 // reach the same fma_mix operands with no v_alignbit and no use of sh.
 template <bool SKIP, bool SHADOW, bool DEEP, bool SPHERES, bool COHERENT = false>
@@ -1066,13 +1031,7 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
       [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
       DIAG(dg.ev[kPhPairHits] += pair);
       // (the shadow kernel keeps the exec-mask pushes: junk writes cost it VGPR spills)
-#ifdef RT_PRIO_PUSH  // (A/B builds: the leaf pushes at another priority; +0.3 %, in the noise)
-      __builtin_amdgcn_s_setprio(RT_PRIO_PUSH);
-#endif
       batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
-#ifdef RT_PRIO_PUSH
-      __builtin_amdgcn_s_setprio(3);  // (RT_PRIO_V)
-#endif
       DIAG(dg.leaves += 1 + pair; dg.leaf_lanes += (1 + pair) * __builtin_popcountll(hm));
       continue;
     }
@@ -1120,12 +1079,12 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
 // The reference's (t, leaf) for every active ray: leaf < 0 = miss.  FAST: the 8-wide culling
 // tree over reference treelets (the launch takes it only when the scene has one); otherwise
 // the reference tree itself.  CAMERA: all rays share one origin (batch_flush).
-// OCT != 0 (FAST only; the frame kernel's octant_walks): one sub-walk of a packet — the active
-// lanes share direction-sign octant k and the walk starts at that octant's copy of the culling
-// nodes, accel_root + root_off (root_off = k * accel_stride).  The caller presets every lane's
-// L.key and reads the packet's result from it after the last sub-walk; best_t and
-// best_leaf are not set.  OCT == 2: the copy's plane order is read as it lies (visit_wide COHERENT).
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false, int OCT = 0>
+// OCT (FAST only; the frame kernel's octant_walks): one sub-walk of a packet — the active lanes
+// share direction-sign octant k and the walk starts at that octant's copy of the culling nodes,
+// accel_root + root_off (root_off = k * accel_stride), whose plane order is read as it lies
+// (visit_wide COHERENT).  The caller presets every lane's L.key and reads the packet's result
+// from it after the last sub-walk; best_t and best_leaf are not set.
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false, bool OCT = false>
 __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode* __restrict__ nodes,
                                             int* spill, WaveLeafLds& L, const LaneRay& r,
                                             bool active, float& best_t, int& best_leaf, Diag& dg,
@@ -1163,9 +1122,10 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
   if (!OCT) L.key[lane] = kNoHitKey;
   int node = FAST ? P.accel_root + root_off : P.root_ref;
-  // (the frame kernel's walks: the visits' priority is set once and after each flush, and lowered
-  // where the walk leaves the loop — no s_setprio pair between two visits that no flush separates)
-  constexpr bool kAtExit = kPrioAtExit && OCT != 0;
+  // (an octant sub-walk: the visits' priority is set once and after each flush, and lowered where
+  // the walk leaves the loop — no s_setprio pair between two visits that no flush separates,
+  // DESIGN.md §4.3 round 14; every other walk keeps the pair around each visit)
+  constexpr bool kAtExit = OCT;
   if (kAtExit) RT_PRIO_VISIT_BEGIN;
   for (;;) {
     if (pending >= kBatchFlush) {  // between visits: only the ray and the stack are live
@@ -1182,8 +1142,7 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
       if (!kAtExit) RT_PRIO_VISIT_BEGIN;
       const bool more =
-          visit_wide<SKIP, false, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, ~0ull,
-                                                           st, dg);
+          visit_wide<SKIP, false, DEEP, SPHERES, OCT>(P, nodes, L, pending, r, node, m, ~0ull, st, dg);
       if (!kAtExit) RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
@@ -1220,11 +1179,11 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
 // ------------------------------------------------------------------ shadow (any hit)
 // Occluded iff some leaf the ray may reach has 0 < t < thr — identical to the reference's
 // closest-hit shadow test `0 < t_closest < dist - eps` (HW2/Scene.cpp:123-127), appendix A.7.
-// OCT != 0: one sub-walk of a packet, as in closest_hit — the caller clears every lane's L.key
+// OCT: one sub-walk of a packet, as in closest_hit — the caller clears every lane's L.key
 // and reads it after the last sub-walk; the value returned then covers the lanes walked so far.
-// KEEP (the frame kernel, kLeafInKey): the flag is the key's high word alone — cleared, tested and
+// KEEP (the frame kernel): the flag is the key's high word alone — cleared, tested and
 // returned — and the low word, the lane's primary leaf, is left as it is.
-template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, int OCT = 0, bool KEEP = false>
+template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool OCT = false, bool KEEP = false>
 __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          int* spill, WaveLeafLds& L, const LaneRay& r, bool active,
                                          float thr, Diag& dg, int root_off = 0) {
@@ -1251,7 +1210,9 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
   const int lane = lane_id();
   WaveStack<DEEP> st;
   st.lds = spill;
-  int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
+  // (waiting: the survivor count the shared flush helpers take by reference; a shadow walk has no
+  // deferred guard, so it stays 0 — kept because the shipped listing changes without it)
+  int pending = 0, waiting = 0;  // queued tests (wave-uniform)
   if (!OCT) {
     unsigned long long clear = 0ull;
     asm volatile("" : "+v"(clear));  // a fresh zero here, not one kept (and spilled) across the walk
@@ -1261,7 +1222,7 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
       L.key[lane] = clear;
   }
   int node = FAST ? P.accel_root + root_off : P.root_ref;
-  constexpr bool kAtExit = kPrioAtExit && OCT != 0;  // (as in closest_hit)
+  constexpr bool kAtExit = OCT;  // (as in closest_hit)
   if (kAtExit) RT_PRIO_VISIT_BEGIN;
   for (;;) {
     if (pending >= kShadowFlush) {  // between visits; a lane found occluded stops entering nodes
@@ -1281,8 +1242,7 @@ __device__ __forceinline__ bool occluded(const RenderParams& P, const DevNode* _
       DIAG(const unsigned long long tv0 = clock_now(); dg.ev[kPhVisits]++);
       if (!kAtExit) RT_PRIO_VISIT_BEGIN;
       const bool more =
-          visit_wide<SKIP, true, DEEP, SPHERES, OCT == 2>(P, nodes, L, pending, r, node, m, alive,
-                                                          st, dg);
+          visit_wide<SKIP, true, DEEP, SPHERES, OCT>(P, nodes, L, pending, r, node, m, alive, st, dg);
       if (!kAtExit) RT_PRIO_VISIT_END;
       DIAG(dg.cyc_visit += clock_now() - tv0);
       if (!more) break;
@@ -1325,11 +1285,11 @@ __device__ __forceinline__ const RenderParams& fresh_params(const RenderParams& 
 
 // ------------------------------------------------------------------ render kernels
 // Three phases per packet (trace_frame_kernel): the primary phase finds each pixel's closest
-// hit and leaves its leaf and its point in the wave's LDS block (a kHitRecords build: an 8-byte
-// {t, leaf} record in memory); the shadow phase traces the point-light shadow rays from the hit
-// point into occlusion bits; the shading phase runs the point-light loop.  Going through LDS (or
-// the records) keeps each phase's live state small (occupancy is what hides the dependent node
-// loads).
+// hit and leaves its leaf and its point in the wave's LDS block; the shadow phase traces the
+// point-light shadow rays from the hit point into occlusion bits; the shading phase runs the
+// point-light loop.  Going through LDS keeps each phase's live state small (occupancy is what
+// hides the dependent node loads).  (Until round 14 an 8-byte {t, leaf} record per pixel went
+// through memory instead)
 //
 // A packet is normally one wave's 64 lanes = the tile's 8x8 pixels.  A heavy tile can instead
 // be split over four waves (sub = 0..3: wave `sub` takes quadrant `sub` of the tile, 4x4 pixels
@@ -1446,10 +1406,15 @@ __device__ __forceinline__ unsigned long long* counter_row(const RenderParams& P
   return P.counters + kCounterWidth * (sel % kCounterSlots);
 }
 
-__device__ __forceinline__ float hit_t(int2_t rec) { return __int_as_float(rec.y); }
+// What the shading phase reads back of the primary hit: x = the leaf (-1 miss, -2 outside the
+// image), y = 0 since the point is parked (it was the bits of t).  (The shape the memory record
+// had until round 14; shade_pixel keeps it because the shipped listing changes with a plain int.)
+struct alignas(8) int2_t {
+  int32_t x, y;
+};
 __device__ __forceinline__ int hit_leaf(int2_t rec) { return rec.x; }
 
-// The frame kernel's walks over the octant copies of the culling nodes (RT_OCTANT_NODES,
+// The frame kernel's walks over the octant copies of the culling nodes (kOctantCopies,
 // rt_internal.h).  A lane's octant is the sign of its three reciprocals — per axis exactly the
 // predicate behind LaneRay::sh, so +-0 and skipped axes fall where the per-lane order puts them
 // (a skipped axis has S = 0 and planes at -+inf: either copy gives the same distances).
@@ -1476,18 +1441,9 @@ __device__ __forceinline__ void octant_walks(const LaneRay& r, bool active, Diag
     walk(mine, k);
   }
 }
-// (A/B builds) RT_OCTANT_NODES 1: the walk keeps its v_alignbit with a shift of 0 — the copy
-// already holds the octant's order — in three VGPRs the compiler cannot fold.
-__device__ __forceinline__ void octant_shifts_zero(LaneRay& r) {
-  r.sh0 = r.sh1 = r.sh2 = 0;
-  asm volatile("" : "+v"(r.sh0), "+v"(r.sh1), "+v"(r.sh2));
-}
 
-// One wave = the 8x8 packet of selected tile `sel` (< num_sel_tiles): closest hit per pixel
-// into its 8-B record.
-#ifndef RT_CAMERA_ORIGIN  // (A/B builds: 0 = the leaf batch fetches the owner's origin here too)
-#define RT_CAMERA_ORIGIN 1
-#endif
+// One wave = the 8x8 packet of selected tile `sel` (< num_sel_tiles): closest hit per pixel, its
+// leaf into the lane's key and its point parked beside it.
 template <bool FAST, bool DEEP, bool SPHERES>
 __device__ __forceinline__ void primary_packet(const RenderParams& P,
                                                const DevNode* __restrict__ nodes, int sel,
@@ -1503,46 +1459,37 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   Diag dg;
   float t;
   int leaf;
-  // (CAMERA: every lane's origin is cam_e, so the leaf batch fetches no owner origin)
-  constexpr bool kCam = RT_CAMERA_ORIGIN != 0;
+  // (CAMERA = true: every lane's origin is cam_e, so the leaf batch fetches no owner origin)
   DIAG(const unsigned long long s1 = clock_now());
-  if constexpr (FAST && kOctantNodes != 0) {
-    if (kOctantNodes == 1) octant_shifts_zero(ray);
+  if constexpr (FAST) {  // the culling tree: one sub-walk per octant present in the packet
     L.key[lane_id()] = kNoHitKey;
     octant_walks(ray, q.valid, dg, [&](bool mine, int k) {
       const int off = k * P.accel_stride;
       if (ballot(mine && any_skip))
-        closest_hit<true, FAST, DEEP, SPHERES, kCam, kOctantNodes>(P, nodes, spill, L, ray, mine, t,
-                                                                   leaf, dg, off);
+        closest_hit<true, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, ray, mine, t, leaf,
+                                                           dg, off);
       else
-        closest_hit<false, FAST, DEEP, SPHERES, kCam, kOctantNodes>(P, nodes, spill, L, ray, mine, t,
-                                                                    leaf, dg, off);
+        closest_hit<false, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, ray, mine, t, leaf,
+                                                            dg, off);
     });
     const unsigned long long key = L.key[lane_id()];
     t = __uint_as_float((unsigned)(key >> 32));
     leaf = (int)(unsigned)key;
-  } else if (ballot(any_skip)) {
-    closest_hit<true, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+  } else if (ballot(any_skip)) {  // the reference traversal
+    closest_hit<true, FAST, DEEP, SPHERES, true>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   } else {
-    closest_hit<false, FAST, DEEP, SPHERES, kCam>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
+    closest_hit<false, FAST, DEEP, SPHERES, true>(P, nodes, spill, L, ray, q.valid, t, leaf, dg);
   }
   DIAG(const unsigned long long s2 = clock_now());
-  // hit_point's e + d * t while d and t are in registers; the later phases read it back (a miss
-  // parks inf or NaN, which nobody reads)
-  if constexpr (kParkPoint) park_point(L, lane_id(), ray.o + ray.d * t);
+  // the hit point e + d * t (Ray::point_at, HW2/Scene.cpp:101) while d and t are in registers; the
+  // later phases read it back (a miss parks inf or NaN, which nobody reads)
+  park_point(L, lane_id(), ray.o + ray.d * t);
   const RenderParams& Pw = fresh_params(P);  // post-traversal fields: not live across it
   const PacketPixel qw = wave_pixel(Pw, L);  // (recomputed, not kept)
-  int2_t rec;  // key layout: leaf low, t bits high (rt_internal.h)
-  rec.x = qw.valid ? leaf : -2;  // -1 miss, -2 outside the image
-  rec.y = __float_as_int(t);
-  if constexpr (kLeafInKey) {
-    // The later phases read the leaf from the low word of this lane's key.  Written by every
-    // lane: a walk that found nothing to enter (or a root primitive) never set the key, and a
-    // lane outside the image, or of a quadrant wave outside the packet, holds -2.
-    key_words(L, lane_id())[0] = (unsigned)rec.x;
-  } else if (qw.own) {
-    Pw.hits[(size_t)sel * (kTile * kTile) + qw.lane] = rec;
-  }
+  // The later phases read the leaf from the low word of this lane's key (-1 a miss).  Written by
+  // every lane: a walk that found nothing to enter (or a root primitive) never set the key, and a
+  // lane outside the image, or of a quadrant wave outside the packet, holds -2.
+  key_words(L, lane_id())[0] = (unsigned)(qw.valid ? leaf : -2);
   const unsigned long long nvalid = __builtin_popcountll(ballot(qw.valid));  // (all lanes)
   const unsigned long long nhit = __builtin_popcountll(ballot(qw.valid && leaf >= 0));
   if (Pw.counters && lane_id() == 0) {  // spread over kCounterSlots rows: no hot address
@@ -1572,18 +1519,11 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   }
 }
 
-// Hit point and normal of a primary hit, rebuilt from its {t, leaf} record exactly as
-// trace_ray computes them (HW2/Scene.cpp:101-105; Sphere.h:42,50 for sphere normals).
-__device__ __forceinline__ V3 hit_point(const RenderParams& P, const PacketPixel& q, float t) {
-  return ld3(P.cam_e) + primary_dir(P, q.px, q.py) * t;  // Ray::point_at = o + t*d
-}
-
 // What the shadow phase leaves in registers for the shading phase (nothing of it is live across
-// a walk that follows: `wi`, `dist` and `bits` are each written after their walk; `dist`, which
-// the walk itself does not use, is live through its own light's walk).
+// a walk that follows: `wi` and `bits` are each written after their walk).  (The last light's
+// length(light - p) handed over as well measured inside the run-to-run range: DESIGN.md §4.3.)
 struct ShadowHand {
   V3 wi = {0.0f, 0.0f, 0.0f};  // the last light's normalize(light - p)
-  float dist = 0.0f;           // ... and its length(light - p) (kHandDist)
   unsigned bits = 0;           // the last occlusion word (the only one when occ_words == 1)
 };
 
@@ -1599,9 +1539,8 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
     unsigned bits = 0;
     const int lend = min(P0.num_lights, 32 * (w + 1));
     for (int li = 32 * w; li < lend; li++) {
-      // per light: the pixel's hit record is re-read and its hit point read back from the wave's
-      // LDS block (park_point), so nothing but the occlusion bits is live across the traversal
-      // (register pressure, not traffic: the 8-B record is an L2 hit)
+      // per light: the pixel's leaf and its hit point are read back from the wave's LDS block
+      // (park_point), so nothing but the occlusion bits is live across the traversal
       DIAG(const unsigned long long s0 = clock_now());
       const RenderParams& P = fresh_params(P0);
       const DevLight& lt = lights[li];
@@ -1610,17 +1549,10 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       int sel_l = sel;
       asm volatile("" : "+s"(sel_l));
       const int lane_l = fresh_lane();
-      bool hit;
+      // the leaf in the lane's key: -1 a miss, -2 no pixel of the frame
+      const bool hit = (int)key_words(L, lane_l)[0] >= 0;
       V3 pk = v3(0, 0, 0);
-      if constexpr (kLeafInKey) {  // the leaf in the lane's key: -1 a miss, -2 no pixel of the frame
-        hit = (int)key_words(L, lane_l)[0] >= 0;
-        if (hit) pk = parked_point(L, lane_l);
-      } else {
-        const PacketPixel q = wave_pixel(P, L, lane_l);
-        const int2_t rec = P.hits[(size_t)sel_l * (kTile * kTile) + q.lane];
-        hit = q.own && hit_leaf(rec) >= 0;
-        if (hit) pk = kParkPoint ? parked_point(L, lane_l) : hit_point(P, q, hit_t(rec));
-      }
+      if (hit) pk = parked_point(L, lane_l);
       if (li == 0 && P.counters) {  // the packet's shadow rays: every light's are these lanes'
         const unsigned long long nhit = __builtin_popcountll(ballot(hit));
         if (lane_l == 0)
@@ -1634,34 +1566,29 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       const bool any_skip = hit && (sr.skip0 || sr.skip1 || sr.skip2);
       bool occ;
       DIAG(const unsigned long long s1 = clock_now());
-      if constexpr (FAST && kOctantNodes != 0) {
-        if (kOctantNodes == 1) octant_shifts_zero(sr);
+      if constexpr (FAST) {  // (KEEP: the walks use the key's flag word only)
         unsigned long long clear = 0ull;
         asm volatile("" : "+v"(clear));  // (a fresh zero, as in occluded)
-        if constexpr (kLeafInKey)  // the flag word only: the leaf below it stays for the shading
-          key_words(L, lane_l)[1] = (unsigned)clear;
-        else
-          L.key[lane_l] = clear;
+        key_words(L, lane_l)[1] = (unsigned)clear;  // the leaf below it stays for the shading
         octant_walks(sr, hit, dg, [&](bool mine, int k) {
           const int off = k * P.accel_stride;
           if (ballot(mine && any_skip))
-            occluded<true, FAST, DEEP, SPHERES, kOctantNodes, kLeafInKey>(P, nodes, spill, L, sr,
-                                                                          mine, thr, dg, off);
+            occluded<true, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, sr, mine, thr, dg,
+                                                            off);
           else
-            occluded<false, FAST, DEEP, SPHERES, kOctantNodes, kLeafInKey>(P, nodes, spill, L, sr,
-                                                                           mine, thr, dg, off);
+            occluded<false, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, sr, mine, thr, dg,
+                                                             off);
         });
-        occ = kLeafInKey ? key_words(L, fresh_lane())[1] != 0u : L.key[fresh_lane()] != 0ull;
-      } else {
-        occ = ballot(any_skip) ? occluded<true, FAST, DEEP, SPHERES, 0, kLeafInKey>(
+        occ = key_words(L, fresh_lane())[1] != 0u;
+      } else {  // the reference traversal
+        occ = ballot(any_skip) ? occluded<true, FAST, DEEP, SPHERES, false, true>(
                                      P, nodes, spill, L, sr, hit, thr, dg)
-                               : occluded<false, FAST, DEEP, SPHERES, 0, kLeafInKey>(
+                               : occluded<false, FAST, DEEP, SPHERES, false, true>(
                                      P, nodes, spill, L, sr, hit, thr, dg);
       }
       DIAG(const unsigned long long s2 = clock_now());
       bits |= (occ ? 1u : 0u) << (li - 32 * w);
-      if constexpr (kHandLight) hand.wi = sr.d;  // (the last light's is the one that stays)
-      if constexpr (kHandDist) hand.dist = dist;
+      hand.wi = sr.d;  // (the last light's is the one that stays)
       DIAG(dg.cyc_setup += s1 - s0);
       DIAG(dg.cyc_walk += s2 - s1);
     }
@@ -1672,7 +1599,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
     const int pl = pixel_lane(fresh_lane(), wave_sub(L));
     // a lone occlusion word goes to the shading in a register; nothing else reads P.occ
     hand.bits = bits;
-    if (pl >= 0 && !(kOccRegister && Pw.occ_words == 1))
+    if (pl >= 0 && Pw.occ_words != 1)
       Pw.occ[((size_t)sel_w * (kTile * kTile) + pl) * Pw.occ_words + w] = bits;
     DIAG(dg.cyc_tail += clock_now() - s3);
   }
@@ -1729,7 +1656,7 @@ __device__ __forceinline__ V3 shade_hit(const RenderParams& P, const DevPrim* __
                                         const DevMaterial* __restrict__ mats,
                                         const DevLight* __restrict__ lights, int leaf, V3 p,
                                         Occ occluded, int hand_li = -1,
-                                        V3 hand_wi = {0.0f, 0.0f, 0.0f}, float hand_dist = 0.0f,
+                                        V3 hand_wi = {0.0f, 0.0f, 0.0f},
                                         unsigned long long* loads_done = nullptr) {
   (void)loads_done;  // (RT_DIAG: the time at which the normal and the material are back)
   V3 color = v3(0.0f, 0.0f, 0.0f);
@@ -1751,10 +1678,9 @@ __device__ __forceinline__ V3 shade_hit(const RenderParams& P, const DevPrim* __
     if (occluded(li)) continue;
     const DevLight& Lt = lights[li];
     const V3 ld = ld3(Lt.position) - p;
-    // hand_li (wave-uniform, the frame kernel's last light): the caller holds normalize(ld),
-    // and with kHandDist length(ld)
+    // hand_li (wave-uniform, the frame kernel's last light): the caller holds normalize(ld)
     const V3 wi = li == hand_li ? hand_wi : normalize_shared(ld);
-    const float dist = kHandDist && li == hand_li ? hand_dist : length(ld);
+    const float dist = length(ld);
     const V3 I = ld3(Lt.intensity);
     const float d2 = dist * dist;
     const float cos_d = dot(n, wi);
@@ -1778,13 +1704,10 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
   const PacketPixel q = wave_pixel(P, L);  // (pair_rows: never a quadrant wave, L.sub is -1)
   const size_t pix = (size_t)sel * (kTile * kTile) + q.lane;
   DIAG(const unsigned long long s0 = clock_now());
+  // the leaf waits in the lane's key (-1 a miss, -2 no pixel); t went into the parked point
   int2_t rec;
-  if constexpr (kLeafInKey) {  // the leaf waits in the lane's key; t went into the parked point
-    rec.x = (int)key_words(L, lane_id())[0];
-    rec.y = 0;
-  } else {
-    rec = P.hits[pix];
-  }
+  rec.x = (int)key_words(L, lane_id())[0];
+  rec.y = 0;
 #ifdef RT_DIAG
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec.x), "+v"(rec.y) : : "memory");
   const unsigned long long s1 = clock_now();
@@ -1793,7 +1716,7 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
   const bool valid = q.own && hit_leaf(rec) != -2;
   const bool hit = q.own && hit_leaf(rec) >= 0;
   // a lone occlusion word is the shadow phase's register (0 without lights: no shadow phase)
-  const bool occ_reg = kOccRegister && P.occ_words == 1;
+  const bool occ_reg = P.occ_words == 1;
   if (P.records) {  // RT_TILE_RECORDS: the pixel record instead of its colour (rt_resolve_*)
     if (!q.own || (!P.tile_major && !valid)) return;
     unsigned r = kRecOutside;
@@ -1810,14 +1733,14 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
   V3 color = v3(0.0f, 0.0f, 0.0f);
   if (hit) {
     const unsigned* occ = P.occ + pix * P.occ_words;
-    const V3 p = kParkPoint ? parked_point(L, lane_id()) : hit_point(P, q, hit_t(rec));
+    const V3 p = parked_point(L, lane_id());
     color = shade_hit<SPHERES>(
         P, prims, normals, mats, lights, hit_leaf(rec), p,
         [&](int li) {
           const unsigned word = occ_reg ? hand.bits : occ[li >> 5];
           return ((word >> (li & 31)) & 1u) != 0;
         },
-        kHandLight ? P.num_lights - 1 : -1, hand.wi, hand.dist
+        P.num_lights - 1, hand.wi
 #ifdef RT_DIAG
         , &s2
 #endif
@@ -1863,6 +1786,9 @@ __device__ __forceinline__ void shade_pixel(const RenderParams& P,
 // unit, tx even) instead leave their colours in their waves' LDS; the second wave to arrive
 // writes both tiles as 8 rows of 192 B — whole 64-B lines, 16-B stores.  (Same values, same
 // pixels: only who stores them changes.)
+// (launch_variant takes pair_rows only with two-wave workgroups; RT_TRACE_WAVES 1 and 4 still build)
+static_assert(kTraceWaves != 2 || (kBlockW == 2 && kBlockH == 1),
+              "pair_write: a workgroup is two tiles of one tile row");
 __device__ __forceinline__ void pair_write(const RenderParams& P, WaveLeafLds* lds, int* arrived) {
   __threadfence_block();  // this wave's staged colours before its arrival
   int first = 0;
@@ -2457,7 +2383,7 @@ __device__ unsigned long long g_timeline[2][kTimelineWaves][3];
 // which keeps the register state of the three phases apart; the hit's leaf and point wait in the
 // wave's LDS block (a lane is the same pixel's in every phase, in a quadrant wave too), and the
 // last light's direction and a lone occlusion word stay in registers from the last shadow walk on
-// (RT_HANDOVER).  tile_cost: the whole packet's time.
+// (ShadowHand).  tile_cost: the whole packet's time.
 template <bool FAST, bool DEEP, bool SPHERES>
 __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_frame_kernel(
     RenderParams P, const DevNode* __restrict__ nodes, const DevLight* __restrict__ lights,
@@ -2585,9 +2511,6 @@ constexpr size_t deep_lds_bytes(int waves) {
 #ifndef RT_ORDER_MIN_TILES  // launches selecting fewer tiles run in block order (no order kernel)
 #define RT_ORDER_MIN_TILES 0
 #endif
-#ifndef RT_ORDER_SPLIT  // (A/B builds: 0 = no heavy-tile split)
-#define RT_ORDER_SPLIT 1
-#endif
 static bool order_geometry(RenderParams& T, PacketGeom& G, int& tblocks, int& per_region) {
   // 2-D blocks of tiles for a selection of whole tile rows: the whole frame, or a row band
   // (dist_tiles.BandPlan: tiles tile_begin .. tile_begin + num_sel_tiles - 1)
@@ -2609,7 +2532,7 @@ static bool order_geometry(RenderParams& T, PacketGeom& G, int& tblocks, int& pe
   per_region = ((chunks + T.order_regions - 1) / T.order_regions) * T.order_chunk;
   // room for order_split units per region listed quadrant group by quadrant group
   const int region_tiles = per_region * kTraceWaves;
-  T.order_split = RT_ORDER_SPLIT && region_tiles <= RT_SPLIT_MAX_TILES
+  T.order_split = region_tiles <= RT_SPLIT_MAX_TILES
                       ? max(1, min(kMaxSplit, region_tiles / RT_SPLIT_DIV) / kTraceWaves) : 0;
   T.order_stride = per_region + (kQuadrants - 1) * T.order_split;
   // the order lists end below the cost snapshot (sched layout: rt_internal.h sched_words_for)
@@ -2808,10 +2731,8 @@ __device__ __forceinline__ V3 resolve_pixel(const RenderParams& P, unsigned rec,
 }
 
 // rt_resolve_rows: row-major pixel records (a row band's, received whole) into the row-major
-// frame, rows [row_begin, row_end) of the camera's own frame; one thread per pixel.
-#ifndef RT_RESOLVE_PATCH  // (A/B builds: 0 = 256 consecutive pixels of a row per workgroup)
-#define RT_RESOLVE_PATCH 1
-#endif
+// frame, rows [row_begin, row_end) of the camera's own frame; one thread per pixel, a patch of
+// pixels per workgroup (256 consecutive pixels of a row measured slower).
 #ifndef RT_RESOLVE_PW  // patch width (A/B builds); height 256 / width
 #define RT_RESOLVE_PW 32
 #endif
@@ -2819,17 +2740,10 @@ constexpr int kResolvePW = RT_RESOLVE_PW, kResolvePH = 256 / RT_RESOLVE_PW;
 template <bool SPHERES>
 __global__ __launch_bounds__(256) void resolve_rows_kernel(RenderParams P, const unsigned* rec,
                                                            int row_begin, int row_end) {
-#if RT_RESOLVE_PATCH
   // a 32 x 8 patch of pixels per workgroup: neighbouring rows' hits share primitives
   const int px = (int)blockIdx.x * kResolvePW + (int)(threadIdx.x % kResolvePW);
   const long long py = row_begin + (long long)blockIdx.y * kResolvePH + (threadIdx.x / kResolvePW);
   if (px >= P.width || py >= row_end) return;
-#else
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long py = row_begin + i / P.width;
-  if (py >= row_end) return;
-  const int px = (int)(i % P.width);
-#endif
   const size_t pix = (size_t)py * P.width + px;
   const V3 color = resolve_pixel<SPHERES>(P, rec[pix], px, (int)py);
   float* o = P.out + 3 * pix;
@@ -2842,9 +2756,8 @@ hipError_t launch_resolve_rows(const RenderParams& P, const unsigned* rec, int r
                                int row_end, bool spheres, hipStream_t stream) {
   const long long n = (long long)(row_end - row_begin) * P.width;
   if (n <= 0) return hipSuccess;
-  const dim3 grid = RT_RESOLVE_PATCH ? dim3((unsigned)((P.width + kResolvePW - 1) / kResolvePW),
-                                            (unsigned)((row_end - row_begin + kResolvePH - 1) / kResolvePH))
-                                     : dim3((unsigned)((n + 255) / 256));
+  const dim3 grid((unsigned)((P.width + kResolvePW - 1) / kResolvePW),
+                  (unsigned)((row_end - row_begin + kResolvePH - 1) / kResolvePH));
   if (spheres)
     hipLaunchKernelGGL(resolve_rows_kernel<true>, grid, dim3(256), 0, stream, P, rec, row_begin, row_end);
   else
@@ -3381,8 +3294,8 @@ __global__ __launch_bounds__(256) void quot_check_vec_kernel(unsigned long long 
   }
   atomicAdd(&counts[0], bad);
   atomicAdd(&counts[1], n);
-  atomicAdd(&counts[2], kShareRcp ? shared : 0ull);
-  atomicAdd(&counts[3], kShareRcp ? plain : shared + plain);
+  atomicAdd(&counts[2], shared);
+  atomicAdd(&counts[3], plain);
 }
 
 hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,

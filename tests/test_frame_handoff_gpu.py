@@ -1,5 +1,5 @@
 """The primary hit stays on chip across the frame kernel's three phases (rt_kernels.hip
-RT_HANDOVER 16): the leaf waits in the low word of the lane's key in the
+primary_packet / shadow_packet / shade_pixel): the leaf waits in the low word of the lane's key in the
 wave's LDS block (-1 a miss, -2 a lane outside the image or the packet), the shadow walks keep
 their any-hit flag in the key's high word, and no hit record goes through memory.  Every frame
 must be the oracle's, bit for bit, in both traversals.
