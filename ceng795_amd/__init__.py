@@ -13,14 +13,18 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
     film = Film(scene, width, height)                # Pixel[w*h] on the GPU for the caller's samples
     film.shade_rays(origins, directions, xy)         # trace, shade and splat (Scene.cpp:51-62)
     image = film.resolve()                           # Pixel::get_color
+    scene = Scene("scene.xml", smooth=True)          # <Mesh shadingMode="smooth"> honoured (HW3)
+    attr = scene.hit_attributes(origins, directions, hits)  # beta, gamma, uv, both normals
 
 Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 """
 from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, RADIANCE_DTYPE,  # noqa: F401
-                    LIGHT_SAMPLE_DTYPE, pack_rays, host_leaf_objects)
+                    LIGHT_SAMPLE_DTYPE, HIT_ATTR_DTYPE, pack_rays, host_leaf_objects,
+                    host_vertex_normals, host_mesh_smooth)
 from .film import Film  # noqa: F401
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
 __all__ = ["Scene", "Film", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_FAST",
-           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "LIGHT_SAMPLE_DTYPE", "pack_rays",
-           "host_leaf_objects"]
+           "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "LIGHT_SAMPLE_DTYPE",
+           "HIT_ATTR_DTYPE", "pack_rays", "host_leaf_objects", "host_vertex_normals",
+           "host_mesh_smooth"]

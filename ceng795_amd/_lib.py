@@ -99,6 +99,20 @@ class rt_light_sample(C.Structure):
                 ("normal", F3), ("pad2", C.c_float)]
 
 
+class rt_surface_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("mesh_smooth", C.POINTER(C.c_ubyte)),
+                ("vertex_normals", C.POINTER(C.c_float)), ("vertex_uv", C.POINTER(C.c_float))]
+
+
+RT_ATTR_HIT, RT_ATTR_TRIANGLE, RT_ATTR_SMOOTH = 1, 2, 4  # rt_hit_attr::flags
+
+
+class rt_hit_attr(C.Structure):
+    _fields_ = [("beta", C.c_float), ("gamma", C.c_float), ("uv", C.c_float * 2),
+                ("shading_normal", F3), ("flags", C.c_int),
+                ("geometric_normal", F3), ("pad", C.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/ceng795_rt.h one to one
 SIGNATURES = {
     "rt_scene_create": (C.c_int, [C.POINTER(rt_scene_desc), C.c_int, C.POINTER(C.c_void_p)]),
@@ -203,6 +217,16 @@ SIGNATURES = {
                                                 C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rt_film_shade_rays_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
                                          C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_stats)]),
+    "rt_surface_version": (C.c_int, []),
+    "rt_scene_create_surface": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_surface_desc),
+                                          C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_scene_load_xml_surface": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_scene_has_smooth": (C.c_int, [C.c_void_p]),
+    "rt_host_vertex_normals_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(C.c_float)]),
+    "rt_host_mesh_smooth_xml": (C.c_int, [C.c_char_p, C.POINTER(C.c_ubyte), C.c_int]),
+    "rt_hit_attributes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                           C.c_void_p, C.c_void_p]),
+    "rt_hit_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
 }
 
 _lib = None

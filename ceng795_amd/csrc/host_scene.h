@@ -53,7 +53,19 @@ struct HostScene {
   std::vector<DevLeaf> leaves;        // culling-tree order (DevLeaf)
   std::vector<DevAncestry> ancestry;  // max(nodes, leaves) entries, see DevAncestry
   int quot_ok = 0;  // every triangle v0 coordinate passes quot_coord_ok (rt_internal.h)
+  // surface data (build_surface): empty unless a mesh is smooth or the caller
+  // gave texture coordinates
+  bool smooth = false;                // some mesh is smooth
+  std::vector<int> leaf_tri;          // 4 per DFS leaf: i0 i1 i2 flags (kSurfSmooth); a sphere: 0
+  std::vector<float> vertex_normals;  // 4 per vertex (smooth scenes)
+  std::vector<float> vertex_uv;       // 2 per vertex (scenes with uv)
 };
+
+// The vertex normals of HW3/src/Scene.cpp:690-695 and 870-876 (the rule in ceng795_rt.h) into
+// out[3 * num_vertices]; throws std::invalid_argument on a bad description.
+void host_vertex_normals(const rt_scene_desc& desc, float* out);
+// The surface data of a built scene (s made from desc by build_host_scene); surf may be null.
+void build_surface(const rt_scene_desc& desc, const rt_surface_desc* surf, HostScene& s);
 
 // Cuts the reference tree into treelets of <= K leaves (K = 1: lone leaves; 2: also leaf
 // pairs; K <= 0: no culling tree) and appends an 8-wide SAH tree over them.  Leaves the
@@ -89,6 +101,9 @@ struct XmlSceneStorage {
   std::vector<int> triangle_indices, triangle_material;
   std::vector<int> sphere_center, sphere_material;
   std::vector<float> sphere_radius;
+  // per <Mesh>: shadingMode="smooth" (HW3/src/Scene.cpp:634-639); no rt_scene_desc field points
+  // here, and rt_scene_load_xml ignores it as HW2 does
+  std::vector<unsigned char> mesh_smooth;
 };
 void load_scene_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc& desc);
 

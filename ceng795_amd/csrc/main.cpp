@@ -1,9 +1,10 @@
-// `raytracer [--gpus N] [--reference-traversal] <scene.xml>` — the host driver of
+// `raytracer [--gpus N] [--reference-traversal] [--smooth] <scene.xml>` — the host driver of
 // HW2/main.cpp:10-70 on top of the C ABI: parse the scene, then for every <Camera> render
 // (timed), quantise and write <ImageName>.  The reference spawns hardware_concurrency()
 // threads on render_image (main.cpp:33-36); here one rt_render call renders every row on the
 // GPU, or with --gpus N on N GPUs of the node (rt_scene_load_xml_multi: tiles dealt over the
-// devices, RCCL gather onto the first).
+// devices, RCCL gather onto the first).  --smooth honours <Mesh shadingMode="smooth"> as the HW3
+// loader does (rt_scene_load_xml_surface; one GPU); without it the attribute is ignored, as in HW2.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,11 +15,14 @@
 
 int main(int argc, char** argv) {
   int mode = RT_TRAVERSAL_FAST, gpus = 0;
+  bool smooth = false;
   const char* xml = nullptr;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     if (a == "--reference-traversal") {
       mode = RT_TRAVERSAL_REFERENCE;
+    } else if (a == "--smooth") {
+      smooth = true;
     } else if (a == "--gpus" && i + 1 < argc) {
       gpus = std::atoi(argv[++i]);
     } else {
@@ -29,8 +33,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "Please provide scene file as argument\n");
     return 1;
   }
+  if (smooth && gpus > 0) {
+    std::fprintf(stderr, "--smooth renders on one GPU (no --gpus)\n");
+    return 1;
+  }
   rt_scene* scene = nullptr;
   const int rc = gpus > 0 ? rt_scene_load_xml_multi(xml, gpus, nullptr, &scene)
+                 : smooth ? rt_scene_load_xml_surface(xml, -1, &scene)
                           : rt_scene_load_xml(xml, -1, &scene);
   if (rc != RT_OK) {
     std::fprintf(stderr, "%s\n", rt_last_error());

@@ -26,7 +26,7 @@
 
 namespace rt {
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
-                         const hipEvent_t* marks, hipStream_t stream);
+                         const hipEvent_t* marks, const SurfParams* surf, hipStream_t stream);
 int max_supported_depth();
 hipError_t launch_msaa_resolve(const MsaaResolveParams& M, hipStream_t stream);
 hipError_t launch_untile(const UntileParams& U, hipStream_t stream);
@@ -43,11 +43,14 @@ long long read_reset_phases(unsigned long long* out, long long max_values);
 hipError_t frame_kernel_occupancy(int* out4);
 int launch_cold_order(RenderParams P, hipStream_t stream);
 hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
-                        bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream);
+                        bool reorder, bool fast, bool deep, bool spheres, const SurfParams* surf,
+                        hipStream_t stream);
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
-                           bool spheres, hipStream_t stream);
+                           bool spheres, const SurfParams* surf, hipStream_t stream);
+hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, const AttrParams& A,
+                                 hipStream_t stream);
 hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
 hipError_t launch_film_resolve(const float* pixels, float* out, int width, int height,
                                hipStream_t stream);
@@ -163,6 +166,11 @@ struct Replica {
   DevBuf<DevMaterial> d_mats;
   DevBuf<DevLight> d_lights;
   DevBuf<int> d_leaf_object;  // per DFS leaf: its object index (rt_ray_hit::object)
+  // surface data (HostScene::leaf_tri / vertex_normals / vertex_uv), each only when the scene
+  // has it; `surf` points at them
+  DevBuf<int> d_surf_tri;
+  DevBuf<float> d_surf_normals, d_surf_uv;
+  SurfParams surf{nullptr, nullptr, nullptr, 0};
   DevBuf<unsigned long long> d_counters;
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
   // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
@@ -184,6 +192,10 @@ struct rt_scene {
   bool deep = false;
   bool needs_recursion = false;
   bool has_spheres = false;
+  // some mesh is smooth (rt_scene_create_surface): frames take the ray-tree path, as a scene that
+  // recurses does, and the ray-tree and closest-hit kernels run their SMOOTH instantiations
+  bool smooth = false;
+  bool tree_frames() const { return needs_recursion || smooth; }
   size_t most = 1;         // pixel records of the largest camera frame (whole tiles)
   unsigned long long msaa_seed = 0;
   // bytes of ray-tree frames one chunk of a radiance query may hold (rt_set_radiance_scratch_limit)
@@ -375,7 +387,7 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
 void seed_cold_orders(const rt_scene* s, Replica& r) {
   const HostScene& h = s->host;
   r.d_cold = std::vector<DevBuf<unsigned>>(h.cameras.size());
-  if (s->needs_recursion || h.lights.empty()) return;  // (no warm order either)
+  if (s->tree_frames() || h.lights.empty()) return;  // (no warm order either)
   for (size_t cam = 0; cam < h.cameras.size(); cam++) {
     const rt_camera& c = h.cameras[cam];
     if (c.num_samples > 1) continue;
@@ -404,6 +416,19 @@ void upload_replica(const rt_scene* s, Replica& r) {
   r.d_mats = upload(h.materials, "upload materials", kPad);
   r.d_lights = upload(h.lights, "upload lights", kPad);
   r.d_leaf_object = upload(h.leaf_object, "upload leaf objects", 0);
+  r.surf.num_leaves = (int)h.prims.size();
+  if (!h.leaf_tri.empty()) {
+    r.d_surf_tri = upload(h.leaf_tri, "upload leaf vertex ids", 0);
+    r.surf.tri = r.d_surf_tri.p;
+  }
+  if (!h.vertex_normals.empty()) {
+    r.d_surf_normals = upload(h.vertex_normals, "upload vertex normals", 0);
+    r.surf.normals = r.d_surf_normals.p;
+  }
+  if (!h.vertex_uv.empty()) {
+    r.d_surf_uv = upload(h.vertex_uv, "upload vertex uv", 0);
+    r.surf.uv = r.d_surf_uv.p;
+  }
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
@@ -422,6 +447,7 @@ int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
                                 " levels is not supported");
   s->deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
   for (const DevPrim& p : h.prims) s->has_spheres |= p.kind == kPrimSphere;
+  s->smooth = h.smooth;
   for (const DevMaterial& m : h.materials) {
     const bool mirror = m.mirror[0] != 0 || m.mirror[1] != 0 || m.mirror[2] != 0;
     const bool glass = m.transparency[0] != 0 || m.transparency[1] != 0 || m.transparency[2] != 0;
@@ -553,7 +579,7 @@ void limit_rows(RenderParams& P, int rows) {
 // Pixel records (RT_TILE_RECORDS) carry the primary hit and up to kRecMaxLights shadow bits:
 // pixel-centre cameras of scenes without mirror/dielectric recursion.
 bool records_ok(const rt_scene* s, int cam) {
-  return s->host.cameras[cam].num_samples <= 1 && !s->needs_recursion &&
+  return s->host.cameras[cam].num_samples <= 1 && !s->tree_frames() &&
          (int)s->host.lights.size() <= kRecMaxLights;
 }
 
@@ -619,6 +645,12 @@ const hipEvent_t* timing_marks(rt_scene* s, const RenderParams& P) {
   return t.pending.back().data();
 }
 
+// The surface data the SMOOTH kernel instantiations take: a smooth scene's (single-device: the
+// surface creators make no other), else null — the flat instantiations.
+const SurfParams* smooth_surface(const rt_scene* s) {
+  return s->smooth ? &s->rep[0]->surf : nullptr;
+}
+
 // The sample passes of an MSAA camera (HW2/Scene.cpp:32-69) over P's rows: pass k renders
 // sample k of every selected pixel into d_samples[k] (row-major, full-frame positions).
 void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_samples,
@@ -635,7 +667,7 @@ void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_s
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
     hip_check(launch_render(Q, fast, s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr,
-                            stream), "render launch");
+                            smooth_surface(s), stream), "render launch");
   }
 }
 
@@ -663,7 +695,7 @@ void enqueue_frame(rt_scene* s, const RenderParams& P, int samples, float* d_sam
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
     hip_check(launch_render(P, fast, s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr,
-                            stream), "render launch");
+                            smooth_surface(s), stream), "render launch");
     return;
   }
   enqueue_samples(s, P, samples, d_samples, stream, timed);
@@ -766,7 +798,7 @@ void WorkSet::bind(const rt_scene* s, const rt_camera& c, RenderParams& P) {
   reserve_tiles(s->host, (size_t)std::max(1, P.num_sel_tiles));
   P.occ = occ.p;
   set_schedule(P, sched.p);
-  if (s->needs_recursion) {
+  if (s->tree_frames()) {
     frames.reserve(frame_floats(s->host, P.num_sel_tiles), "alloc ray-tree frames");
     P.frames = frames.p;
   }
@@ -1091,13 +1123,17 @@ StreamScratch* scratch_for(rt_scene* s, Replica& r, void* stream, std::unique_lo
 }
 
 int load_xml_into(rt_scene* s, const char* xml_path, const std::vector<int>* devices,
-                  int device_count, const int* device_ids) {
+                  int device_count, const int* device_ids, bool surface = false) {
   return guarded([&] {
     XmlSceneStorage st;
     rt_scene_desc d;
     load_scene_xml(xml_path, st, d);
     s->host.image_names = st.image_names;
     build_host_scene(d, s->host);
+    if (surface) {  // rt_scene_load_xml_surface: the meshes' shadingMode, computed normals, no uv
+      const rt_surface_desc sd{sizeof(rt_surface_desc), st.mesh_smooth.data(), nullptr, nullptr};
+      build_surface(d, &sd, s->host);
+    }
     std::vector<int> devs;
     if (devices) {
       devs = *devices;
@@ -1208,7 +1244,7 @@ void enqueue_hits(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws
     Q.n = std::min(q.n - done, kQueryMaxLaunch);
     if (reorder) carve_reorder(Q, ws, Q.n);
     hip_check(launch_query(P, Q, r.d_nodes.p, OCCLUSION, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
-                           s->deep, s->has_spheres, stream),
+                           s->deep, s->has_spheres, smooth_surface(s), stream),
               "query launch");
   }
 }
@@ -1270,7 +1306,8 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
       QueryParams C = Q;
       C.n = std::min(part, R.first + chunk);
       hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
-                                s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres, stream),
+                                s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres,
+                                smooth_surface(s), stream),
                 "radiance query launch");
     }
   }
@@ -1527,6 +1564,119 @@ int rt_scene_load_xml_multi(const char* xml_path, int device_count, const int* d
   if (rc != RT_OK) return rc;
   *out = s.release();
   return RT_OK;
+}
+
+int rt_surface_version(void) { return 1; }
+
+int rt_scene_create_surface(const rt_scene_desc* desc, const rt_surface_desc* surface, int device,
+                            rt_scene** out) {
+  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_surface: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    if (surface && surface->struct_size < sizeof(rt_surface_desc))
+      throw std::invalid_argument("rt_scene_create_surface: rt_surface_desc::struct_size too small");
+    const std::vector<int> devs = single_device(device);
+    build_host_scene(*desc, s->host);
+    build_surface(*desc, surface, s->host);
+    return create_from_host(s.get(), devs, false);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_scene_load_xml_surface(const char* xml_path, int device, rt_scene** out) {
+  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_surface: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  std::vector<int> devs;
+  int rc = guarded([&] {
+    devs = single_device(device);
+    return RT_OK;
+  });
+  if (rc == RT_OK) rc = load_xml_into(s.get(), xml_path, &devs, 0, nullptr, true);
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_scene_has_smooth(const rt_scene* s) { return s && s->smooth ? 1 : 0; }
+
+int rt_host_vertex_normals_desc(const rt_scene_desc* desc, float* out3n) {
+  if (!desc || (!out3n && desc->num_vertices > 0))
+    return set_error(RT_E_INVALID, "rt_host_vertex_normals_desc: NULL argument");
+  return guarded([&] {
+    host_vertex_normals(*desc, out3n);
+    return RT_OK;
+  });
+}
+
+int rt_host_mesh_smooth_xml(const char* xml_path, unsigned char* out, int capacity) {
+  if (!xml_path || capacity < 0 || (!out && capacity > 0))
+    return set_error(RT_E_INVALID, "rt_host_mesh_smooth_xml: bad argument");
+  return guarded([&] {
+    XmlSceneStorage st;
+    rt_scene_desc d;
+    load_scene_xml(xml_path, st, d);
+    const int n = (int)st.mesh_smooth.size();
+    for (int m = 0; m < std::min(n, capacity); m++) out[m] = st.mesh_smooth[m];
+    return n;
+  });
+}
+
+// rt_hit_attributes*' argument rules (rt_trace_rays*'); they need no GPU.
+static void check_attr_args(const char* fn, const rt_scene* s, const void* rays, const void* hits,
+                            long long n, const void* attr) {
+  const std::string f(fn);
+  if (n < 0) throw std::invalid_argument(f + ": n < 0");
+  if (n > 0 && (!rays || !hits || !attr)) throw std::invalid_argument(f + ": NULL pointer");
+  if ((uintptr_t)rays % 16 != 0 || (uintptr_t)hits % 16 != 0 || (uintptr_t)attr % 16 != 0)
+    throw std::invalid_argument(f + ": rays, hits and attr must be 16-byte aligned");
+  if (!s) throw std::invalid_argument(f + ": scene is NULL");
+  if (s->multi)
+    throw std::domain_error(f + ": hit attributes on multi-device scenes are not supported");
+}
+
+int rt_hit_attributes_device(rt_scene* s, const rt_ray* d_rays, const rt_ray_hit* d_hits,
+                             long long n, rt_hit_attr* d_attr, void* stream) {
+  return guarded([&] {
+    check_attr_args("rt_hit_attributes_device", s, d_rays, d_hits, n, d_attr);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    hip_check(launch_hit_attributes(scene_params(s, r), r.surf, AttrParams{d_rays, d_hits, d_attr, n},
+                                    (hipStream_t)stream), "hit attributes launch");
+    return RT_OK;
+  });
+}
+
+int rt_hit_attributes(rt_scene* s, const rt_ray* rays, const rt_ray_hit* hits, long long n,
+                      rt_hit_attr* attr) {
+  return guarded([&] {
+    check_attr_args("rt_hit_attributes", s, rays, hits, n, attr);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    CtxLease lease(s, 1);
+    RenderCtx* x = lease.x[0];
+    // rays, then (in one buffer of 32-B records) the hits followed by the 48-B results
+    const size_t attr_recs = ((size_t)n * sizeof(rt_hit_attr) + sizeof(rt_ray_hit) - 1) / sizeof(rt_ray_hit);
+    x->d_rays.reserve((size_t)n, "alloc rays");
+    x->d_ray_out.reserve((size_t)n + attr_recs, "alloc hits and attributes");
+    rt_hit_attr* d_attr = reinterpret_cast<rt_hit_attr*>(x->d_ray_out.p + n);
+    hip_check(hipMemcpyAsync(x->d_rays.p, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice,
+                             x->stream), "upload rays");
+    hip_check(hipMemcpyAsync(x->d_ray_out.p, hits, (size_t)n * sizeof(rt_ray_hit),
+                             hipMemcpyHostToDevice, x->stream), "upload hits");
+    hip_check(launch_hit_attributes(scene_params(s, r), r.surf,
+                                    AttrParams{x->d_rays.p, x->d_ray_out.p, d_attr, n}, x->stream),
+              "hit attributes launch");
+    hip_check(hipMemcpyAsync(attr, d_attr, (size_t)n * sizeof(rt_hit_attr), hipMemcpyDeviceToHost,
+                             x->stream), "download attributes");
+    hip_check(hipStreamSynchronize(x->stream), "synchronize hit attributes");
+    return RT_OK;
+  });
 }
 
 void rt_scene_destroy(rt_scene* s) {

@@ -545,6 +545,32 @@ struct LitArg {};
 template <>
 struct LitArg<true> : LitParams {};
 
+// Surface data (rt_scene_create_surface), found by DFS leaf and by vertex id.
+// A scene has `tri` when a mesh is smooth or it has uv, `normals` when a mesh is smooth, `uv` when
+// the caller gave texture coordinates; a scene with none of them has all three null.
+// SurfArg<SMOOTH> is what the ray-tree and closest-hit code takes: empty in the flat
+// instantiations, whose kernels take no surface argument at all (rt_kernels.hip surf_of), so their
+// code is that of a build without surface data.
+constexpr int kSurfSmooth = 1;  // leaf flag: a face of a smooth mesh
+struct SurfParams {
+  const int* tri;        // int4 per DFS leaf: i0 i1 i2 flags; a sphere: zeros
+  const float* normals;  // float4 per vertex: the vertex normal, 0
+  const float* uv;       // float2 per vertex
+  int num_leaves;        // rt_hit_attributes' bound on rt_ray_hit::leaf
+};
+template <bool SMOOTH>
+struct SurfArg {};
+template <>
+struct SurfArg<true> : SurfParams {};
+
+// rt_hit_attributes*: rays, hits and attr hold n records each.
+struct AttrParams {
+  const void* rays;
+  const void* hits;
+  void* attr;
+  long long n;
+};
+
 #if defined(__HIPCC__)
 // The reference's splat weight (HW2/Scene.cpp:12-14): double exp of a float argument, double
 // division, narrowed.  One definition for the MSAA resolve (rt_kernels.hip) and the films

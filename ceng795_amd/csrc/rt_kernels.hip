@@ -368,6 +368,62 @@ __device__ __forceinline__ bool leaf_test(const DevPrim* __restrict__ prims, int
   return sphere_test(v0, p.a1[0], r, t);
 }
 
+// ------------------------------------------------------------------ surface data
+// Where inside its triangle a ray hit: tri_test's beta and gamma
+// (HW2/Triangle.cpp:51, 53), computed again after the walk from the winning leaf's record and the
+// same ray by the same functions, shared-reciprocal quotients included — the same bits, as
+// resolve_pixel re-derives t.
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void tri_barycentrics(const DevPrim& p, const LaneRay& r, float& beta,
+                                                 float& gamma) {
+  const V3 a1 = ld3(p.a1), a2 = ld3(p.a2);
+  const float det = det3(a1, a2, r.d);
+  const V3 b = tri_quotients(ld3(p.v0) - r.o, det, r.quot);
+  beta = det3(b, a2, r.d);
+  gamma = det3(a1, b, r.d);
+}
+
+// ((x0 * w) + (x1 * beta)) + (x2 * gamma) per component, w = (1 - beta) - gamma: every product and
+// sum rounded (the file compiles without contraction).
+__device__ __forceinline__ float bary_mix(float x0, float x1, float x2, float w, float beta,
+                                          float gamma) {
+  return ((x0 * w) + (x1 * beta)) + (x2 * gamma);
+}
+
+// Mesh_triangle.cpp:101-106: the interpolated vertex normal, normalised by a true division.
+__device__ __forceinline__ V3 smooth_normal(const SurfParams& S, i4 tr, float beta, float gamma) {
+  const f4* vn = reinterpret_cast<const f4*>(S.normals);
+  const f4 n0 = vn[tr.x], n1 = vn[tr.y], n2 = vn[tr.z];
+  const float w = (1.0f - beta) - gamma;
+  const V3 N = v3(bary_mix(n0.x, n1.x, n2.x, w, beta, gamma), bary_mix(n0.y, n1.y, n2.y, w, beta, gamma),
+                  bary_mix(n0.z, n1.z, n2.z, w, beta, gamma));
+  return N / length(N);
+}
+
+// Hit_data::normal of a triangle leaf: `flat`, or on a face of a smooth mesh the normal above.
+// Nothing in the flat instantiations.
+template <bool SMOOTH>
+__device__ __forceinline__ V3 triangle_normal(const SurfArg<SMOOTH>& S, const DevPrim& p, int leaf,
+                                              const LaneRay& r, V3 flat) {
+  if constexpr (SMOOTH) {
+    const i4 tr = reinterpret_cast<const i4*>(S.tri)[leaf];
+    if (tr.w & kSurfSmooth) {
+      float beta, gamma;
+      tri_barycentrics(p, r, beta, gamma);
+      return smooth_normal(S, tr, beta, gamma);
+    }
+  }
+  return flat;
+}
+
+// The kernels that read Hit_data::normal take the scene's surface data as a parameter pack: empty
+// in the flat instantiations, whose argument list (and implicit-argument offsets) is then that of
+// a build without surface data, and one SurfArg<true> in the SMOOTH ones.
+__device__ __forceinline__ SurfArg<false> surf_of() { return {}; }
+__device__ __forceinline__ const SurfArg<true>& surf_of(const SurfArg<true>& s) { return s; }
+
 // ------------------------------------------------------------------ traversal stack
 // Wave-uniform (node, lane-mask) entries.  DEEP == false: entry i lives in VGPR lane i
 // (v_writelane push / v_readlane pop, no memory traffic, 64 deep).  DEEP == true: a
@@ -653,8 +709,6 @@ __device__ __forceinline__ void batch_push_n(WaveLeafLds& L, int& n, int leaf, u
 __device__ __forceinline__ float lane_f(int src, float v) {
   return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v)));
 }
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // Runs the n queued tests; SHADOW: 0 < t < thr of the owner sets its flag, else the owner's
 // key takes min(key, (t, leaf)) for 0 < t < inf.  All lanes of the wave take part.  SKIP:
@@ -1939,7 +1993,10 @@ struct TreeCounts {
 // RECURSE = false (depth 0, or a scene without mirror or glass: no material can spawn a ray):
 // closest hit, local shading or the miss rule, and no frame is read or written.
 // LIT: the lane's own light records join every local shading of its tree (local_color).
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true, bool LIT = false>
+// SMOOTH: the scene has a smooth mesh; a hit on one of its faces takes the interpolated vertex
+// normal (triangle_normal) wherever Hit_data::normal is read.
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true, bool LIT = false,
+          bool SMOOTH = false>
 __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          const DevPrim* __restrict__ prims,
                                          const float* __restrict__ normals,
@@ -1947,7 +2004,8 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
                                          const DevLight* __restrict__ lights, int* spill,
                                          WaveLeafLds& L, float* frames, size_t stride, V3 ro, V3 rd,
                                          bool medium, int depth, bool active, float& t_first,
-                                         TreeCounts& cnt, const f4* own = nullptr, int own_k = 0) {
+                                         TreeCounts& cnt, const SurfArg<SMOOTH>& surf,
+                                         const f4* own = nullptr, int own_k = 0) {
   auto frame = [&](int level) {
     return FrameRef{frames + (size_t)level * kFrFields * stride, stride};
   };
@@ -1977,7 +2035,9 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
     if (hit) {
       p = ray.o + ray.d * t;
       const DevPrim& pr = prims[leaf];
-      n = pr.kind == kPrimTriangle ? ld3(normals + 4 * leaf) : normalize(p - ld3(pr.v0));
+      n = pr.kind == kPrimTriangle
+              ? triangle_normal<SMOOTH>(surf, pr, leaf, ray, ld3(normals + 4 * leaf))
+              : normalize(p - ld3(pr.v0));
       mat = pr.material;
     }
     const V3 local = local_color<FAST, DEEP, SPHERES, LIT>(P, nodes, prims, mats, lights, spill, L,
@@ -2115,14 +2175,15 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
   return out;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH>
 __device__ __forceinline__ void recursive_packet(const RenderParams& P,
                                                  const DevNode* __restrict__ nodes,
                                                  const DevPrim* __restrict__ prims,
                                                  const float* __restrict__ normals,
                                                  const DevMaterial* __restrict__ mats,
                                                  const DevLight* __restrict__ lights, int sel,
-                                                 int* spill, WaveLeafLds& L) {
+                                                 int* spill, WaveLeafLds& L,
+                                                 const SurfArg<SMOOTH>& surf) {
   const PacketPixel q = packet_pixel(P, sel);
   const size_t lanes_total = (size_t)P.num_sel_tiles * (kTile * kTile);
   const size_t g = (size_t)sel * (kTile * kTile) + q.lane;
@@ -2130,10 +2191,9 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
   float t_first;
   TreeCounts cnt;
   // the camera's pixel ray at the scene's maximum depth
-  const V3 out = trace_tree<FAST, DEEP, SPHERES>(P, nodes, prims, normals, mats, lights, spill, L,
-                                                 P.frames + g, lanes_total, ld3(P.cam_e),
-                                                 primary_dir(P, q.px, q.py), false, P.max_depth,
-                                                 q.valid, t_first, cnt);
+  const V3 out = trace_tree<FAST, DEEP, SPHERES, true, false, SMOOTH>(
+      P, nodes, prims, normals, mats, lights, spill, L, P.frames + g, lanes_total, ld3(P.cam_e),
+      primary_dir(P, q.px, q.py), false, P.max_depth, q.valid, t_first, cnt, surf);
   const unsigned long long n_hits = cnt.hits, n_shadow = cnt.shadow, n_secondary = cnt.secondary;
   if (q.valid) {
     float* o;
@@ -2454,18 +2514,19 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
   TL_END(0);
 }
 
-template <bool FAST, bool DEEP, bool SPHERES>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename... Surf>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void recursive_kernel(
     RenderParams P, const DevNode* __restrict__ nodes, const DevPrim* __restrict__ prims,
     const float* __restrict__ normals, const DevMaterial* __restrict__ mats,
-    const DevLight* __restrict__ lights) {
+    const DevLight* __restrict__ lights, Surf... surf) {
+  static_assert(sizeof...(Surf) == (SMOOTH ? 1 : 0), "SMOOTH kernels take one SurfArg<true>");
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
   const int sel = packet_index<kWavesPerBlock>();
   if (sel >= P.num_sel_tiles) return;
   int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
-  recursive_packet<FAST, DEEP, SPHERES>(P, nodes, prims, normals, mats, lights, sel, spill,
-                                        leaf_lds[threadIdx.x >> 6]);
+  recursive_packet<FAST, DEEP, SPHERES, SMOOTH>(P, nodes, prims, normals, mats, lights, sel, spill,
+                                                leaf_lds[threadIdx.x >> 6], surf_of(surf...));
 }
 
 // marks (nullable): 4 events recorded before the frame kernel (or the recursive kernel), after
@@ -2554,17 +2615,32 @@ int launch_cold_order(RenderParams P, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 1 : 0;
 }
 
+// The surface argument of a launch: f(std::true_type, the scene's surface data) for a scene with
+// a smooth mesh (surf non-null), else f(std::false_type) — the flat kernels take none.
+template <typename F>
+static void with_surface(const SurfParams* surf, F&& f) {
+  if (surf) {
+    SurfArg<true> arg;
+    static_cast<SurfParams&>(arg) = *surf;
+    f(std::true_type{}, arg);
+  } else {
+    f(std::false_type{});
+  }
+}
+
 template <bool FAST, bool DEEP, bool SPHERES>
 static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* marks,
-                           hipStream_t stream) {
+                           const SurfParams* surf, hipStream_t stream) {
   const DevNode* nodes = P.nodes;
   const DevLight* lights = P.lights;
   if (P.frames) {  // recursive scenes: one kernel walks each pixel's ray tree
     const size_t lds = deep_lds_bytes<DEEP>(kWavesPerBlock);
     mark(marks, 0, stream);
-    hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, SPHERES>), dim3(blocks),
-                       dim3(kWavesPerBlock * 64), lds, stream, P, nodes, P.prims, P.normals,
-                       P.materials, lights);
+    with_surface(surf, [&](auto sm, auto... arg) {
+      hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, SPHERES, decltype(sm)::value>), dim3(blocks),
+                         dim3(kWavesPerBlock * 64), lds, stream, P, nodes, P.prims, P.normals,
+                         P.materials, lights, arg...);
+    });
     mark(marks, 1, stream);
     mark(marks, 2, stream);
     mark(marks, 3, stream);
@@ -2845,9 +2921,10 @@ __device__ __forceinline__ QueryRay load_query_ray(const QueryParams& Q, long lo
   return q;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename... Surf>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void query_closest_kernel(
-    RenderParams P, QueryParams Q, const DevNode* __restrict__ nodes) {
+    RenderParams P, QueryParams Q, const DevNode* __restrict__ nodes, Surf... surf) {
+  static_assert(sizeof...(Surf) == (SMOOTH ? 1 : 0), "SMOOTH kernels take one SurfArg<true>");
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
   if ((query_index() & ~63ll) >= Q.n) return;  // the whole wave is past the batch
@@ -2867,11 +2944,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void query_closest_kernel(
   f4 h1 = {0.0f, 0.0f, 0.0f, 0.0f};
   if (q.valid && leaf >= 0) {
     const DevPrim& pr = P.prims[leaf];
-    // Hit_data::normal: the flat normal (Triangle.cpp:14), or Sphere.h:42,50's
-    // (ray.point_at(t) - center).normalize()
-    const V3 n = !SPHERES || pr.kind == kPrimTriangle
-                     ? ld3(P.normals + 4 * leaf)
-                     : normalize((ray.o + ray.d * t) - ld3(pr.v0));
+    // Hit_data::normal: the flat normal (Triangle.cpp:14; a smooth mesh's face: the interpolated
+    // vertex normal), or Sphere.h:42,50's (ray.point_at(t) - center).normalize()
+    V3 n = !SPHERES || pr.kind == kPrimTriangle
+               ? ld3(P.normals + 4 * leaf)
+               : normalize((ray.o + ray.d * t) - ld3(pr.v0));
+    if constexpr (SMOOTH) {
+      if (!SPHERES || pr.kind == kPrimTriangle)
+        n = triangle_normal<true>(surf_of(surf...), pr, leaf, ray, n);
+    }
     h0 = (f4){t, __int_as_float(Q.leaf_object[leaf]), __int_as_float(pr.material),
               __int_as_float(leaf)};
     h1 = (f4){n.x, n.y, n.z, 0.0f};
@@ -2927,11 +3008,13 @@ constexpr int kRadianceWaves = RT_RADIANCE_WAVES;
 // LIT (rt_shade_rays_lit_device): the ray's own light records, found by the
 // ray's index in the caller's batch (its result slot), not by its place in the chunk or in the
 // reordered order; shared records sit at index 0 for every ray.  LitArg<false> is empty.
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE, bool LIT = false>
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE, bool LIT, bool SMOOTH, typename... Surf>
 __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void query_radiance_kernel(
     RenderParams P, QueryParams Q, RadianceParams R, const DevNode* __restrict__ nodes,
     const DevPrim* __restrict__ prims, const float* __restrict__ normals,
-    const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights, LitArg<LIT> lit) {
+    const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights, LitArg<LIT> lit,
+    Surf... surf) {
+  static_assert(sizeof...(Surf) == (SMOOTH ? 1 : 0), "SMOOTH kernels take one SurfArg<true>");
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
   const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;  // in the chunk
@@ -2950,9 +3033,10 @@ __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void que
     own = reinterpret_cast<const f4*>(lit.lights) + 3 * (size_t)ray * (size_t)lit.k;
     own_k = lit.k;
   }
-  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE, LIT>(
+  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE, LIT, SMOOTH>(
       P, nodes, prims, normals, mats, lights, spill, L, RECURSE ? R.frames + slot : nullptr,
-      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, own, own_k);
+      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, surf_of(surf...), own,
+      own_k);
   if (i < Q.n) {
     // Pixel::add_color(color, 1) onto a zeroed pixel; an invalid ray: (0, 0, 0, +inf)
     const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
@@ -3130,7 +3214,8 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 // perm_out point at query_scratch_words(n) words of scratch.  The variant is picked as
 // launch_render picks the frame kernels'.
 hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
-                        bool reorder, bool fast, bool deep, bool spheres, hipStream_t stream) {
+                        bool reorder, bool fast, bool deep, bool spheres, const SurfParams* surf,
+                        hipStream_t stream) {
   if (Q.n <= 0) return hipSuccess;
   Q.perm = nullptr;
   if (reorder) {
@@ -3146,8 +3231,10 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
       hipLaunchKernelGGL((query_occluded_kernel<F, D, S>), grid, dim3(kWavesPerBlock * 64), lds,
                          stream, P, Q, nodes);
     else
-      hipLaunchKernelGGL((query_closest_kernel<F, D, S>), grid, dim3(kWavesPerBlock * 64), lds,
-                         stream, P, Q, nodes);
+      with_surface(surf, [&](auto sm, auto... arg) {
+        hipLaunchKernelGGL((query_closest_kernel<F, D, S, decltype(sm)::value>), grid,
+                           dim3(kWavesPerBlock * 64), lds, stream, P, Q, nodes, arg...);
+      });
   });
   return hipGetLastError();
 }
@@ -3175,7 +3262,7 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
 // cannot recurse.
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
-                           bool spheres, hipStream_t stream) {
+                           bool spheres, const SurfParams* surf, hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
   const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
@@ -3183,8 +3270,11 @@ hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const Ra
     const size_t lds = deep_lds_bytes<D>(kRadianceWaves);
     auto launch = [&](auto re, auto li, auto arg) {
       constexpr bool RE = decltype(re)::value, LI = decltype(li)::value;
-      hipLaunchKernelGGL((query_radiance_kernel<F, D, S, RE, LI>), grid, dim3(kRadianceWaves * 64),
-                         lds, stream, P, Q, R, nodes, P.prims, P.normals, P.materials, P.lights, arg);
+      with_surface(surf, [&](auto sm, auto... sarg) {
+        hipLaunchKernelGGL((query_radiance_kernel<F, D, S, RE, LI, decltype(sm)::value>), grid,
+                           dim3(kRadianceWaves * 64), lds, stream, P, Q, R, nodes, P.prims,
+                           P.normals, P.materials, P.lights, arg, sarg...);
+      });
     };
     using T = std::true_type;
     using N = std::false_type;
@@ -3201,6 +3291,77 @@ hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const Ra
       launch(T{}, N{}, LitArg<false>{});
     }
   });
+  return hipGetLastError();
+}
+
+// rt_hit_attributes* (DESIGN.md §4.15): a lane per ray; two 16-B loads of the ray, one of the hit
+// record's first half (t and the leaf), three 16-B stores.  Record i comes from ray i and
+// hits[i].leaf alone: a triangle's beta and gamma as the walk computed them (tri_barycentrics), a
+// sphere's normal from hits[i].t as query_closest_kernel computes it.  A leaf outside
+// [0, S.num_leaves) or an invalid ray (query_ray_ok) gives the all-zero record, and no load
+// depends on anything else the caller wrote.  S.tri / S.normals / S.uv may each be null.
+constexpr int kAttrHit = 1, kAttrTriangle = 2, kAttrSmooth = 4;  // RT_ATTR_*
+__global__ __launch_bounds__(256) void hit_attr_kernel(RenderParams P, SurfParams S, AttrParams A) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  const f4* rp = reinterpret_cast<const f4*>(A.rays) + 2 * i;
+  const f4 ra = rp[0], rb = rp[1];
+  const f4 h0 = reinterpret_cast<const f4*>(A.hits)[2 * i];
+  const V3 o = v3(ra.x, ra.y, ra.z), d = v3(rb.x, rb.y, rb.z);
+  const int leaf = __float_as_int(h0.w);
+  f4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = a0, a2 = a0;
+  if (leaf >= 0 && leaf < S.num_leaves && query_ray_ok(o, d)) {
+    const DevPrim& pr = P.prims[leaf];
+    if (pr.kind == kPrimTriangle) {
+      const LaneRay ray = make_ray(o, d, P.quot_ok);
+      float beta, gamma;
+      tri_barycentrics(pr, ray, beta, gamma);
+      const V3 flat = ld3(P.normals + 4 * leaf);
+      V3 sn = flat;
+      int flags = kAttrHit | kAttrTriangle;
+      float u = 0.0f, v = 0.0f;
+      if (S.tri) {
+        const i4 tr = reinterpret_cast<const i4*>(S.tri)[leaf];
+        if (S.uv) {
+          const float w = (1.0f - beta) - gamma;
+          const float* t0 = S.uv + 2 * (size_t)tr.x;
+          const float* t1 = S.uv + 2 * (size_t)tr.y;
+          const float* t2 = S.uv + 2 * (size_t)tr.z;
+          u = bary_mix(t0[0], t1[0], t2[0], w, beta, gamma);
+          v = bary_mix(t0[1], t1[1], t2[1], w, beta, gamma);
+        }
+        if (S.normals && (tr.w & kSurfSmooth)) {
+          sn = smooth_normal(S, tr, beta, gamma);
+          flags |= kAttrSmooth;
+        }
+      }
+      a0 = (f4){beta, gamma, u, v};
+      a1 = (f4){sn.x, sn.y, sn.z, __int_as_float(flags)};
+      a2 = (f4){flat.x, flat.y, flat.z, 0.0f};
+    } else {  // Sphere.h:42,50: (ray.point_at(t) - center).normalize()
+      const V3 n = normalize((o + d * h0.x) - ld3(pr.v0));
+      a1 = (f4){n.x, n.y, n.z, __int_as_float(kAttrHit)};
+      a2 = (f4){n.x, n.y, n.z, 0.0f};
+    }
+  }
+  f4* out = reinterpret_cast<f4*>(A.attr) + 3 * i;
+  out[0] = a0;
+  out[1] = a1;
+  out[2] = a2;
+}
+
+hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, const AttrParams& A,
+                                 hipStream_t stream) {
+  if (A.n <= 0) return hipSuccess;
+  for (long long done = 0; done < A.n; done += kQueryMaxLaunch) {  // (32-bit grids)
+    AttrParams C;
+    C.rays = static_cast<const char*>(A.rays) + (size_t)done * 32;
+    C.hits = static_cast<const char*>(A.hits) + (size_t)done * 32;
+    C.attr = static_cast<char*>(A.attr) + (size_t)done * 48;
+    C.n = A.n - done < kQueryMaxLaunch ? A.n - done : kQueryMaxLaunch;
+    hipLaunchKernelGGL(hit_attr_kernel, dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, stream,
+                       P, S, C);
+  }
   return hipGetLastError();
 }
 
@@ -3309,12 +3470,12 @@ hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,
 }
 
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
-                         const hipEvent_t* marks, hipStream_t stream) {
+                         const hipEvent_t* marks, const SurfParams* surf, hipStream_t stream) {
   if (P.num_sel_tiles <= 0) return hipSuccess;
   const int blocks = (P.num_sel_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
     launch_variant<decltype(fa)::value, decltype(de)::value, decltype(sp)::value>(
-        P, blocks, marks, stream);
+        P, blocks, marks, surf, stream);
   });
   return hipGetLastError();
 }

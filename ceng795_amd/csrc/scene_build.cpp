@@ -594,6 +594,88 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
   }
 }
 
+// Vertex normals as the HW3 loader accumulates them: Scene.cpp:690-695 per face (Mesh_triangle's
+// normal, Mesh_triangle.cpp:16, and get_surface_area, :69-74), Vertex::add_vertex_normal
+// (Vertex.h:13-16), then finalize_normal for every vertex with a contribution (Scene.cpp:870-876).
+void host_vertex_normals(const rt_scene_desc& d, float* out) {
+  if (d.num_vertices < 0 || d.num_meshes < 0) fail("negative count in scene description");
+  if (d.num_vertices && !d.vertices) fail("vertices == NULL");
+  if (d.num_meshes && (!d.mesh_face_count || !d.mesh_faces))
+    fail("mesh_face_count / mesh_faces == NULL");
+  for (int m = 0; m < d.num_meshes; m++)
+    if (d.mesh_face_count[m] <= 0) fail("mesh without faces (the reference dereferences a NULL bvh)");
+  const size_t nv = (size_t)d.num_vertices;
+  std::vector<F3> vn(nv, F3{0.0f, 0.0f, 0.0f});
+  std::vector<char> has(nv, 0);
+  auto vtx = [&](int i) -> F3 {
+    if (i < 0 || i >= d.num_vertices) fail("vertex index out of range");
+    return {d.vertices[3 * i], d.vertices[3 * i + 1], d.vertices[3 * i + 2]};
+  };
+  long long fb = 0;
+  for (int m = 0; m < d.num_meshes; m++) {
+    const int nf = d.mesh_face_count[m];
+    for (int f = 0; f < nf; f++) {
+      const int* idx = d.mesh_faces + 3 * (fb + f);
+      const F3 v0 = vtx(idx[0]), v1 = vtx(idx[1]), v2 = vtx(idx[2]);
+      const F3 c = cross(v1 - v0, v2 - v0);
+      const F3 n = unit(c);
+      const float area = std::sqrt(c.x * c.x + c.y * c.y + c.z * c.z) / 2;
+      for (int k = 0; k < 3; k++) {
+        vn[idx[k]] = vn[idx[k]] + n * area;
+        has[idx[k]] = 1;
+      }
+    }
+    fb += nf;
+  }
+  for (size_t v = 0; v < nv; v++) {
+    const F3 n = has[v] ? unit(vn[v]) : vn[v];
+    out[3 * v] = n.x;
+    out[3 * v + 1] = n.y;
+    out[3 * v + 2] = n.z;
+  }
+}
+
+void build_surface(const rt_scene_desc& d, const rt_surface_desc* surf, HostScene& s) {
+  s.smooth = false;
+  s.leaf_tri.clear();
+  s.vertex_normals.clear();
+  s.vertex_uv.clear();
+  if (!surf) return;
+  if (surf->struct_size < sizeof(rt_surface_desc)) fail("rt_surface_desc::struct_size too small");
+  long long faces = 0;
+  std::vector<long long> mesh_end;  // faces of meshes 0 .. m
+  for (int m = 0; m < d.num_meshes; m++) {
+    faces += d.mesh_face_count[m];
+    mesh_end.push_back(faces);
+    s.smooth |= surf->mesh_smooth && surf->mesh_smooth[m] != 0;
+  }
+  if (!s.smooth && !surf->vertex_uv) return;
+  const size_t nv = (size_t)d.num_vertices;
+  s.leaf_tri.assign(4 * s.leaf_src.size(), 0);
+  for (size_t k = 0; k < s.leaf_src.size(); k++) {
+    const LeafSource& l = s.leaf_src[k];
+    if (l.kind != kPrimTriangle) continue;
+    int flags = 0;
+    if (s.smooth && l.object < faces) {  // a mesh face: its mesh's mode
+      const size_t m = std::upper_bound(mesh_end.begin(), mesh_end.end(), (long long)l.object) -
+                       mesh_end.begin();
+      flags = surf->mesh_smooth[m] ? kSurfSmooth : 0;
+    }
+    const int rec[4] = {l.i0, l.i1, l.i2, flags};
+    std::memcpy(&s.leaf_tri[4 * k], rec, sizeof rec);
+  }
+  if (s.smooth) {
+    std::vector<float> vn(3 * nv);
+    if (surf->vertex_normals)
+      std::memcpy(vn.data(), surf->vertex_normals, sizeof(float) * 3 * nv);
+    else
+      host_vertex_normals(d, vn.data());
+    s.vertex_normals.assign(4 * nv, 0.0f);
+    for (size_t v = 0; v < nv; v++) std::memcpy(&s.vertex_normals[4 * v], &vn[3 * v], 12);
+  }
+  if (surf->vertex_uv) s.vertex_uv.assign(surf->vertex_uv, surf->vertex_uv + 2 * nv);
+}
+
 std::string dump_bvh(const HostScene& s) {
   std::ostringstream os;
   auto hex = [](float f) {

@@ -266,6 +266,8 @@ void load_scene_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc&
     ss.clear();
     st.mesh_material.push_back(mat - 1);
     st.mesh_face_count.push_back(count);
+    const char* mode = m->attr("shadingMode");
+    st.mesh_smooth.push_back(mode && std::string(mode) == "smooth" ? 1 : 0);
   }
   ss.clear();
   for (const Node* t : objs->each("Triangle")) {

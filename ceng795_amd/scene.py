@@ -19,6 +19,10 @@ RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float
                       ("pad", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("material", np.int32),
                       ("leaf", np.int32), ("normal", np.float32, 3), ("pad", np.int32)])
+# rt_hit_attr, 48 bytes; flags: RT_ATTR_HIT 1, RT_ATTR_TRIANGLE 2, RT_ATTR_SMOOTH 4
+HIT_ATTR_DTYPE = np.dtype([("beta", np.float32), ("gamma", np.float32), ("uv", np.float32, 2),
+                           ("shading_normal", np.float32, 3), ("flags", np.int32),
+                           ("geometric_normal", np.float32, 3), ("pad", np.int32)])
 # rt_radiance, 16 bytes
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
 # rt_light_sample, 48 bytes: a non-finite position = no light; normal 0 0 0 = a point light
@@ -91,16 +95,48 @@ class Scene:
     """
 
     def __init__(self, file_name: str, device: int = -1, traversal: str = "fast",
-                 devices: Optional[list] = None):
+                 devices: Optional[list] = None, smooth: bool = False):
         h = C.c_void_p()
         if devices is not None:
+            if smooth:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
+                                   "smooth shading on multi-device scenes is not supported")
             arr = (C.c_int * len(devices))(*devices)
             check(lib().rt_scene_load_xml_multi(str(file_name).encode(), len(devices), arr,
                                                 C.byref(h)))
+        elif smooth:  # <Mesh shadingMode="smooth"> honoured (rt_scene_load_xml_surface)
+            check(lib().rt_scene_load_xml_surface(str(file_name).encode(), device, C.byref(h)))
         else:
             check(lib().rt_scene_load_xml(str(file_name).encode(), device, C.byref(h)))
         self._h = h
         self.set_traversal(traversal)
+
+    @classmethod
+    def create(cls, desc, mesh_smooth=None, vertex_normals=None, vertex_uv=None,
+               device: int = -1) -> "Scene":
+        """A scene from an ``rt_scene_desc`` with surface data (rt_scene_create_surface):
+        ``mesh_smooth`` one flag per mesh, ``vertex_normals`` (num_vertices, 3) used as given
+        (None: the area-weighted normals of the HW3 loader), ``vertex_uv`` (num_vertices, 2)."""
+        surf = _lib.rt_surface_desc()
+        surf.struct_size = C.sizeof(_lib.rt_surface_desc)
+        keep = []
+
+        def arr(a, dtype, count, ctype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype).reshape(-1)
+            if a.size != count:
+                raise ValueError(f"{what} must hold {count} values")
+            keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ctype))
+
+        surf.mesh_smooth = arr(mesh_smooth, np.uint8, desc.num_meshes, C.c_ubyte, "mesh_smooth")
+        surf.vertex_normals = arr(vertex_normals, np.float32, 3 * desc.num_vertices, C.c_float,
+                                  "vertex_normals")
+        surf.vertex_uv = arr(vertex_uv, np.float32, 2 * desc.num_vertices, C.c_float, "vertex_uv")
+        h = C.c_void_p()
+        check(lib().rt_scene_create_surface(C.byref(desc), C.byref(surf), device, C.byref(h)))
+        return cls._from_handle(h)
 
     @classmethod
     def _from_handle(cls, h: C.c_void_p) -> "Scene":
@@ -282,6 +318,35 @@ class Scene:
                                        _lib.RT_QUERY_REORDER if reorder else 0,
                                        C.c_void_p(stream)))
 
+    # ------------------------------------------------------------------ hit attributes
+    @property
+    def has_smooth(self) -> bool:
+        """Some mesh of the scene is smooth-shaded (rt_scene_has_smooth)."""
+        return bool(lib().rt_scene_has_smooth(self._h))
+
+    def hit_attributes(self, origins, directions, hits) -> np.ndarray:
+        """Where each ray hit its primitive (rt_hit_attributes): ``hits`` is the HIT_DTYPE array
+        ``trace_rays`` gave for these rays; returns a HIT_ATTR_DTYPE array with the triangle's
+        ``beta`` / ``gamma``, the interpolated ``uv``, the shading normal (smooth on a smooth
+        mesh) and the geometric normal.  A miss or an invalid ray: the all-zero record."""
+        rays = pack_rays(origins, directions)
+        h = np.asarray(hits)
+        if h.dtype != HIT_DTYPE or h.shape != (len(rays),):
+            raise ValueError("hits must be a HIT_DTYPE array with one record per ray")
+        hin = _aligned(len(rays), HIT_DTYPE)
+        hin[...] = h
+        attr = _aligned(len(rays), HIT_ATTR_DTYPE)
+        check(lib().rt_hit_attributes(self._h, rays.ctypes.data, hin.ctypes.data, len(rays),
+                                      attr.ctypes.data))
+        return attr
+
+    def hit_attributes_device(self, rays_ptr: int, hits_ptr: int, n: int, attr_ptr: int, *,
+                              stream: int = 0) -> None:
+        """rt_hit_attributes_device: n rt_ray and n rt_ray_hit records in device memory to n
+        rt_hit_attr records at ``attr_ptr``, asynchronously on HIP stream ``stream``."""
+        check(lib().rt_hit_attributes_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), n,
+                                             C.c_void_p(attr_ptr), C.c_void_p(stream)))
+
     # ------------------------------------------------------------------ radiance queries
     @staticmethod
     def _radiance_flags(in_medium: bool, reorder: bool) -> int:
@@ -406,6 +471,23 @@ def write_png(path: str, rgb: np.ndarray) -> None:
 def host_dump_bvh(xml_path: str, out_path: str) -> None:
     """Host-only: parse + build + flatten the BVH and dump it (no GPU needed)."""
     check(lib().rt_host_dump_bvh_xml(str(xml_path).encode(), str(out_path).encode()))
+
+
+def host_vertex_normals(desc) -> np.ndarray:
+    """Host-only (rt_host_vertex_normals_desc): the (num_vertices, 3) area-weighted vertex normals
+    a smooth scene made from ``desc`` (an ``rt_scene_desc``) uses when the caller gives none."""
+    out = np.zeros((max(0, desc.num_vertices), 3), np.float32)
+    check(lib().rt_host_vertex_normals_desc(C.byref(desc), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def host_mesh_smooth(xml_path: str) -> np.ndarray:
+    """Host-only (rt_host_mesh_smooth_xml): uint8 per <Mesh>, 1 where shadingMode="smooth"."""
+    n = check(lib().rt_host_mesh_smooth_xml(str(xml_path).encode(), None, 0))
+    out = np.zeros(n, np.uint8)
+    check(lib().rt_host_mesh_smooth_xml(str(xml_path).encode(),
+                                        out.ctypes.data_as(C.POINTER(C.c_ubyte)), n))
+    return out
 
 
 def host_leaf_objects(desc) -> np.ndarray:

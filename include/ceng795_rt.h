@@ -434,7 +434,8 @@ typedef struct rt_ray_hit {  /* 32 B */
   int   object;   /* index in the object lists, bvh_leaf_object's numbering; -1 miss */
   int   material; /* -1 miss                                                         */
   int   leaf;     /* DFS leaf index = the closest-hit tie-break key; -1 miss         */
-  float normal[3];/* Hit_data::normal: flat triangle normal, or
+  float normal[3];/* Hit_data::normal: flat triangle normal (a smooth mesh's face: the
+                     interpolated vertex normal, "Surface data" below), or
                      (o + d*t - center).normalize() for a sphere; 0 0 0 on a miss    */
   int   pad;
 } rt_ray_hit;
@@ -648,6 +649,89 @@ int rt_film_shade_rays_lit_device(rt_film* film, const rt_ray* d_rays, const flo
                                   int flags, void* hip_stream);
 int rt_film_shade_rays_lit(rt_film* film, const rt_ray* rays, const float* xy, long long n, int depth,
                            const rt_light_sample* lights, int k, int flags, rt_stats* stats);
+
+/* ---- Surface data: smooth shading and hit attributes (barycentrics, normals, uv) --------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_SURFACE / rt_surface_version);
+ * rt_scene_desc and rt_ray_hit keep their layout.  Every entry above shades with one normal per
+ * triangle (HW2's Triangle::normal).  These add the smooth-shaded meshes of the later homeworks
+ * (<Mesh shadingMode="smooth">, HW3/src/Scene.cpp:634-639) and tell a caller with its own shading
+ * where inside a triangle a ray hit.
+ *
+ *   scenes    rt_scene_create_surface is rt_scene_create with an rt_surface_desc beside the
+ *             description: which meshes are smooth, the per-vertex normals (used as given, not
+ *             normalised; NULL: computed by the rule below) and per-vertex texture coordinates.
+ *             A NULL surface, or one without a smooth mesh and without uv, gives a scene whose
+ *             every result equals rt_scene_create's, byte for byte.  The caller's own BVH
+ *             (bvh_*) works as before: vertex data is found by vertex id.
+ *             rt_scene_load_xml_surface is rt_scene_load_xml with shadingMode="smooth" honoured
+ *             (no uv); rt_scene_load_xml itself keeps ignoring the attribute, as HW2 does.
+ *             There is no _multi variant of either.
+ *   normals   vn[v] = 0; then for the meshes in order and each mesh's faces in order (flat meshes
+ *             too, loose <Triangle>s not): c = (v1 - v0).cross(v2 - v0), n = c / length(c) (the
+ *             bits of the flat normal), area = length(c) / 2, vn[i] = vn[i] + n * area for i0, i1,
+ *             i2 in that order; at the end every vertex that got a contribution becomes
+ *             vn / length(vn) (HW3/src/Scene.cpp:690-695, 870-876, Mesh_triangle.cpp:16, 69-74,
+ *             Vertex.h:13-22).  All fp32, one rounding per operation; a 0/0 stays NaN.
+ *             rt_host_vertex_normals_desc computes exactly this on the host.
+ *   hit       on a triangle of a smooth mesh Hit_data::normal is Mesh_triangle.cpp:101-106 with the
+ *             beta, gamma of HW2/Triangle.cpp:51, 53 (re-derived after the walk from the winning
+ *             leaf and the ray by the arithmetic the walk ran: the same bits):
+ *               w = (1.0f - beta) - gamma;  N = ((n0 * w) + (n1 * beta)) + (n2 * gamma);
+ *               normal = N / length(N)
+ *             every product and sum rounded, no contraction, a true division.  Everything else of
+ *             Scene::trace_ray is HW2's; the smooth normal feeds the diffuse and specular cosines,
+ *             the mirror direction, the entering / leaving test and the refraction.  (The HW3
+ *             program itself renormalises this normal once more in Mesh_instance, Mesh.h:69, so
+ *             its frames differ from this contract in the last bits.)
+ *   entries   rt_trace_rays* report the smooth normal in rt_ray_hit::normal; rt_shade_rays*,
+ *             rt_shade_rays_lit*, rt_film_shade_rays*, rt_render* and MSAA frames shade with it.
+ *             A scene with a smooth mesh renders its frames on the ray-tree path, and to pixel
+ *             records, tile costs and the dispatch order it behaves like a scene that recurses:
+ *             rt_scene_records_ok is 0, RT_TILE_RECORDS is refused, rt_tile_costs has nothing.
+ *   attributes rt_hit_attributes* turn rays and the rt_ray_hit records a closest-hit query gave for
+ *             them into rt_hit_attr records, on any single-device scene (flat ones too): record i
+ *             is computed from ray i and hits[i].leaf alone.  A triangle gives beta, gamma as above,
+ *             uv = ((uv0 * w) + (uv1 * beta)) + (uv2 * gamma) (0 0 without vertex_uv), the shading
+ *             normal (smooth as above, else the flat normal) and the flat normal.  A sphere gives
+ *             (o + d * hits[i].t - center).normalize() for both normals (Sphere.h:57) and beta =
+ *             gamma = 0.  A leaf outside [0, leaves) or an invalid ray gives the all-zero record;
+ *             nothing is read out of bounds whatever the caller passes.
+ *
+ * rays, hits, attr: 16-byte aligned.  n == 0 succeeds and launches nothing; n < 0, a NULL pointer
+ * with n > 0 or a misaligned pointer is RT_E_INVALID before any HIP call.  Multi-device scenes:
+ * RT_E_UNSUPPORTED. */
+#define CENG795_RT_HAS_SURFACE 1
+int rt_surface_version(void); /* 1 */
+
+typedef struct rt_surface_desc {
+  size_t struct_size;                 /* sizeof(rt_surface_desc): room to grow          */
+  const unsigned char* mesh_smooth;   /* [num_meshes], non-zero: tsm_smooth; NULL: none */
+  const float* vertex_normals;        /* fp32[3*num_vertices] used as given (not
+                                         normalised), or NULL: computed by the rule above */
+  const float* vertex_uv;             /* fp32[2*num_vertices] or NULL                   */
+} rt_surface_desc;
+int rt_scene_create_surface(const rt_scene_desc* desc, const rt_surface_desc* surface, int device,
+                            rt_scene** out);
+int rt_scene_load_xml_surface(const char* xml_path, int device, rt_scene** out);
+int rt_scene_has_smooth(const rt_scene* scene);   /* 1 iff some mesh is smooth */
+/* Host-only, touch no HIP API.  rt_host_vertex_normals_desc: the rule above into
+ * out3n[3*num_vertices].  rt_host_mesh_smooth_xml: the scene file's meshes' shadingMode (1: smooth)
+ * into out[min(meshes, capacity)]; returns the number of meshes. */
+int rt_host_vertex_normals_desc(const rt_scene_desc* desc, float* out3n);
+int rt_host_mesh_smooth_xml(const char* xml_path, unsigned char* out, int capacity);
+
+enum { RT_ATTR_HIT = 1, RT_ATTR_TRIANGLE = 2, RT_ATTR_SMOOTH = 4 };
+typedef struct rt_hit_attr {       /* 48 B, 16-byte aligned */
+  float beta, gamma;               /* 0 0: sphere, miss                                */
+  float uv[2];                     /* ((uv0*w) + (uv1*beta)) + (uv2*gamma); 0 0 without vertex_uv */
+  float shading_normal[3]; int flags;  /* RT_ATTR_* */
+  float geometric_normal[3]; int pad;  /* flat normal / the sphere normal              */
+} rt_hit_attr;
+int rt_hit_attributes_device(rt_scene* scene, const rt_ray* d_rays, const rt_ray_hit* d_hits,
+                             long long n, rt_hit_attr* d_attr, void* hip_stream);
+int rt_hit_attributes(rt_scene* scene, const rt_ray* rays, const rt_ray_hit* hits, long long n,
+                      rt_hit_attr* attr);
 
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);

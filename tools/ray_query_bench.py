@@ -18,8 +18,15 @@ tile-order result and the frame in the same run; writes profiles/radiance_query.
 first three do the same work through three paths; every case checked bit for bit against the
 first; writes profiles/radiance_lights.json.  --dry-run (needs no GPU) writes the case list only.
 
+--smooth (with or without --radiance): what smooth shading costs.  The C3 scene
+twice, as it is and with its mesh smooth (shadingMode="smooth", Scene(..., smooth=True)), camera 0's rays in tile
+order through SMOOTH_CASES — closest hits, radiance and rt_hit_attributes_device on both scenes,
+alternated within every round; the flat scene's results checked against the frame, the smooth
+scene's hits against the flat one's in everything but the normal; writes profiles/smooth_query.json.
+--dry-run (needs no GPU) writes the case list only.
+
 usage: ray_query_bench.py [--calls 50] [--warmup 3] [--n 708] [--out PATH] [--check] [--radiance]
-                          [--lights] [--dry-run]
+                          [--lights] [--smooth] [--dry-run]
 """
 from __future__ import annotations
 
@@ -89,6 +96,17 @@ LIGHT_CASES = {
 }
 
 
+# --smooth: name -> (scene, what runs)
+SMOOTH_CASES = {
+    "flat/closest": ("flat", "rt_trace_rays_device"),
+    "smooth/closest": ("smooth", "rt_trace_rays_device"),
+    "flat/radiance": ("flat", "rt_shade_rays_device"),
+    "smooth/radiance": ("smooth", "rt_shade_rays_device"),
+    "flat/attributes": ("flat", "rt_hit_attributes_device"),
+    "smooth/attributes": ("smooth", "rt_hit_attributes_device"),
+}
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--calls", type=int, default=50)
@@ -103,19 +121,26 @@ def main(argv=None) -> int:
                    help="radiance queries (rt_shade_rays_device) instead of hits and occlusion")
     p.add_argument("--lights", action="store_true",
                    help="with --radiance: the cost of caller light records (LIGHT_CASES)")
+    p.add_argument("--smooth", action="store_true",
+                   help="C3 flat against C3 with its mesh smooth (SMOOTH_CASES)")
     p.add_argument("--dry-run", action="store_true",
-                   help="with --radiance --lights: write the case list and stop (no GPU)")
+                   help="with --radiance --lights or --smooth: write the case list and stop (no GPU)")
     p.add_argument("--check", action="store_true",
                    help="also compare every case's results with the row-major ones, bit for bit")
     a = p.parse_args(argv)
     if a.lights and not a.radiance:
         p.error("--lights goes with --radiance")
-    if a.dry_run and not a.lights:
-        p.error("--dry-run goes with --radiance --lights")
+    if a.lights and a.smooth:
+        p.error("--lights and --smooth are separate runs")
+    if a.dry_run and not (a.lights or a.smooth):
+        p.error("--dry-run goes with --radiance --lights or with --smooth")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles",
+                             "smooth_query.json" if a.smooth else
                              "radiance_lights.json" if a.lights else
                              "radiance_query.json" if a.radiance else "ray_query.json")
+    if a.smooth:
+        return smooth_main(a)
     if a.lights:
         return lights_main(a)
     if a.radiance:
@@ -433,6 +458,115 @@ def lights_main(a) -> int:
                         for k in LIGHT_CASES if k != "a_plain"}
     result["bit_identical_to_a_plain"] = checks
     scene.close()
+    write_result(a.out, result)
+    return 0 if all(checks.values()) else 1
+
+
+def smooth_main(a) -> int:
+    """SMOOTH_CASES on camera 0's rays in tile order, alternated within every round."""
+    spec = gen_scene.heightfield_scene(a.n, a.width, a.height, name="c3.png")
+    assert len(spec.meshes) == 1
+    result = {"scene": f"C3: height field {a.n}, camera 0 {a.width}x{a.height}; smooth: the same "
+                       "scene with its one mesh smooth",
+              "rays": a.width * a.height, "order": "tile_8x8", "calls": a.calls,
+              "warmup": a.warmup,
+              "timing": "device events around each call; cases alternated within every round",
+              "case_list": {k: {"scene": v[0], "entry": v[1]} for k, v in SMOOTH_CASES.items()}}
+    if a.dry_run:
+        result["dry_run"] = True
+        write_result(a.out, result)
+        return 0
+
+    import torch
+    import ceng795_amd
+    from ceng795_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU")
+    text = spec.to_xml()
+    assert text.count('<Mesh id="1">') == 1
+    with tempfile.TemporaryDirectory() as d:
+        xml, xml_smooth = os.path.join(d, "c3.xml"), os.path.join(d, "c3_smooth.xml")
+        with open(xml, "w") as f:
+            f.write(text)
+        with open(xml_smooth, "w") as f:
+            f.write(text.replace('<Mesh id="1">', '<Mesh id="1" shadingMode="smooth">'))
+        scenes = {"flat": ceng795_amd.Scene(xml, device=0),
+                  "smooth": ceng795_amd.Scene(xml_smooth, device=0, smooth=True)}
+    assert scenes["smooth"].has_smooth and not scenes["flat"].has_smooth
+    cam = scenes["flat"].camera(0)
+    o, dirs = primary_rays(cam)
+    n = len(dirs)
+    idx = orders(cam.width, cam.height, a.seed)["tile_8x8"]
+    r = ceng795_amd.pack_rays(o[idx], dirs[idx])
+    rays = torch.from_numpy(r.view(np.uint8).reshape(-1)).cuda()
+    hits = {k: torch.zeros(n * 32, dtype=torch.uint8, device="cuda") for k in scenes}
+    rad = {k: torch.zeros(n * 16, dtype=torch.uint8, device="cuda") for k in scenes}
+    attr = {k: torch.zeros(n * 48, dtype=torch.uint8, device="cuda") for k in scenes}
+    frame = torch.zeros((cam.height, cam.width, 3), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(name):
+        which, entry = SMOOTH_CASES[name]
+        s = scenes[which]
+        if entry == "rt_trace_rays_device":
+            s.trace_rays_device(rays.data_ptr(), n, hits[which].data_ptr(), stream=stream)
+        elif entry == "rt_shade_rays_device":
+            s.shade_rays_device(rays.data_ptr(), n, rad[which].data_ptr(), stream=stream)
+        else:  # (the hits of the scene's own closest-hit case)
+            s.hit_attributes_device(rays.data_ptr(), hits[which].data_ptr(), n,
+                                    attr[which].data_ptr(), stream=stream)
+
+    for name in SMOOTH_CASES:
+        run(name)
+    scenes["flat"].render_device(0, frame.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    H = {k: hits[k].cpu().numpy().view(ceng795_amd.HIT_DTYPE) for k in scenes}
+    R = {k: rad[k].cpu().numpy().view(ceng795_amd.RADIANCE_DTYPE) for k in scenes}
+    A = {k: attr[k].cpu().numpy().view(ceng795_amd.HIT_ATTR_DTYPE) for k in scenes}
+    back = np.empty((n, 3), np.float32)
+    back[idx] = R["flat"]["rgb"]
+    hit = H["flat"]["leaf"] >= 0
+    checks = {
+        "flat_radiance_equals_frame": bool(np.array_equal(
+            back.view(np.uint32), frame.cpu().numpy().reshape(n, 3).view(np.uint32))),
+        "same_t_and_leaf": bool(np.array_equal(H["flat"]["t"].view(np.uint32),
+                                               H["smooth"]["t"].view(np.uint32)) and
+                                np.array_equal(H["flat"]["leaf"], H["smooth"]["leaf"])),
+        "smooth_hit_normal_is_the_attribute": bool(np.array_equal(
+            H["smooth"]["normal"].view(np.uint32), A["smooth"]["shading_normal"].view(np.uint32))),
+        "flat_hit_normal_is_the_geometric_normal": bool(np.array_equal(
+            H["flat"]["normal"].view(np.uint32), A["smooth"]["geometric_normal"].view(np.uint32))),
+        "same_barycentrics": bool(np.array_equal(A["flat"][["beta", "gamma"]],
+                                                 A["smooth"][["beta", "gamma"]])),
+    }
+    differing = float((np.abs(H["flat"]["normal"][hit] - H["smooth"]["normal"][hit]).max(axis=1)
+                       > 1e-3).mean())
+    times = {c: [] for c in SMOOTH_CASES}
+    for rnd in range(a.warmup + a.calls):
+        marks = []
+        for c in SMOOTH_CASES:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(c)
+            e1.record()
+            marks.append((c, e0, e1))
+        torch.cuda.synchronize()
+        if rnd >= a.warmup:
+            for c, e0, e1 in marks:
+                times[c].append(e0.elapsed_time(e1))
+    result.update({"lib_sha256": file_sha256(_lib.LIB_PATH),
+                   "device": torch.cuda.get_device_name(0), "hit_share": float(hit.mean()),
+                   "hits_whose_normals_differ_by_1e-3": differing, "cases": {}})
+    for name, ms in times.items():
+        q = quartiles(ms)
+        q["mrays_per_s"] = n / q["ms_median"] / 1e3
+        result["cases"][name] = q
+    c = result["cases"]
+    result["ratios"] = {f"smooth_over_flat_{k}": c[f"smooth/{k}"]["ms_median"] /
+                        c[f"flat/{k}"]["ms_median"] for k in ("closest", "radiance", "attributes")}
+    result["checks"] = checks
+    for s in scenes.values():
+        s.close()
     write_result(a.out, result)
     return 0 if all(checks.values()) else 1
 
