@@ -104,6 +104,12 @@ class rt_surface_desc(C.Structure):
                 ("vertex_normals", C.POINTER(C.c_float)), ("vertex_uv", C.POINTER(C.c_float))]
 
 
+class rt_instance_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("num_instances", C.c_int),
+                ("instance_mesh", C.POINTER(C.c_int)), ("instance_material", C.POINTER(C.c_int)),
+                ("instance_transform", C.POINTER(C.c_float))]
+
+
 RT_ATTR_HIT, RT_ATTR_TRIANGLE, RT_ATTR_SMOOTH = 1, 2, 4  # rt_hit_attr::flags
 
 
@@ -227,6 +233,19 @@ SIGNATURES = {
     "rt_hit_attributes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                            C.c_void_p, C.c_void_p]),
     "rt_hit_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "rt_instances_version": (C.c_int, []),
+    "rt_scene_create_instanced": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
+                                            C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_scene_num_instances": (C.c_int, [C.c_void_p]),
+    "rt_scene_load_xml_instanced": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_host_instances_xml": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_float), C.c_int]),
+    "rt_host_check_accel_instanced_desc": (C.c_int, [C.POINTER(rt_scene_desc),
+                                                     C.POINTER(rt_instance_desc), C.c_int,
+                                                     C.POINTER(C.c_longlong)]),
+    "rt_host_instance_info_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_int)]),
 }
 
 _lib = None

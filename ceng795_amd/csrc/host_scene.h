@@ -86,6 +86,52 @@ void accel_slot_histogram(const HostScene& s, long long hist[kWideSlots + 1]);
 // Builds `out` from `desc`; throws std::invalid_argument on a bad description.
 void build_host_scene(const rt_scene_desc& desc, HostScene& out);
 
+// The part of build_host_scene that copies the description's scalars, materials, lights and
+// cameras (what an instanced scene keeps in its HostScene; it has no flat tree).
+void build_host_globals(const rt_scene_desc& desc, HostScene& out);
+
+// An instanced scene on the host (instances.cpp): one HostScene per base mesh
+// (tree, culling tree, leaves; no globals), the instance records, and the top-level reference
+// tree over instances, loose triangles and spheres in that order (HW3/src/Scene.cpp:706-869).
+struct InstHost {
+  std::vector<HostScene> meshes;
+  std::vector<int> mesh_leaf_base;    // scene-wide leaf id of each mesh's leaf 0
+  std::vector<int> mesh_object_base;  // object-list index of each mesh's face 0
+  std::vector<long long> accel_stats; // 4 per mesh: check_accel's stats (zeros: no culling tree)
+  std::vector<DevInstance> instances;
+  std::vector<float> inverse;         // 16 per instance: the whole inverse matrix
+  std::vector<int> inst_top_dfs;      // per instance: its top-level DFS position
+  std::vector<DevNode> top_nodes;     // leaf children: ~top-level DFS position
+  std::vector<DevPrim> top_prims;     // per position (rt_internal.h InstParams)
+  std::vector<float> top_normals;     // 4 per position
+  std::vector<int> top_info;          // 2 per position: object index, scene-wide leaf id
+  int top_root_kind = kTopNode;
+  int top_depth = 0;                  // internal-node levels of the top-level tree
+  int top_quot_ok = 1;
+  float top_box[6] = {0, 0, 0, 0, 0, 0};
+  bool has_spheres = false;
+  int leaves = 0;                     // scene-wide leaf ids
+};
+// Builds `out` from the description's meshes (bases only) and the instance descriptor; treelets:
+// build_accel's K for every base mesh, each checked with check_accel.  Throws
+// std::invalid_argument on a bad description (a singular matrix among them) and std::domain_error
+// on what instanced scenes do not take (the caller's own BVH, trees deeper than the wave stack).
+void build_instanced(const rt_scene_desc& desc, const rt_instance_desc& inst, int treelets,
+                     InstHost& out);
+
+// load_scene_xml plus the file's instances (instances_xml.cpp): the root <Transformations> block,
+// every <Mesh> as an instance with its own transformation list, then the <MeshInstance>s;
+// vertexOffset is added to the meshes' vertex ids in `st`.  Throws std::domain_error on what
+// instanced scenes do not take (<Transformations> on a <Triangle> or <Sphere>, a non-zero
+// <MotionBlur>, plyFile).
+struct XmlSceneStorage;
+struct XmlInstances {
+  std::vector<int> mesh, material;
+  std::vector<float> transform;  // 16 per instance, row-major
+};
+void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc& desc,
+                        XmlInstances& out);
+
 // Preorder dump in oracle/ref/ref_harness.cpp's format (without the Mesh "M" markers, which
 // the flattened layout splices away).
 std::string dump_bvh(const HostScene& s);

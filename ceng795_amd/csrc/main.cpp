@@ -1,10 +1,12 @@
-// `raytracer [--gpus N] [--reference-traversal] [--smooth] <scene.xml>` — the host driver of
+// `raytracer [--gpus N] [--reference-traversal] [--smooth] [--instanced] <scene.xml>` — the host driver of
 // HW2/main.cpp:10-70 on top of the C ABI: parse the scene, then for every <Camera> render
 // (timed), quantise and write <ImageName>.  The reference spawns hardware_concurrency()
 // threads on render_image (main.cpp:33-36); here one rt_render call renders every row on the
 // GPU, or with --gpus N on N GPUs of the node (rt_scene_load_xml_multi: tiles dealt over the
 // devices, RCCL gather onto the first).  --smooth honours <Mesh shadingMode="smooth"> as the HW3
 // loader does (rt_scene_load_xml_surface; one GPU); without it the attribute is ignored, as in HW2.
+// --instanced honours HW3's <Transformations> and <MeshInstance> (rt_scene_load_xml_instanced; one
+// GPU, flat shading).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -15,7 +17,7 @@
 
 int main(int argc, char** argv) {
   int mode = RT_TRAVERSAL_FAST, gpus = 0;
-  bool smooth = false;
+  bool smooth = false, instanced = false;
   const char* xml = nullptr;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -23,6 +25,8 @@ int main(int argc, char** argv) {
       mode = RT_TRAVERSAL_REFERENCE;
     } else if (a == "--smooth") {
       smooth = true;
+    } else if (a == "--instanced") {
+      instanced = true;
     } else if (a == "--gpus" && i + 1 < argc) {
       gpus = std::atoi(argv[++i]);
     } else {
@@ -37,8 +41,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--smooth renders on one GPU (no --gpus)\n");
     return 1;
   }
+  if (instanced && (gpus > 0 || smooth)) {
+    std::fprintf(stderr, "--instanced renders on one GPU, flat-shaded (no --gpus, no --smooth)\n");
+    return 1;
+  }
   rt_scene* scene = nullptr;
   const int rc = gpus > 0 ? rt_scene_load_xml_multi(xml, gpus, nullptr, &scene)
+                 : instanced ? rt_scene_load_xml_instanced(xml, -1, &scene)
                  : smooth ? rt_scene_load_xml_surface(xml, -1, &scene)
                           : rt_scene_load_xml(xml, -1, &scene);
   if (rc != RT_OK) {

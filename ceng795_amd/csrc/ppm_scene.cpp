@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "mat4.h"
 #include "ppm_host.h"
 #include "xml_dom.h"
 
@@ -43,90 +44,14 @@ float hi_of(float a, float b) { return (a < b) ? b : a; }  // std::max(a, b)
 float comp(Vec v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 
 // ------------------------------------------------------------------ 4x4 matrices (Matrix4x4.cpp)
-struct Mat {
-  float a[4][4];
-  static Mat zero() {
-    Mat m;
-    std::memset(m.a, 0, sizeof m.a);
-    return m;
-  }
-  static Mat identity() {
-    Mat m = zero();
-    for (int i = 0; i < 4; i++) m.a[i][i] = 1.0f;
-    return m;
-  }
-  Mat operator*(const Mat& r) const {  // result[i][j] += a[i][k] * r[k][j], k ascending
-    Mat o = zero();
-    for (int i = 0; i < 4; i++)
-      for (int j = 0; j < 4; j++)
-        for (int k = 0; k < 4; k++) o.a[i][j] += a[i][k] * r.a[k][j];
-    return o;
-  }
-  Mat transposed() const {
-    Mat t;
-    for (int i = 0; i < 4; i++)
-      for (int j = 0; j < 4; j++) t.a[i][j] = a[j][i];
-    return t;
-  }
-  Vec point(Vec v) const {  // multiply(v, false)
-    float r[3];
-    for (int i = 0; i < 3; i++) {
-      r[i] = a[i][3];
-      r[i] += a[i][0] * v.x;
-      r[i] += a[i][1] * v.y;
-      r[i] += a[i][2] * v.z;
-    }
-    return vec(r[0], r[1], r[2]);
-  }
-  bool identity_p() const {
-    for (int i = 0; i < 4; i++)
-      for (int j = 0; j < 4; j++)
-        if (a[i][j] != (i == j ? 1.0f : 0.0f)) return false;
-    return true;
-  }
-  // Matrix4x4::invert_matrix: cofactors as written there, det = 1/det, inv * det.
-  bool inverse(Mat& out) const {
-    float m[16], c[16];
-    for (int k = 0; k < 16; k++) m[k] = a[k / 4][k % 4];
-    c[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] +
-           m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
-    c[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] -
-           m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
-    c[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] +
-           m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
-    c[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] -
-            m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
-    c[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] -
-           m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
-    c[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] +
-           m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
-    c[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] -
-           m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
-    c[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] +
-            m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
-    c[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] +
-           m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
-    c[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] -
-           m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
-    c[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] +
-            m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
-    c[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] -
-            m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
-    c[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] -
-           m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
-    c[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] +
-           m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
-    c[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] -
-            m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
-    c[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] +
-            m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
-    float det = m[0] * c[0] + m[1] * c[4] + m[2] * c[8] + m[3] * c[12];
-    if (det == 0.0f) return false;
-    det = 1.0f / det;
-    for (int k = 0; k < 16; k++) out.a[k / 4][k % 4] = c[k] * det;
-    return true;
-  }
-};
+// (shared with the instanced ray-tracing scenes: mat4.h)
+using Mat = rt::Mat4;
+Vec mat_point(const Mat& m, Vec v) {  // multiply(v, false)
+  const float in[3] = {v.x, v.y, v.z};
+  float r[3];
+  m.point(in, r);
+  return vec(r[0], r[1], r[2]);
+}
 
 struct Transform {  // Transformation.h: M, M^-1, (M^-1)^T
   Mat m = Mat::identity(), inv = Mat::identity(), nrm = Mat::identity();
@@ -160,9 +85,9 @@ BBox transformed(const BBox& b, const Mat& m) {  // Bounding_box::apply_transfor
   const Vec corner[8] = {vec(l.x, l.y, l.z), vec(l.x, l.y, h.z), vec(l.x, h.y, l.z),
                          vec(l.x, h.y, h.z), vec(h.x, l.y, l.z), vec(h.x, l.y, h.z),
                          vec(h.x, h.y, l.z), vec(h.x, h.y, h.z)};
-  Vec mn = m.point(corner[0]), mx = mn;
+  Vec mn = mat_point(m, corner[0]), mx = mn;
   for (int k = 1; k < 8; k++) {
-    const Vec p = m.point(corner[k]);
+    const Vec p = mat_point(m, corner[k]);
     mn = vec(lo_of(mn.x, p.x), lo_of(mn.y, p.y), lo_of(mn.z, p.z));
     mx = vec(hi_of(mx.x, p.x), hi_of(mx.y, p.y), hi_of(mx.z, p.z));
   }

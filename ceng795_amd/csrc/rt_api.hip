@@ -26,7 +26,8 @@
 
 namespace rt {
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
-                         const hipEvent_t* marks, const SurfParams* surf, hipStream_t stream);
+                         const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
+                         hipStream_t stream);
 int max_supported_depth();
 hipError_t launch_msaa_resolve(const MsaaResolveParams& M, hipStream_t stream);
 hipError_t launch_untile(const UntileParams& U, hipStream_t stream);
@@ -46,9 +47,13 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
                         bool reorder, bool fast, bool deep, bool spheres, const SurfParams* surf,
                         hipStream_t stream);
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
+hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstParams& T,
+                             bool occlusion, bool reorder, bool fast, bool spheres,
+                             hipStream_t stream);
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
-                           bool spheres, const SurfParams* surf, hipStream_t stream);
+                           bool spheres, const SurfParams* surf, const InstParams* inst,
+                           hipStream_t stream);
 hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, const AttrParams& A,
                                  hipStream_t stream);
 hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
@@ -171,6 +176,24 @@ struct Replica {
   DevBuf<int> d_surf_tri;
   DevBuf<float> d_surf_normals, d_surf_uv;
   SurfParams surf{nullptr, nullptr, nullptr, 0};
+  // an instanced scene: every base mesh's arrays, the mesh and instance tables
+  // and the top-level tree; `inst` points at them
+  struct MeshBufs {
+    DevBuf<DevNode> nodes;
+    DevBuf<DevPrim> prims;
+    DevBuf<DevLeaf> leaves;
+    DevBuf<float> normals;
+    DevBuf<DevAncestry> anc;
+    DevBuf<int> leaf_object;
+  };
+  std::vector<MeshBufs> d_mesh;
+  DevBuf<DevMesh> d_mesh_table;
+  DevBuf<DevInstance> d_instances;
+  DevBuf<DevNode> d_top_nodes;
+  DevBuf<DevPrim> d_top_prims;
+  DevBuf<float> d_top_normals;
+  DevBuf<int> d_top_info;
+  InstParams inst{};
   DevBuf<unsigned long long> d_counters;
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
   // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
@@ -195,7 +218,12 @@ struct rt_scene {
   // some mesh is smooth (rt_scene_create_surface): frames take the ray-tree path, as a scene that
   // recurses does, and the ray-tree and closest-hit kernels run their SMOOTH instantiations
   bool smooth = false;
-  bool tree_frames() const { return needs_recursion || smooth; }
+  bool tree_frames() const { return needs_recursion || smooth || inst != nullptr; }
+  // made of instances (rt_scene_create_instanced): `host` holds the scene's scalars, materials,
+  // lights and cameras and no tree; the ray queries, the radiance queries and the frames (on the
+  // ray-tree path, like a smooth scene's) run their INST kernels; nothing that reads the flat
+  // tree takes such a scene (hit attributes, pixel records, the BVH dump)
+  std::unique_ptr<InstHost> inst;
   size_t most = 1;         // pixel records of the largest camera frame (whole tiles)
   unsigned long long msaa_seed = 0;
   // bytes of ray-tree frames one chunk of a radiance query may hold (rt_set_radiance_scratch_limit)
@@ -436,6 +464,21 @@ void upload_replica(const rt_scene* s, Replica& r) {
 
 // Builds the culling tree once on the host, then uploads the scene to every device.  Several
 // devices: one RCCL communicator each, for the framebuffer gather (render_multi).
+// What the materials and cameras decide (flat and instanced scenes alike): whether a ray tree can
+// recurse, and the largest frame.
+void scene_shading_state(rt_scene* s) {
+  const HostScene& h = s->host;
+  for (const DevMaterial& m : h.materials) {
+    const bool mirror = m.mirror[0] != 0 || m.mirror[1] != 0 || m.mirror[2] != 0;
+    const bool glass = m.transparency[0] != 0 || m.transparency[1] != 0 || m.transparency[2] != 0;
+    if ((mirror || glass) && h.max_depth > 0) s->needs_recursion = true;
+  }
+  for (const rt_camera& c : h.cameras) {
+    const size_t tiles = (size_t)((c.width + kTile - 1) / kTile) * ((c.height + kTile - 1) / kTile);
+    s->most = std::max(s->most, tiles * kTile * kTile);
+  }
+}
+
 int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
   build_accel(s->host, kDefaultTreeletLeaves);
   if (s->host.accel_depth > max_supported_depth()) build_accel(s->host, 0);
@@ -448,15 +491,7 @@ int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
   s->deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
   for (const DevPrim& p : h.prims) s->has_spheres |= p.kind == kPrimSphere;
   s->smooth = h.smooth;
-  for (const DevMaterial& m : h.materials) {
-    const bool mirror = m.mirror[0] != 0 || m.mirror[1] != 0 || m.mirror[2] != 0;
-    const bool glass = m.transparency[0] != 0 || m.transparency[1] != 0 || m.transparency[2] != 0;
-    if ((mirror || glass) && h.max_depth > 0) s->needs_recursion = true;
-  }
-  for (const rt_camera& c : h.cameras) {
-    const size_t tiles = (size_t)((c.width + kTile - 1) / kTile) * ((c.height + kTile - 1) / kTile);
-    s->most = std::max(s->most, tiles * kTile * kTile);
-  }
+  scene_shading_state(s);
   for (int d : devices) {
     s->rep.push_back(std::make_unique<Replica>());
     s->rep.back()->device = d;
@@ -524,7 +559,7 @@ RenderParams scene_params(const rt_scene* s, const Replica& r) {
   std::memcpy(P.root_box, h.root_box, sizeof P.root_box);
   P.accel_root = h.accel_root;
   P.accel_stride = h.accel_stride;
-  P.quot_ok = h.quot_ok;
+  P.quot_ok = s->inst ? s->inst->top_quot_ok : h.quot_ok;  // (instanced: the loose triangles')
   std::memcpy(P.accel_box, h.accel_box, sizeof P.accel_box);
   P.anc = r.d_anc.p;
   P.occ_words = occ_words(h);
@@ -579,7 +614,7 @@ void limit_rows(RenderParams& P, int rows) {
 // Pixel records (RT_TILE_RECORDS) carry the primary hit and up to kRecMaxLights shadow bits:
 // pixel-centre cameras of scenes without mirror/dielectric recursion.
 bool records_ok(const rt_scene* s, int cam) {
-  return s->host.cameras[cam].num_samples <= 1 && !s->tree_frames() &&
+  return !s->inst && s->host.cameras[cam].num_samples <= 1 && !s->tree_frames() &&
          (int)s->host.lights.size() <= kRecMaxLights;
 }
 
@@ -650,6 +685,8 @@ const hipEvent_t* timing_marks(rt_scene* s, const RenderParams& P) {
 const SurfParams* smooth_surface(const rt_scene* s) {
   return s->smooth ? &s->rep[0]->surf : nullptr;
 }
+// What the INST kernels take: an instanced scene's tables (single-device), else null.
+const InstParams* inst_params(const rt_scene* s) { return s->inst ? &s->rep[0]->inst : nullptr; }
 
 // The sample passes of an MSAA camera (HW2/Scene.cpp:32-69) over P's rows: pass k renders
 // sample k of every selected pixel into d_samples[k] (row-major, full-frame positions).
@@ -667,7 +704,7 @@ void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_s
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
     hip_check(launch_render(Q, fast, s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr,
-                            smooth_surface(s), stream), "render launch");
+                            smooth_surface(s), inst_params(s), stream), "render launch");
   }
 }
 
@@ -695,7 +732,7 @@ void enqueue_frame(rt_scene* s, const RenderParams& P, int samples, float* d_sam
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
     hip_check(launch_render(P, fast, s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr,
-                            smooth_surface(s), stream), "render launch");
+                            smooth_surface(s), inst_params(s), stream), "render launch");
     return;
   }
   enqueue_samples(s, P, samples, d_samples, stream, timed);
@@ -1212,10 +1249,11 @@ QueryParams query_params(const rt_scene* s, const Replica& r) {
   QueryParams Q;
   std::memset(&Q, 0, sizeof Q);
   Q.leaf_object = r.d_leaf_object.p;
-  if (h.root_kind == kRootNode)
+  const float* root_box = s->inst ? s->inst->top_box : h.root_box;
+  if (s->inst ? s->inst->top_root_kind == kTopNode : h.root_kind == kRootNode)
     for (int a = 0; a < 3; a++) {
-      const float ext = h.root_box[a + 3] - h.root_box[a];
-      Q.box_lo[a] = h.root_box[a];
+      const float ext = root_box[a + 3] - root_box[a];
+      Q.box_lo[a] = root_box[a];
       Q.box_scale[a] = ext > 0.0f && std::isfinite(ext) ? 1.0f / ext : 0.0f;  // cells: kernel
     }
   return Q;
@@ -1243,6 +1281,12 @@ void enqueue_hits(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws
     Q.out = static_cast<char*>(q.out) + (size_t)done * stride;
     Q.n = std::min(q.n - done, kQueryMaxLaunch);
     if (reorder) carve_reorder(Q, ws, Q.n);
+    if (s->inst) {
+      hip_check(launch_inst_query(P, Q, r.inst, OCCLUSION, reorder,
+                                  s->mode != RT_TRAVERSAL_REFERENCE, s->has_spheres, stream),
+                "query launch");
+      continue;
+    }
     hip_check(launch_query(P, Q, r.d_nodes.p, OCCLUSION, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
                            s->deep, s->has_spheres, smooth_surface(s), stream),
               "query launch");
@@ -1307,7 +1351,7 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
       C.n = std::min(part, R.first + chunk);
       hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
                                 s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres,
-                                smooth_surface(s), stream),
+                                smooth_surface(s), inst_params(s), stream),
                 "radiance query launch");
     }
   }
@@ -1603,6 +1647,191 @@ int rt_scene_load_xml_surface(const char* xml_path, int device, rt_scene** out) 
 
 int rt_scene_has_smooth(const rt_scene* s) { return s && s->smooth ? 1 : 0; }
 
+int rt_instances_version(void) { return 1; }
+
+int rt_scene_num_instances(const rt_scene* s) {
+  return s && s->inst ? (int)s->inst->instances.size() : 0;
+}
+
+static void check_instance_desc(const char* fn, const rt_instance_desc* in) {
+  if (in && in->struct_size < sizeof(rt_instance_desc))
+    throw std::invalid_argument(std::string(fn) + ": rt_instance_desc::struct_size too small");
+  if (in && in->num_instances < 0)
+    throw std::invalid_argument(std::string(fn) + ": num_instances < 0");
+}
+
+// The instanced scene on its device: every base mesh's arrays, the tables that point at them and
+// the top-level tree.
+static void upload_instanced(rt_scene* s, Replica& r) {
+  DeviceGuard g(r.device);
+  const InstHost& ih = *s->inst;
+  constexpr size_t kPad = 64;  // (as upload_replica)
+  std::vector<DevMesh> table(ih.meshes.size());
+  r.d_mesh.resize(ih.meshes.size());
+  for (size_t m = 0; m < ih.meshes.size(); m++) {
+    const HostScene& h = ih.meshes[m];
+    Replica::MeshBufs& b = r.d_mesh[m];
+    b.nodes = upload(h.nodes, "upload mesh nodes", kPad);
+    b.prims = upload(h.prims, "upload mesh prims", kPad);
+    b.leaves = upload(h.leaves, "upload mesh culling leaves", kPad);
+    b.normals = upload(h.normals, "upload mesh normals", kPad);
+    b.anc = upload(h.ancestry, "upload mesh ancestry", kPad);
+    b.leaf_object = upload(h.leaf_object, "upload mesh leaf objects", 0);
+    DevMesh& dm = table[m];
+    std::memset(&dm, 0, sizeof dm);
+    dm.nodes = b.nodes.p;
+    dm.leaves = b.leaves.p;
+    dm.prims = b.prims.p;
+    dm.anc = b.anc.p;
+    dm.normals = b.normals.p;
+    dm.leaf_object = b.leaf_object.p;
+    dm.root_kind = h.root_kind;
+    dm.root_ref = h.root_ref;
+    // (the rule of use_fast in rt_kernels.hip: a culling tree only over a node root)
+    const bool culled = h.accel_root >= 0 && h.root_kind == kRootNode && !h.leaves.empty();
+    dm.accel_root = culled ? h.accel_root : -1;
+    dm.accel_stride = h.accel_stride;
+    std::memcpy(dm.root_box, h.root_box, sizeof dm.root_box);
+    std::memcpy(dm.accel_box, h.accel_box, sizeof dm.accel_box);
+    dm.quot_ok = h.quot_ok;
+    dm.leaf_base = ih.mesh_leaf_base[m];
+    dm.object_base = ih.mesh_object_base[m];
+  }
+  r.d_mesh_table = upload(table, "upload mesh table", kPad);
+  r.d_instances = upload(ih.instances, "upload instances", kPad);
+  r.d_top_nodes = upload(ih.top_nodes, "upload top-level nodes", kPad);
+  r.d_top_prims = upload(ih.top_prims, "upload top-level primitives", kPad);
+  r.d_top_normals = upload(ih.top_normals, "upload top-level normals", kPad);
+  r.d_top_info = upload(ih.top_info, "upload top-level objects", 0);
+  r.d_mats = upload(s->host.materials, "upload materials", kPad);
+  r.d_lights = upload(s->host.lights, "upload lights", kPad);
+  r.inst.top_nodes = r.d_top_nodes.p;
+  r.inst.top_prims = r.d_top_prims.p;
+  r.inst.top_normals = r.d_top_normals.p;
+  r.inst.top_info = r.d_top_info.p;
+  r.inst.instances = r.d_instances.p;
+  r.inst.meshes = r.d_mesh_table.p;
+  r.inst.top_root_kind = ih.top_root_kind;
+  r.inst.top_quot_ok = ih.top_quot_ok;
+  std::memcpy(r.inst.top_box, ih.top_box, sizeof r.inst.top_box);
+  r.d_counters.reserve(kCounterAlloc, "alloc counters");
+  hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
+}
+
+// An instanced scene from its host parts: s->inst is built.  (Not through create_from_host: there
+// is no flat tree to cull or upload, `deep` stays false — build_instanced refuses deeper trees —
+// and there are no cold orders, which only the fused frame kernel reads.)
+static int create_instanced(rt_scene* s, int device) {
+  const std::vector<int> devs = single_device(device);
+  s->has_spheres = s->inst->has_spheres;
+  scene_shading_state(s);
+  s->rep.push_back(std::make_unique<Replica>());
+  s->rep.back()->device = devs[0];
+  upload_instanced(s, *s->rep.back());
+  return RT_OK;
+}
+
+int rt_scene_create_instanced(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                              int device, rt_scene** out) {
+  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_instanced: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    check_instance_desc("rt_scene_create_instanced", instances);
+    if (!instances || instances->num_instances == 0) {  // rt_scene_create's scene
+      const std::vector<int> devs = single_device(device);
+      build_host_scene(*desc, s->host);
+      return create_from_host(s.get(), devs, false);
+    }
+    s->inst = std::make_unique<InstHost>();
+    build_host_globals(*desc, s->host);
+    build_instanced(*desc, *instances, kDefaultTreeletLeaves, *s->inst);
+    return create_instanced(s.get(), device);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_scene_load_xml_instanced(const char* xml_path, int device, rt_scene** out) {
+  if (!xml_path || !out)
+    return set_error(RT_E_INVALID, "rt_scene_load_xml_instanced: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    XmlSceneStorage st;
+    XmlInstances xi;
+    rt_scene_desc d;
+    load_instances_xml(xml_path, st, d, xi);
+    s->host.image_names = st.image_names;
+    if (xi.mesh.empty()) {  // no <Mesh>: rt_scene_load_xml's scene
+      const std::vector<int> devs = single_device(device);
+      build_host_scene(d, s->host);
+      return create_from_host(s.get(), devs, false);
+    }
+    const rt_instance_desc in{sizeof(rt_instance_desc), (int)xi.mesh.size(), xi.mesh.data(),
+                              xi.material.data(), xi.transform.data()};
+    s->inst = std::make_unique<InstHost>();
+    build_host_globals(d, s->host);
+    build_instanced(d, in, kDefaultTreeletLeaves, *s->inst);
+    return create_instanced(s.get(), device);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_host_instances_xml(const char* xml_path, int* mesh, int* material, float* transform16,
+                          int capacity) {
+  if (!xml_path || capacity < 0)
+    return set_error(RT_E_INVALID, "rt_host_instances_xml: bad argument");
+  return guarded([&] {
+    XmlSceneStorage st;
+    XmlInstances xi;
+    rt_scene_desc d;
+    load_instances_xml(xml_path, st, d, xi);
+    const int n = (int)xi.mesh.size(), k = std::min(n, capacity);
+    for (int i = 0; i < k; i++) {
+      if (mesh) mesh[i] = xi.mesh[i];
+      if (material) material[i] = xi.material[i];
+    }
+    if (transform16) std::memcpy(transform16, xi.transform.data(), 16 * (size_t)k * sizeof(float));
+    return n;
+  });
+}
+
+int rt_host_check_accel_instanced_desc(const rt_scene_desc* desc,
+                                       const rt_instance_desc* instances, int treelet_leaves,
+                                       long long* stats4) {
+  if (!desc || !instances)
+    return set_error(RT_E_INVALID, "rt_host_check_accel_instanced_desc: NULL argument");
+  return guarded([&] {
+    check_instance_desc("rt_host_check_accel_instanced_desc", instances);
+    InstHost ih;
+    build_instanced(*desc, *instances, treelet_leaves, ih);
+    if (stats4) std::memcpy(stats4, ih.accel_stats.data(), ih.accel_stats.size() * sizeof(long long));
+    return (int)ih.meshes.size();
+  });
+}
+
+int rt_host_instance_info_desc(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                               float* inverse16, float* box6, int* top_dfs) {
+  if (!desc || !instances)
+    return set_error(RT_E_INVALID, "rt_host_instance_info_desc: NULL argument");
+  return guarded([&] {
+    check_instance_desc("rt_host_instance_info_desc", instances);
+    InstHost ih;
+    build_instanced(*desc, *instances, kDefaultTreeletLeaves, ih);
+    const size_t n = ih.instances.size();
+    if (inverse16) std::memcpy(inverse16, ih.inverse.data(), 16 * n * sizeof(float));
+    for (size_t i = 0; i < n; i++) {
+      if (box6) std::memcpy(box6 + 6 * i, ih.instances[i].box, 6 * sizeof(float));
+      if (top_dfs) top_dfs[i] = ih.inst_top_dfs[i];
+    }
+    return RT_OK;
+  });
+}
+
 int rt_host_vertex_normals_desc(const rt_scene_desc* desc, float* out3n) {
   if (!desc || (!out3n && desc->num_vertices > 0))
     return set_error(RT_E_INVALID, "rt_host_vertex_normals_desc: NULL argument");
@@ -1636,6 +1865,7 @@ static void check_attr_args(const char* fn, const rt_scene* s, const void* rays,
   if (!s) throw std::invalid_argument(f + ": scene is NULL");
   if (s->multi)
     throw std::domain_error(f + ": hit attributes on multi-device scenes are not supported");
+  if (s->inst) throw std::domain_error(f + ": hit attributes on instanced scenes are not supported");
 }
 
 int rt_hit_attributes_device(rt_scene* s, const rt_ray* d_rays, const rt_ray_hit* d_hits,
@@ -1702,6 +1932,8 @@ const char* rt_scene_image_name(const rt_scene* s, int cam) {
 
 int rt_scene_dump_bvh(const rt_scene* s, const char* path) {
   if (!s || !path) return set_error(RT_E_INVALID, "rt_scene_dump_bvh: NULL argument");
+  if (s->inst)
+    return set_error(RT_E_UNSUPPORTED, "rt_scene_dump_bvh: not for instanced scenes");
   FILE* f = std::fopen(path, "w");
   if (!f) return set_error(RT_E_IO, std::string("cannot open ") + path);
   const std::string d = dump_bvh(s->host);

@@ -563,6 +563,50 @@ struct SurfArg {};
 template <>
 struct SurfArg<true> : SurfParams {};
 
+// Instanced scenes (rt_scene_create_instanced).  The top-level reference tree
+// (top_nodes, DevNode records whose leaf children are ~top-level DFS position) holds the
+// instances and the loose primitives; top_prims[pos] is the loose primitive at that position, or
+// for an instance a record of kind kPrimInstance whose `material` is the instance index.  Each
+// base mesh is a scene of its own (DevMesh: the fields of RenderParams a walk reads), entered with
+// the ray taken through the instance's inverse matrix.  The instance kernels take InstParams as
+// an argument of their own; no other kernel's argument list changes.
+constexpr int32_t kPrimInstance = 2;
+struct alignas(16) DevInstance {
+  float inv[12];  // rows 0..2 of the inverse matrix, four columns each
+  float box[6];   // Bounding_box::apply_transform of the base mesh's root box
+  int32_t mesh, material;
+  int32_t pad[4];
+};
+static_assert(sizeof(DevInstance) == 96, "instance record is six 16-byte words");
+struct alignas(16) DevMesh {
+  const DevNode* nodes;
+  const DevLeaf* leaves;
+  const DevPrim* prims;
+  const DevAncestry* anc;
+  const float* normals;    // float4 per mesh leaf
+  const int* leaf_object;  // per mesh leaf: the face's index within the mesh
+  int32_t root_kind, root_ref, accel_root, accel_stride;  // accel_root < 0: no culling tree
+  float root_box[6];
+  float accel_box[6];
+  int32_t quot_ok;
+  int32_t leaf_base;    // scene-wide leaf id of the mesh's leaf 0
+  int32_t object_base;  // object-list index of the mesh's face 0
+  int32_t pad;
+};
+static_assert(sizeof(DevMesh) == 128, "mesh record is two 64-byte scalar loads");
+enum : int32_t { kTopNode = 0, kTopSingle = 1 };
+struct InstParams {
+  const DevNode* top_nodes;
+  const DevPrim* top_prims;
+  const float* top_normals;  // float4 per top-level position (loose triangles: the flat normal)
+  const int* top_info;       // int2 per top-level position: object index, scene-wide leaf id
+  const DevInstance* instances;
+  const DevMesh* meshes;
+  int top_root_kind;         // kTopNode, or kTopSingle: the list is the one object at position 0
+  int top_quot_ok;           // quot_coord_ok of every loose triangle's v0
+  float top_box[6];
+};
+
 // rt_hit_attributes*: rays, hits and attr hold n records each.
 struct AttrParams {
   const void* rays;

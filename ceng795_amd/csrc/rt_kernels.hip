@@ -21,6 +21,7 @@
 // / log are the fp64 ocml functions, matching the reference's double libm islands.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 #include <vector>
@@ -1902,6 +1903,224 @@ __device__ __forceinline__ bool refract_ray(V3 dir, V3 n, float idx, V3& out) {
   return true;
 }
 
+// ------------------------------------------------------------------ instanced scenes
+__device__ __forceinline__ bool query_ray_ok(V3 o, V3 d);  // (below, with the ray queries)
+// A two-level walk.  The wave walks the TOP-LEVEL reference tree over the
+// instances and the loose primitives with visit_node / advance and the exact box rule.  A loose
+// primitive is tested in place.  An instance is wave-uniform: its record and its base mesh's
+// descriptor come by scalar loads, the lanes that reached it test its world box (one more
+// ancestor box) and take their ray through the inverse matrix — Matrix4x4::multiply's order, every
+// product and sum rounded, the direction not normalised, so the local t is the world t — and the
+// wave calls the ordinary closest_hit / occluded on a RenderParams view of the base mesh with only
+// those lanes active.  The inner walk owns L.key and its own stack; the outer best
+// (t, top-level position, mesh leaf) stays in registers.  A local ray that is no valid query ray
+// misses the instance.
+__device__ __forceinline__ V3 inst_point(const float* e, V3 p) {  // multiply(p, false), rows 0..2
+  return v3(((e[3] + e[0] * p.x) + e[1] * p.y) + e[2] * p.z,
+            ((e[7] + e[4] * p.x) + e[5] * p.y) + e[6] * p.z,
+            ((e[11] + e[8] * p.x) + e[9] * p.y) + e[10] * p.z);
+}
+__device__ __forceinline__ V3 inst_vector(const float* e, V3 d) {  // multiply(d, true)
+  return v3(((0.0f + e[0] * d.x) + e[1] * d.y) + e[2] * d.z,
+            ((0.0f + e[4] * d.x) + e[5] * d.y) + e[6] * d.z,
+            ((0.0f + e[8] * d.x) + e[9] * d.y) + e[10] * d.z);
+}
+// The normal matrix is the inverse's transpose: row i of it is column i of `e`.
+__device__ __forceinline__ V3 inst_normal(const float* e, V3 n) {
+  return v3(((0.0f + e[0] * n.x) + e[4] * n.y) + e[8] * n.z,
+            ((0.0f + e[1] * n.x) + e[5] * n.y) + e[9] * n.z,
+            ((0.0f + e[2] * n.x) + e[6] * n.y) + e[10] * n.z);
+}
+
+// The records of a reached instance and of its base mesh by scalar loads, as load_node8 takes a
+// wide node: the kernel stores results, so the compiler would fetch them per lane.  (The first 16
+// words of a DevInstance are its matrix rows and box[0..3]; the next 8 the rest.)
+typedef int v8i __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void load_instance(const DevInstance* __restrict__ instances, int index,
+                                              v16i& a, v8i& b) {
+  const unsigned off = (unsigned)index * (unsigned)sizeof(DevInstance), off2 = off + 64u;
+  asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b) : "s"(instances), "s"(off), "s"(off2) : "memory");
+}
+__device__ __forceinline__ DevNode load_top_node(const DevNode* __restrict__ nodes, int index) {
+  const unsigned off = (unsigned)index << 6;
+  v16i a;
+  asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a) : "s"(nodes), "s"(off) : "memory");
+  return __builtin_bit_cast(DevNode, a);
+}
+template <typename T>
+__device__ __forceinline__ const T* word_pointer(int lo, int hi) {
+  return reinterpret_cast<const T*>(((uint64_t)(unsigned)hi << 32) | (uint64_t)(unsigned)lo);
+}
+
+// The base mesh as the scene a walk sees: a, b the two halves of its DevMesh record.
+__device__ __forceinline__ RenderParams mesh_view(const RenderParams& P, const v16i& a,
+                                                  const v16i& b) {
+  RenderParams V = P;
+  V.nodes = word_pointer<DevNode>(a[0], a[1]);
+  V.leaves = word_pointer<DevLeaf>(a[2], a[3]);
+  V.prims = word_pointer<DevPrim>(a[4], a[5]);
+  V.anc = word_pointer<DevAncestry>(a[6], a[7]);
+  V.normals = word_pointer<float>(a[8], a[9]);
+  V.root_kind = a[12];
+  V.root_ref = a[13];
+  V.accel_root = a[14];
+  V.accel_stride = a[15];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    V.root_box[k] = __int_as_float(b[k]);
+    V.accel_box[k] = __int_as_float(b[6 + k]);
+  }
+  V.quot_ok = b[12];
+  return V;
+}
+static_assert(offsetof(DevMesh, root_kind) == 48 && offsetof(DevMesh, root_box) == 64 &&
+              offsetof(DevMesh, quot_ok) == 112 && offsetof(DevInstance, box) == 48 &&
+              offsetof(DevInstance, mesh) == 72, "the word indices above");
+
+// OCC == false: the closest hit of every valid lane's ray w — bt, and btop / bleaf (the top-level
+// position and, under an instance, the mesh leaf; -1: a miss).  OCC == true: returns whether some
+// reachable primitive has 0 < t < thr; a lane found occluded leaves the walk.
+template <bool FAST, bool SPHERES, bool OCC>
+__device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParams& T,
+                                          WaveLeafLds& L, const LaneRay& w, bool valid, float thr,
+                                          float& bt, int& btop, int& bleaf, Diag& dg) {
+  bt = RT_INF;
+  btop = -1;
+  bleaf = -1;
+  bool occ = false;
+  if (OCC) valid = valid && thr > 0.0f;  // thr <= 0 (or NaN): nothing satisfies 0 < t < thr
+  const bool lone = T.top_root_kind != kTopNode;  // the list is one object: its own rule
+  uint64_t m, alive = ~0ull;
+  int node = -1;
+  if (lone) {
+    m = ballot(valid);
+  } else {
+    float tn;
+    bool acc, und;
+    slab_fast<true>(T.top_box, w, tn, acc, und);
+    m = ballot(valid && (acc || (und && box_exact(T.top_box, w))));
+    node = 0;
+  }
+  if (!m) return false;
+  WaveStack<false> st;
+  for (;;) {
+    int q0 = lone ? 0 : -1, q1 = -1;  // the top-level leaves the lanes of m test at this step
+    int c0 = -1, c1 = -1;
+    uint64_t m0 = 0ull, m1 = 0ull;
+    float t0 = 0.0f, t1 = 0.0f;
+    if (!lone) {
+      const DevNode N = load_top_node(T.top_nodes, node);
+      bool h0, h1;
+      visit_node<true>(N, w, lane_in(m), h0, h1, t0, t1);
+      c0 = N.child[0];
+      c1 = N.child[1];
+      // a leaf child has no box: every lane in the node tests it; inner children are entered
+      if (c0 < 0) q0 = ~c0; else m0 = ballot(h0) & alive;
+      if (c1 < 0) q1 = ~c1; else m1 = ballot(h1) & alive;
+    }
+#pragma nounroll
+    for (int k = 0; k < 2; k++) {
+      const int pos = k ? q1 : q0;
+      if (pos < 0) continue;
+      const bool in = lane_in(m & alive);
+      const DevPrim* __restrict__ tp = T.top_prims + pos;
+      const int kind = uniform(tp->kind);
+      float t = RT_INF;
+      int leaf = -1;
+      bool hit;
+      if (kind == kPrimInstance) {
+        v16i ia, ma, mb;
+        v8i ib;
+        load_instance(T.instances, uniform(tp->material), ia, ib);
+        load_node8(reinterpret_cast<const DevNode*>(T.meshes), 2 * ib[2], ma, mb);  // (128 B each)
+        float inv[12];
+#pragma unroll
+        for (int e = 0; e < 12; e++) inv[e] = __int_as_float(ia[e]);
+        const float box[6] = {__int_as_float(ia[12]), __int_as_float(ia[13]),
+                              __int_as_float(ia[14]), __int_as_float(ia[15]),
+                              __int_as_float(ib[0]), __int_as_float(ib[1])};
+        float tn;
+        bool acc, und;
+        slab_fast<true>(box, w, tn, acc, und);
+        const bool boxed = in && (acc || (und && box_exact(box, w)));
+        V3 lo = inst_point(inv, w.o), ld = inst_vector(inv, w.d);
+        const bool go = boxed && query_ray_ok(lo, ld);
+        if (!ballot(go)) continue;
+        if (!go) {  // an idle lane still takes part in the wave-wide steps: a harmless ray
+          lo = v3(0.0f, 0.0f, 0.0f);
+          ld = v3(0.0f, 0.0f, 1.0f);
+        }
+        const RenderParams V = mesh_view(P, ma, mb);
+        const LaneRay lr = make_ray(lo, ld, V.quot_ok);
+        if (OCC) {
+          bool o;
+          if (FAST && V.accel_root >= 0)
+            o = occluded<true, true, false, false>(V, V.nodes, nullptr, L, lr, go, thr, dg);
+          else
+            o = occluded<true, false, false, false>(V, V.nodes, nullptr, L, lr, go, thr, dg);
+          occ |= go && o;
+          hit = false;
+        } else {
+          if (FAST && V.accel_root >= 0)
+            closest_hit<true, true, false, false>(V, V.nodes, nullptr, L, lr, go, t, leaf, dg);
+          else
+            closest_hit<true, false, false, false>(V, V.nodes, nullptr, L, lr, go, t, leaf, dg);
+          // (0 < t by the leaf test; a one-face mesh's lone-root answer may still be t = inf,
+          // which the top-level tree's leaf rule rejects)
+          hit = go && leaf >= 0 && (lone || t < RT_INF);
+        }
+      } else {
+        hit = in && leaf_test<SPHERES>(T.top_prims, pos, w, t);
+        // in the tree: the leaf rule 0 < t < inf; the lone object: its own answer as it is
+        if (!lone) hit = hit && t > 0.0f && t < RT_INF;
+        if (OCC) {
+          occ |= hit && t > 0.0f && t < thr;
+          hit = false;
+        }
+      }
+      // HW2/HW3 BVH::intersect over the top level: the smaller t, at equal t the earlier leaf
+      if (!OCC && hit && (t < bt || btop < 0 || (t == bt && pos < btop))) {
+        bt = t;
+        btop = pos;
+        bleaf = leaf;
+      }
+    }
+    if (lone) break;
+    if (OCC) {
+      alive &= ~ballot(occ);
+      m0 &= alive;
+      m1 &= alive;
+    }
+    if (!advance(st, c0, c1, m0, m1, t0, t1, node, m, alive)) break;
+  }
+  return occ;
+}
+
+
+// What the ray-tree code takes for an instanced scene: nothing in the flat instantiations (NoInst,
+// the default: their code is that of a build without instances), the scene's InstParams in the
+// INST ones, where every closest hit and every shadow ray goes through inst_walk and
+// Hit_data::normal / the material come from the instance (Mesh.h:69) or the loose primitive.
+struct NoInst {
+  static constexpr bool on = false;
+};
+struct InstArg {
+  static constexpr bool on = true;
+  InstParams T;
+};
+// A shadow ray of an instanced scene's local shading.
+template <bool FAST, bool SPHERES>
+__device__ __forceinline__ bool inst_occluded(const RenderParams& P, const InstArg& inst,
+                                              WaveLeafLds& L, const LaneRay& sr, bool active,
+                                              float thr, Diag& dg, std::bool_constant<FAST>,
+                                              std::bool_constant<SPHERES>) {
+  float t;
+  int top, leaf;
+  return inst_walk<FAST, SPHERES, true>(P, inst.T, L, sr, active, thr, t, top, leaf, dg);
+}
+
 // Local shading of one hit (ambient + point lights with shadow rays), Scene.cpp:107-139.
 // Wave-uniform: every lane calls it; `shade` selects the lanes that shade (hit, !in_medium).
 // LIT (rt_shade_rays_lit*): after the scene's lights, the lane's own `own_k`
@@ -1909,14 +2128,14 @@ __device__ __forceinline__ bool refract_ray(V3 dir, V3 n, float idx, V3& out) {
 // not finite is absent; a light no shading lane of the wave has is skipped wave-wide.  A record
 // with a non-zero normal is a sample of an emitter: both terms carry dot(-w_i, normal)
 // (HW3/src/Scene.cpp:207-218), chosen per lane behind a select.
-template <bool FAST, bool DEEP, bool SPHERES, bool LIT = false>
+template <bool FAST, bool DEEP, bool SPHERES, bool LIT = false, typename Inst = NoInst>
 __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* __restrict__ nodes,
                                           const DevPrim* __restrict__ prims,
                                           const DevMaterial* __restrict__ mats,
                                           const DevLight* __restrict__ lights, int* spill, WaveLeafLds& L,
                                           bool shade, V3 o, V3 p, V3 n, int mat, Diag& dg,
                                           unsigned long long& shadow_rays, const f4* own = nullptr,
-                                          int own_k = 0) {
+                                          int own_k = 0, const Inst& inst = Inst{}) {
   V3 color = v3(0.0f, 0.0f, 0.0f);
   const DevMaterial& m = mats[shade ? mat : 0];
   if (shade) color = color + ld3(m.ambient) * ld3(P.ambient);
@@ -1928,9 +2147,15 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
     const float dist = length(ld);
     const LaneRay sr = make_ray(p + wi * P.eps, wi, P.quot_ok);
     const float thr = dist - P.eps;
-    const bool sskip = ballot(shade && (sr.skip0 || sr.skip1 || sr.skip2)) != 0;
-    const bool occ = sskip ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, shade, thr, dg)
-                           : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, shade, thr, dg);
+    bool occ;
+    if constexpr (Inst::on) {
+      occ = inst_occluded(P, inst, L, sr, shade, thr, dg, std::bool_constant<FAST>{},
+                          std::bool_constant<SPHERES>{});
+    } else {
+      const bool sskip = ballot(shade && (sr.skip0 || sr.skip1 || sr.skip2)) != 0;
+      occ = sskip ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, shade, thr, dg)
+                  : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, shade, thr, dg);
+    }
     shadow_rays += __builtin_popcountll(ballot(shade));
     if (shade && !occ) {
       const V3 I = ld3(lt.intensity);
@@ -1957,9 +2182,15 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
       const float dist = length(ld);
       const LaneRay sr = make_ray(p + wi * P.eps, wi, P.quot_ok);
       const float thr = dist - P.eps;
-      const bool sskip = ballot(lit && (sr.skip0 || sr.skip1 || sr.skip2)) != 0;
-      const bool occ = sskip ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg)
-                             : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg);
+      bool occ;
+      if constexpr (Inst::on) {
+        occ = inst_occluded(P, inst, L, sr, lit, thr, dg, std::bool_constant<FAST>{},
+                            std::bool_constant<SPHERES>{});
+      } else {
+        const bool sskip = ballot(lit && (sr.skip0 || sr.skip1 || sr.skip2)) != 0;
+        occ = sskip ? occluded<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg)
+                    : occluded<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, sr, lit, thr, dg);
+      }
       shadow_rays += __builtin_popcountll(ballot(lit));
       if (lit && !occ) {
         const V3 I = v3(b.x, b.y, b.z), en = v3(c.x, c.y, c.z);
@@ -1996,7 +2227,7 @@ struct TreeCounts {
 // SMOOTH: the scene has a smooth mesh; a hit on one of its faces takes the interpolated vertex
 // normal (triangle_normal) wherever Hit_data::normal is read.
 template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true, bool LIT = false,
-          bool SMOOTH = false>
+          bool SMOOTH = false, typename Inst = NoInst>
 __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          const DevPrim* __restrict__ prims,
                                          const float* __restrict__ normals,
@@ -2005,7 +2236,8 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
                                          WaveLeafLds& L, float* frames, size_t stride, V3 ro, V3 rd,
                                          bool medium, int depth, bool active, float& t_first,
                                          TreeCounts& cnt, const SurfArg<SMOOTH>& surf,
-                                         const f4* own = nullptr, int own_k = 0) {
+                                         const f4* own = nullptr, int own_k = 0,
+                                         const Inst& inst = Inst{}) {
   auto frame = [&](int level) {
     return FrameRef{frames + (size_t)level * kFrFields * stride, stride};
   };
@@ -2017,10 +2249,13 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
   t_first = RT_INF;
   while (ballot(active)) {
     const LaneRay ray = make_ray(ro, rd, P.quot_ok);
-    const bool skip = ballot(active && (ray.skip0 || ray.skip1 || ray.skip2)) != 0;
+    const bool skip = !Inst::on && ballot(active && (ray.skip0 || ray.skip1 || ray.skip2)) != 0;
     float t;
     int leaf;
-    if (skip)
+    [[maybe_unused]] int mesh_leaf = -1;  // INST: `leaf` is the top-level position
+    if constexpr (Inst::on)
+      inst_walk<FAST, SPHERES, false>(P, inst.T, L, ray, active, 0.0f, t, leaf, mesh_leaf, dg);
+    else if (skip)
       closest_hit<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, active, t, leaf, dg);
     else
       closest_hit<false, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, active, t, leaf, dg);
@@ -2034,15 +2269,28 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
     int mat = 0;
     if (hit) {
       p = ray.o + ray.d * t;
-      const DevPrim& pr = prims[leaf];
-      n = pr.kind == kPrimTriangle
-              ? triangle_normal<SMOOTH>(surf, pr, leaf, ray, ld3(normals + 4 * leaf))
-              : normalize(p - ld3(pr.v0));
-      mat = pr.material;
+      if constexpr (Inst::on) {
+        const DevPrim& pr = inst.T.top_prims[leaf];
+        if (pr.kind == kPrimInstance) {  // Mesh.h:69: the instance's normal matrix and material
+          const DevInstance& I = inst.T.instances[pr.material];
+          n = normalize(inst_normal(I.inv, ld3(inst.T.meshes[I.mesh].normals + 4 * mesh_leaf)));
+          mat = I.material;
+        } else {
+          n = pr.kind == kPrimTriangle ? ld3(inst.T.top_normals + 4 * leaf)
+                                       : normalize(p - ld3(pr.v0));
+          mat = pr.material;
+        }
+      } else {
+        const DevPrim& pr = prims[leaf];
+        n = pr.kind == kPrimTriangle
+                ? triangle_normal<SMOOTH>(surf, pr, leaf, ray, ld3(normals + 4 * leaf))
+                : normalize(p - ld3(pr.v0));
+        mat = pr.material;
+      }
     }
-    const V3 local = local_color<FAST, DEEP, SPHERES, LIT>(P, nodes, prims, mats, lights, spill, L,
-                                                           hit && !medium, ray.o, p, n, mat, dg,
-                                                           n_shadow, own, own_k);
+    const V3 local = local_color<FAST, DEEP, SPHERES, LIT, Inst>(
+        P, nodes, prims, mats, lights, spill, L, hit && !medium, ray.o, p, n, mat, dg, n_shadow, own,
+        own_k, inst);
     if constexpr (!RECURSE) {  // the one ray of the tree (a miss: Scene.cpp:96-99)
       if (hit)
         out = local;
@@ -2175,7 +2423,7 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
   return out;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename Inst = NoInst>
 __device__ __forceinline__ void recursive_packet(const RenderParams& P,
                                                  const DevNode* __restrict__ nodes,
                                                  const DevPrim* __restrict__ prims,
@@ -2183,7 +2431,8 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
                                                  const DevMaterial* __restrict__ mats,
                                                  const DevLight* __restrict__ lights, int sel,
                                                  int* spill, WaveLeafLds& L,
-                                                 const SurfArg<SMOOTH>& surf) {
+                                                 const SurfArg<SMOOTH>& surf,
+                                                 const Inst& inst = Inst{}) {
   const PacketPixel q = packet_pixel(P, sel);
   const size_t lanes_total = (size_t)P.num_sel_tiles * (kTile * kTile);
   const size_t g = (size_t)sel * (kTile * kTile) + q.lane;
@@ -2191,9 +2440,9 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
   float t_first;
   TreeCounts cnt;
   // the camera's pixel ray at the scene's maximum depth
-  const V3 out = trace_tree<FAST, DEEP, SPHERES, true, false, SMOOTH>(
+  const V3 out = trace_tree<FAST, DEEP, SPHERES, true, false, SMOOTH, Inst>(
       P, nodes, prims, normals, mats, lights, spill, L, P.frames + g, lanes_total, ld3(P.cam_e),
-      primary_dir(P, q.px, q.py), false, P.max_depth, q.valid, t_first, cnt, surf);
+      primary_dir(P, q.px, q.py), false, P.max_depth, q.valid, t_first, cnt, surf, nullptr, 0, inst);
   const unsigned long long n_hits = cnt.hits, n_shadow = cnt.shadow, n_secondary = cnt.secondary;
   if (q.valid) {
     float* o;
@@ -2527,6 +2776,20 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void recursive_kernel(
   int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
   recursive_packet<FAST, DEEP, SPHERES, SMOOTH>(P, nodes, prims, normals, mats, lights, sel, spill,
                                                 leaf_lds[threadIdx.x >> 6], surf_of(surf...));
+}
+
+// recursive_kernel for an instanced scene: the same packets and ray trees, every
+// walk through inst_walk.  (No DEEP variant: instanced scenes' trees fit the wave stack.)
+template <bool FAST, bool SPHERES>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void inst_recursive_kernel(
+    RenderParams P, const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights,
+    InstArg inst) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  const int sel = packet_index<kWavesPerBlock>();
+  if (sel >= P.num_sel_tiles) return;
+  recursive_packet<FAST, false, SPHERES, false, InstArg>(P, nullptr, nullptr, nullptr, mats, lights,
+                                                        sel, nullptr, leaf_lds[threadIdx.x >> 6],
+                                                        surf_of(), inst);
 }
 
 // marks (nullable): 4 events recorded before the frame kernel (or the recursive kernel), after
@@ -2987,6 +3250,68 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void query_occluded_kernel(
     reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ instanced scenes: the query kernels
+// (inst_walk and InstArg: before local_color)
+template <bool FAST, bool SPHERES>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void inst_closest_kernel(RenderParams P,
+                                                                           QueryParams Q,
+                                                                           InstParams T) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, T.top_quot_ok);
+  Diag dg;
+  float t;
+  int top, leaf;
+  inst_walk<FAST, SPHERES, false>(P, T, L, ray, q.valid, 0.0f, t, top, leaf, dg);
+  f4 h0 = {RT_INF, __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)};
+  f4 h1 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (q.valid && top >= 0) {
+    const DevPrim& pr = T.top_prims[top];
+    if (pr.kind == kPrimInstance) {
+      // Mesh.h:69: normalT.multiply(flat normal, true).normalize(); the instance's material
+      const DevInstance& I = T.instances[pr.material];
+      const DevMesh& M = T.meshes[I.mesh];
+      const V3 n = normalize(inst_normal(I.inv, ld3(M.normals + 4 * leaf)));
+      h0 = (f4){t, __int_as_float(M.object_base + M.leaf_object[leaf]),
+                __int_as_float(I.material), __int_as_float(M.leaf_base + leaf)};
+      h1 = (f4){n.x, n.y, n.z, __int_as_float(pr.material)};
+    } else {
+      const V3 n = !SPHERES || pr.kind == kPrimTriangle
+                       ? ld3(T.top_normals + 4 * top)
+                       : normalize((ray.o + ray.d * t) - ld3(pr.v0));
+      h0 = (f4){t, __int_as_float(T.top_info[2 * top]), __int_as_float(pr.material),
+                __int_as_float(T.top_info[2 * top + 1])};
+      h1 = (f4){n.x, n.y, n.z, __int_as_float(-1)};
+    }
+  }
+  const long long i = query_index();
+  if (i < Q.n) {
+    f4* out = reinterpret_cast<f4*>(Q.out) + 2 * query_slot(Q, i);
+    out[0] = h0;
+    out[1] = h1;
+  }
+}
+
+template <bool FAST, bool SPHERES>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void inst_occluded_kernel(RenderParams P,
+                                                                            QueryParams Q,
+                                                                            InstParams T) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, T.top_quot_ok);
+  Diag dg;
+  float t;
+  int top, leaf;
+  const bool occ = inst_walk<FAST, SPHERES, true>(P, T, L, ray, q.valid, q.tmax, t, top, leaf, dg);
+  const long long i = query_index();
+  if (i < Q.n)
+    reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
+}
+
 // Radiance of caller-supplied rays (rt_shade_rays_device): the layout of
 // query_closest_kernel, and between the lane's two 16-B loads and its one 16-B store the ray tree
 // of trace_tree from (o, d, R.in_medium, R.depth).  One launch covers the rays
@@ -3039,6 +3364,46 @@ __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void que
       own_k);
   if (i < Q.n) {
     // Pixel::add_color(color, 1) onto a zeroed pixel; an invalid ray: (0, 0, 0, +inf)
+    const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
+    reinterpret_cast<f4*>(Q.out)[query_slot(Q, i)] = out;
+  }
+  if (P.counters) {
+    unsigned long long* row = counter_row(P, (int)((i >> 6) % kCounterSlots));
+    if (cnt.secondary) atomicAdd(&row[kCntSecondary], cnt.secondary);
+    if (lane_id() == 0) {
+      atomicAdd(&row[kCntPrimary], n_primary);
+      atomicAdd(&row[kCntHits], cnt.hits);
+      atomicAdd(&row[kCntShadow], cnt.shadow);
+    }
+  }
+}
+
+// query_radiance_kernel for an instanced scene.
+template <bool FAST, bool SPHERES, bool RECURSE, bool LIT>
+__global__ __launch_bounds__(kRadianceWaves * 64) void inst_radiance_kernel(
+    RenderParams P, QueryParams Q, RadianceParams R, const DevMaterial* __restrict__ mats,
+    const DevLight* __restrict__ lights, LitArg<LIT> lit, InstArg inst) {
+  __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
+  const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;
+  const long long i = R.first + slot;
+  if ((i & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_query_ray(Q, i);
+  const unsigned long long n_primary = __builtin_popcountll(ballot(q.valid));
+  float t;
+  TreeCounts cnt;
+  const f4* own = nullptr;
+  int own_k = 0;
+  if constexpr (LIT) {
+    const long long ray = q.in && !lit.shared ? query_slot(Q, i) : 0;
+    own = reinterpret_cast<const f4*>(lit.lights) + 3 * (size_t)ray * (size_t)lit.k;
+    own_k = lit.k;
+  }
+  const V3 c = trace_tree<FAST, false, SPHERES, RECURSE, LIT, false, InstArg>(
+      P, nullptr, nullptr, nullptr, mats, lights, nullptr, L, RECURSE ? R.frames + slot : nullptr,
+      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, surf_of(), own, own_k,
+      inst);
+  if (i < Q.n) {
     const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
     reinterpret_cast<f4*>(Q.out)[query_slot(Q, i)] = out;
   }
@@ -3239,6 +3604,31 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
   return hipGetLastError();
 }
 
+// launch_query for an instanced scene.  fast: the base meshes that have a
+// culling tree are walked through it; spheres: the top level holds a loose sphere.
+hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstParams& T,
+                             bool occlusion, bool reorder, bool fast, bool spheres,
+                             hipStream_t stream) {
+  if (Q.n <= 0) return hipSuccess;
+  Q.perm = nullptr;
+  if (reorder) {
+    const hipError_t e = launch_query_sort(Q, stream);
+    if (e != hipSuccess) return e;
+    Q.perm = Q.perm_out;
+  }
+  const dim3 grid((unsigned)((Q.n + kWavesPerBlock * 64 - 1) / (kWavesPerBlock * 64)));
+  dispatch_variant(fast, false, spheres, [&](auto fa, auto, auto sp) {
+    constexpr bool F = decltype(fa)::value, S = decltype(sp)::value;
+    if (occlusion)
+      hipLaunchKernelGGL((inst_occluded_kernel<F, S>), grid, dim3(kWavesPerBlock * 64), 0, stream,
+                         P, Q, T);
+    else
+      hipLaunchKernelGGL((inst_closest_kernel<F, S>), grid, dim3(kWavesPerBlock * 64), 0, stream,
+                         P, Q, T);
+  });
+  return hipGetLastError();
+}
+
 // The permutation of Q's rays [0, Q.n) into Q.perm_out (RT_QUERY_REORDER), for launches that
 // trace the batch in chunks afterwards (launch_radiance).
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
@@ -3262,9 +3652,36 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
 // cannot recurse.
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
-                           bool spheres, const SurfParams* surf, hipStream_t stream) {
+                           bool spheres, const SurfParams* surf, const InstParams* inst,
+                           hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
   const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
+  if (inst) {  // an instanced scene: the INST kernels (fast: the base meshes' culling trees)
+    const InstArg ia{*inst};
+    dispatch_variant(fast, false, spheres, [&](auto fa, auto, auto sp) {
+      constexpr bool F = decltype(fa)::value, S = decltype(sp)::value;
+      auto launch = [&](auto re, auto li, auto arg) {
+        hipLaunchKernelGGL((inst_radiance_kernel<F, S, decltype(re)::value, decltype(li)::value>),
+                           grid, dim3(kRadianceWaves * 64), 0, stream, P, Q, R, P.materials,
+                           P.lights, arg, ia);
+      };
+      using T = std::true_type;
+      using N = std::false_type;
+      if (lit) {
+        LitArg<true> arg;
+        static_cast<LitParams&>(arg) = *lit;
+        if (R.frames == nullptr)
+          launch(N{}, T{}, arg);
+        else
+          launch(T{}, T{}, arg);
+      } else if (R.frames == nullptr) {
+        launch(N{}, N{}, LitArg<false>{});
+      } else {
+        launch(T{}, N{}, LitArg<false>{});
+      }
+    });
+    return hipGetLastError();
+  }
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
     constexpr bool F = decltype(fa)::value, D = decltype(de)::value, S = decltype(sp)::value;
     const size_t lds = deep_lds_bytes<D>(kRadianceWaves);
@@ -3470,9 +3887,24 @@ hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,
 }
 
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
-                         const hipEvent_t* marks, const SurfParams* surf, hipStream_t stream) {
+                         const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
+                         hipStream_t stream) {
   if (P.num_sel_tiles <= 0) return hipSuccess;
   const int blocks = (P.num_sel_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (inst) {  // an instanced scene renders on the ray-tree path (P.frames: the host sees to it)
+    if (!P.frames) return hipErrorInvalidValue;
+    const InstArg ia{*inst};
+    mark(marks, 0, stream);
+    dispatch_variant(fast, false, spheres, [&](auto fa, auto, auto sp) {
+      hipLaunchKernelGGL((inst_recursive_kernel<decltype(fa)::value, decltype(sp)::value>),
+                         dim3(blocks), dim3(kWavesPerBlock * 64), 0, stream, P, P.materials,
+                         P.lights, ia);
+    });
+    mark(marks, 1, stream);
+    mark(marks, 2, stream);
+    mark(marks, 3, stream);
+    return hipGetLastError();
+  }
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
     launch_variant<decltype(fa)::value, decltype(de)::value, decltype(sp)::value>(
         P, blocks, marks, surf, stream);

@@ -349,7 +349,7 @@ void adopt_tree(const rt_scene_desc& d, HostScene& s, const std::vector<LeafSour
 
 }  // namespace
 
-void build_host_scene(const rt_scene_desc& d, HostScene& s) {
+void build_host_globals(const rt_scene_desc& d, HostScene& s) {
   if (d.num_vertices < 0 || d.num_materials < 0 || d.num_lights < 0 || d.num_cameras < 0 ||
       d.num_meshes < 0 || d.num_triangles < 0 || d.num_spheres < 0)
     fail("negative count in scene description");
@@ -383,6 +383,10 @@ void build_host_scene(const rt_scene_desc& d, HostScene& s) {
   for (const rt_camera& c : s.cameras)
     if (c.width <= 0 || c.height <= 0 || c.num_samples <= 0) fail("bad camera resolution");
   if (s.image_names.size() != s.cameras.size()) s.image_names.assign(s.cameras.size(), "");
+}
+
+void build_host_scene(const rt_scene_desc& d, HostScene& s) {
+  build_host_globals(d, s);
 
   auto vtx = [&](int i) -> F3 {
     if (i < 0 || i >= d.num_vertices) fail("vertex index out of range");

@@ -95,9 +95,14 @@ class Scene:
     """
 
     def __init__(self, file_name: str, device: int = -1, traversal: str = "fast",
-                 devices: Optional[list] = None, smooth: bool = False):
+                 devices: Optional[list] = None, smooth: bool = False, instanced: bool = False):
         h = C.c_void_p()
-        if devices is not None:
+        if instanced:  # <Transformations> / <MeshInstance> honoured (rt_scene_load_xml_instanced)
+            if smooth or devices is not None:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED, "instanced scenes are single-device "
+                                   "and flat-shaded")
+            check(lib().rt_scene_load_xml_instanced(str(file_name).encode(), device, C.byref(h)))
+        elif devices is not None:
             if smooth:
                 raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
                                    "smooth shading on multi-device scenes is not supported")
@@ -113,10 +118,26 @@ class Scene:
 
     @classmethod
     def create(cls, desc, mesh_smooth=None, vertex_normals=None, vertex_uv=None,
-               device: int = -1) -> "Scene":
+               device: int = -1, instance_mesh=None, instance_material=None,
+               instance_transform=None) -> "Scene":
         """A scene from an ``rt_scene_desc`` with surface data (rt_scene_create_surface):
         ``mesh_smooth`` one flag per mesh, ``vertex_normals`` (num_vertices, 3) used as given
-        (None: the area-weighted normals of the HW3 loader), ``vertex_uv`` (num_vertices, 2)."""
+        (None: the area-weighted normals of the HW3 loader), ``vertex_uv`` (num_vertices, 2).
+
+        Or a scene made of instances (rt_scene_create_instanced): ``instance_mesh`` and
+        ``instance_material`` (n,) and ``instance_transform`` (n, 4, 4) object -> world; the
+        description's meshes are then bases only.  Not together with surface data."""
+        given = [a is not None for a in (instance_mesh, instance_material, instance_transform)]
+        if any(given) and not all(given):
+            raise ValueError("instance_mesh, instance_material and instance_transform go together")
+        if instance_mesh is not None:
+            if mesh_smooth is not None or vertex_normals is not None or vertex_uv is not None:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
+                                   "surface data in instanced scenes is not supported")
+            inst, keep = _instance_desc(instance_mesh, instance_material, instance_transform)
+            h = C.c_void_p()
+            check(lib().rt_scene_create_instanced(C.byref(desc), C.byref(inst), device, C.byref(h)))
+            return cls._from_handle(h)
         surf = _lib.rt_surface_desc()
         surf.struct_size = C.sizeof(_lib.rt_surface_desc)
         keep = []
@@ -320,6 +341,11 @@ class Scene:
 
     # ------------------------------------------------------------------ hit attributes
     @property
+    def num_instances(self) -> int:
+        """Instances of the scene (rt_scene_num_instances); 0: a flat scene."""
+        return lib().rt_scene_num_instances(self._h)
+
+    @property
     def has_smooth(self) -> bool:
         """Some mesh of the scene is smooth-shaded (rt_scene_has_smooth)."""
         return bool(lib().rt_scene_has_smooth(self._h))
@@ -479,6 +505,51 @@ def host_vertex_normals(desc) -> np.ndarray:
     out = np.zeros((max(0, desc.num_vertices), 3), np.float32)
     check(lib().rt_host_vertex_normals_desc(C.byref(desc), out.ctypes.data_as(C.POINTER(C.c_float))))
     return out
+
+
+def _instance_desc(instance_mesh, instance_material, instance_transform):
+    """An ``rt_instance_desc`` over the three arrays, and the arrays it points into."""
+    mesh = np.ascontiguousarray(instance_mesh, np.int32).reshape(-1)
+    mat = np.ascontiguousarray(instance_material, np.int32).reshape(-1)
+    xf = np.ascontiguousarray(instance_transform, np.float32).reshape(-1)
+    if mat.size != mesh.size or xf.size != 16 * mesh.size:
+        raise ValueError("instance_material needs n values and instance_transform n x 4 x 4")
+    inst = _lib.rt_instance_desc()
+    inst.struct_size = C.sizeof(_lib.rt_instance_desc)
+    inst.num_instances = mesh.size
+    inst.instance_mesh = mesh.ctypes.data_as(C.POINTER(C.c_int))
+    inst.instance_material = mat.ctypes.data_as(C.POINTER(C.c_int))
+    inst.instance_transform = xf.ctypes.data_as(C.POINTER(C.c_float))
+    return inst, (mesh, mat, xf)
+
+
+def host_instance_info(desc, instance_mesh, instance_material, instance_transform):
+    """Host-only (rt_host_instance_info_desc): per instance its inverse matrix (n, 4, 4), its world
+    box (n, 6: min xyz, max xyz) and its DFS position among the top-level leaves (n,)."""
+    inst, keep = _instance_desc(instance_mesh, instance_material, instance_transform)
+    n = inst.num_instances
+    inverse = np.zeros((n, 4, 4), np.float32)
+    box = np.zeros((n, 6), np.float32)
+    top = np.zeros(n, np.int32)
+    check(lib().rt_host_instance_info_desc(C.byref(desc), C.byref(inst),
+                                           inverse.ctypes.data_as(C.POINTER(C.c_float)),
+                                           box.ctypes.data_as(C.POINTER(C.c_float)),
+                                           top.ctypes.data_as(C.POINTER(C.c_int))))
+    return inverse, box, top
+
+
+def host_instances_xml(xml_path: str):
+    """Host-only (rt_host_instances_xml): the scene file's instances as the instanced loader makes
+    them — (mesh (n,), material (n,), transform (n, 4, 4)): every <Mesh> with its own
+    transformation, then the <MeshInstance>s."""
+    path = str(xml_path).encode()
+    n = check(lib().rt_host_instances_xml(path, None, None, None, 0))
+    mesh, mat = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    xf = np.zeros((n, 4, 4), np.float32)
+    check(lib().rt_host_instances_xml(path, mesh.ctypes.data_as(C.POINTER(C.c_int)),
+                                      mat.ctypes.data_as(C.POINTER(C.c_int)),
+                                      xf.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return mesh, mat, xf
 
 
 def host_mesh_smooth(xml_path: str) -> np.ndarray:

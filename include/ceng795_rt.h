@@ -733,6 +733,90 @@ int rt_hit_attributes_device(rt_scene* scene, const rt_ray* d_rays, const rt_ray
 int rt_hit_attributes(rt_scene* scene, const rt_ray* rays, const rt_ray_hit* hits, long long n,
                       rt_hit_attr* attr);
 
+/* ---- Mesh instances: transformed meshes through a two-level walk ------------------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_INSTANCES / rt_instances_version).
+ * A scene can be made of INSTANCES: a base mesh, a material and a 4x4 transformation each, beside
+ * loose triangles and spheres — HW3's Mesh_instance (HW3/include/Mesh.h:55-74, static branch)
+ * under HW2's Scene::trace_ray.  The reference transforms the ray, not the vertices, and so does
+ * this: 1000 copies of a mesh cost 1000 instance records, and the bits are the reference's.
+ *
+ *   objects   In an instanced scene the description's meshes are bases only: a mesh is reached only
+ *             through instances and mesh_material is ignored.  The top-level object list is the
+ *             instances in order, then the loose triangles, then the spheres
+ *             (HW3/src/Scene.cpp:706-869), under the reference's median-split BVH; each base mesh
+ *             has its own tree over its faces (Mesh::Mesh; a one-face mesh is that triangle).
+ *             A NULL instance descriptor, or num_instances == 0, gives rt_scene_create's scene.
+ *   matrices  instance_transform is object -> world, row-major.  Its inverse is
+ *             Matrix4x4::invert_matrix (HW3/src/Matrix4x4.cpp:99-235: cofactors in that order,
+ *             fp32); a zero determinant is RT_E_INVALID (the reference exits).  The normal matrix
+ *             is the inverse's transpose.  The instance's box is Bounding_box::apply_transform
+ *             (HW3/src/bounding_box.cpp:40-114) of the base mesh's root box.
+ *   hit       ray (o, d) meets an instance as Mesh.h:55-74 has it: (1) the world ray against the
+ *             instance box by the node rule (bbox_t < 0 || bbox_t == inf: a miss); (2) the local
+ *             ray o' = inverse.multiply(o), d' = inverse.multiply(d, true) (Matrix4x4.cpp:29-49:
+ *             per row from e[i][3] for a point, from 0.0f for a vector, then + e[i][0] x,
+ *             + e[i][1] y, + e[i][2] z, every product and sum rounded); d' is not normalised, so
+ *             the local t is the world t; (3) the mesh's closest hit for (o', d') from t = inf;
+ *             (4) normal = normalT.multiply(n, true) / its length, n the flat normal; the material
+ *             is the instance's.  An identity transformation takes this path too.
+ *             Over the top level the result is the minimum of (t, top-level DFS leaf, mesh DFS
+ *             leaf) over what the ray may reach; a one-object list is that object's own rule.
+ *             Occlusion: some reachable primitive, through an instance or not, has 0 < t < tmax.
+ *   departure a local ray that is no valid query ray (a non-finite component of o' or d', or all
+ *             three |d'_i| < 1e-6) misses that instance and disturbs nothing.
+ *   rt_ray_hit  t, normal as above; material the instance's; object the face's index in the object
+ *             lists (mesh faces in mesh order, then loose triangles, then spheres); leaf a
+ *             scene-wide leaf id: each base mesh's leaves in its DFS order, meshes in order, then
+ *             the loose primitives in object-list order; pad the instance index, -1 for a loose
+ *             primitive.  Flat scenes write what they always wrote.
+ *   entries   rt_trace_rays*, rt_occluded*, rt_shade_rays*, rt_shade_rays_lit*,
+ *             rt_film_*shade_rays* and rt_render* (MSAA frames included) take an instanced scene,
+ *             in both traversal modes (the same bits) and with RT_QUERY_REORDER.  Like a smooth
+ *             scene it renders its frames on the ray-tree path and behaves like a recursing scene
+ *             elsewhere: rt_scene_records_ok is 0, RT_TILE_RECORDS is refused, rt_tile_costs has
+ *             nothing.  RT_E_UNSUPPORTED with a message: rt_hit_attributes* and rt_scene_dump_bvh
+ *             on an instanced scene, the caller's own BVH (bvh_*) with instances, multi-device
+ *             scenes, a top-level or base-mesh tree deeper than 62 levels. */
+#define CENG795_RT_HAS_INSTANCES 1
+int rt_instances_version(void); /* 1 */
+
+typedef struct rt_instance_desc {
+  size_t struct_size;              /* sizeof(rt_instance_desc): room to grow            */
+  int num_instances;
+  const int*   instance_mesh;      /* [n] 0-based mesh of the description               */
+  const int*   instance_material;  /* [n]                                               */
+  const float* instance_transform; /* fp32[16 n], row-major 4x4, object -> world        */
+} rt_instance_desc;
+int rt_scene_create_instanced(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                              int device, rt_scene** out);
+/* rt_scene_load_xml with the file's instances honoured (rt_scene_load_xml itself keeps ignoring
+ * all of it): the root <Transformations> block (Scaling, Translation, Rotation in degrees:
+ * HW3/src/Transformation.cpp:6-72 with the host's std::cos / std::sin), per-object lists such as
+ * "s1 t2 r1", each element left-multiplying (Scene.cpp:641-664); <Mesh> k becomes instance k with
+ * its own transformation and material, then each <MeshInstance baseMeshId resetTransform> with its
+ * material (Scene.cpp:713-761); vertexOffset is honoured, shadingMode ignored.
+ * RT_E_UNSUPPORTED: <Transformations> on a <Triangle> or <Sphere>, a non-zero <MotionBlur>,
+ * plyFile.  rt_host_instances_xml (host-only, touches no HIP API) writes the first
+ * min(n, capacity) instances' mesh, material and matrix (any output may be NULL) and returns n. */
+int rt_scene_load_xml_instanced(const char* xml_path, int device, rt_scene** out);
+int rt_host_instances_xml(const char* xml_path, int* mesh, int* material, float* transform16,
+                          int capacity);
+/* Host-only: builds every base mesh's culling tree (treelets of <= treelet_leaves leaves) and
+ * checks the invariants of rt_host_check_accel_xml on each; stats4[4 m ..] = mesh m's treelets,
+ * culling nodes, culling-tree depth, lone-leaf treelets (NULL: not reported).  Returns the number
+ * of base meshes, or RT_E_INVALID with the violation in rt_last_error(). */
+int rt_host_check_accel_instanced_desc(const rt_scene_desc* desc,
+                                       const rt_instance_desc* instances, int treelet_leaves,
+                                       long long* stats4);
+int rt_scene_num_instances(const rt_scene* scene);   /* 0: a flat scene */
+/* Host-only, touches no HIP API: per instance its inverse matrix (row-major 4x4), its world box
+ * (min xyz, max xyz) and its DFS position among the top-level leaves.  Any output may be NULL.
+ * Also builds and checks every base mesh's culling tree (RT_E_INVALID with the violation). */
+int rt_host_instance_info_desc(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                               float* inverse16 /*[16 n]*/, float* box6 /*[6 n]*/,
+                               int* top_dfs /*[n]*/);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 

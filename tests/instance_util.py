@@ -1,0 +1,683 @@
+"""Reference for instanced scenes, composed from the existing oracle.
+
+An instanced scene is HW3's Mesh_instance (HW3/include/Mesh.h:55-74, static branch) under HW2's
+Scene::trace_ray.  The composite holds one OracleScene per base mesh (an XML with that mesh alone)
+and one per loose primitive, and restates in numpy fp32 what lies between them:
+
+    invert_matrix      HW3/src/Matrix4x4.cpp:99-235 (cofactors in that order)
+    multiply           Matrix4x4.cpp:29-49 (point / vector)
+    apply_transform    HW3/src/bounding_box.cpp:40-114
+    slab rule          HW2/bounding_box.cpp:15-35 and the caller's `t < 0 || t == inf` reject
+    top-level BVH      HW2/Bounding_volume_hierarchy.cpp:3-29 over instances, triangles, spheres
+
+A ray's hit is the lexicographic minimum of (t, top-level DFS leaf) over the objects it may
+reach; under an instance the oracle's own closest hit of the local ray.  Every operation is one
+numpy float32 operation, so every intermediate rounds once, as in the reference's SSE build."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+
+import desc_xml
+from scenes import G
+
+F = np.float32
+INF = F(np.inf)
+EPS = F(0.000001)  # HW2/Vector3.h kEpsilon
+
+
+# ------------------------------------------------------------------ matrices (fp32, one rounding each)
+def invert_matrix(mat):
+    """Matrix4x4::invert_matrix; None when the determinant is 0."""
+    m = np.asarray(mat, F).reshape(16)
+    c = np.zeros(16, F)
+
+    def s6(terms):  # ((((a - b) - c) + d) + e) - f, each term a*b*c left to right, signed
+        acc = None
+        for sign, i, j, k in terms:
+            first = -m[i] if (acc is None and sign < 0) else m[i]
+            p = F(F(first * m[j]) * m[k])
+            if acc is None:
+                acc = p
+            elif sign > 0:
+                acc = F(acc + p)
+            else:
+                acc = F(acc - p)
+        return acc
+
+    P, N = 1, -1
+    c[0] = s6([(P, 5, 10, 15), (N, 5, 11, 14), (N, 9, 6, 15), (P, 9, 7, 14), (P, 13, 6, 11), (N, 13, 7, 10)])
+    c[4] = s6([(N, 4, 10, 15), (P, 4, 11, 14), (P, 8, 6, 15), (N, 8, 7, 14), (N, 12, 6, 11), (P, 12, 7, 10)])
+    c[8] = s6([(P, 4, 9, 15), (N, 4, 11, 13), (N, 8, 5, 15), (P, 8, 7, 13), (P, 12, 5, 11), (N, 12, 7, 9)])
+    c[12] = s6([(N, 4, 9, 14), (P, 4, 10, 13), (P, 8, 5, 14), (N, 8, 6, 13), (N, 12, 5, 10), (P, 12, 6, 9)])
+    c[1] = s6([(N, 1, 10, 15), (P, 1, 11, 14), (P, 9, 2, 15), (N, 9, 3, 14), (N, 13, 2, 11), (P, 13, 3, 10)])
+    c[5] = s6([(P, 0, 10, 15), (N, 0, 11, 14), (N, 8, 2, 15), (P, 8, 3, 14), (P, 12, 2, 11), (N, 12, 3, 10)])
+    c[9] = s6([(N, 0, 9, 15), (P, 0, 11, 13), (P, 8, 1, 15), (N, 8, 3, 13), (N, 12, 1, 11), (P, 12, 3, 9)])
+    c[13] = s6([(P, 0, 9, 14), (N, 0, 10, 13), (N, 8, 1, 14), (P, 8, 2, 13), (P, 12, 1, 10), (N, 12, 2, 9)])
+    c[2] = s6([(P, 1, 6, 15), (N, 1, 7, 14), (N, 5, 2, 15), (P, 5, 3, 14), (P, 13, 2, 7), (N, 13, 3, 6)])
+    c[6] = s6([(N, 0, 6, 15), (P, 0, 7, 14), (P, 4, 2, 15), (N, 4, 3, 14), (N, 12, 2, 7), (P, 12, 3, 6)])
+    c[10] = s6([(P, 0, 5, 15), (N, 0, 7, 13), (N, 4, 1, 15), (P, 4, 3, 13), (P, 12, 1, 7), (N, 12, 3, 5)])
+    c[14] = s6([(N, 0, 5, 14), (P, 0, 6, 13), (P, 4, 1, 14), (N, 4, 2, 13), (N, 12, 1, 6), (P, 12, 2, 5)])
+    c[3] = s6([(N, 1, 6, 11), (P, 1, 7, 10), (P, 5, 2, 11), (N, 5, 3, 10), (N, 9, 2, 7), (P, 9, 3, 6)])
+    c[7] = s6([(P, 0, 6, 11), (N, 0, 7, 10), (N, 4, 2, 11), (P, 4, 3, 10), (P, 8, 2, 7), (N, 8, 3, 6)])
+    c[11] = s6([(N, 0, 5, 11), (P, 0, 7, 9), (P, 4, 1, 11), (N, 4, 3, 9), (N, 8, 1, 7), (P, 8, 3, 5)])
+    c[15] = s6([(P, 0, 5, 10), (N, 0, 6, 9), (N, 4, 1, 10), (P, 4, 2, 9), (P, 8, 1, 6), (N, 8, 2, 5)])
+    det = F(F(F(F(m[0] * c[0]) + F(m[1] * c[4])) + F(m[2] * c[8])) + F(m[3] * c[12]))
+    if det == 0:
+        return None
+    det = F(F(1.0) / det)
+    return (c * det).astype(F).reshape(4, 4)
+
+
+def multiply(mat, v, is_vector=False):
+    """Matrix4x4::multiply over rows of v (n, 3): per row i from e[i][3] (point) or 0 (vector),
+    then + e[i][0] x, + e[i][1] y, + e[i][2] z."""
+    e = np.asarray(mat, F).reshape(4, 4)
+    v = np.asarray(v, F).reshape(-1, 3)
+    out = np.zeros_like(v)
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            r = np.full(len(v), F(0.0) if is_vector else e[i][3], F)
+            for j in range(3):
+                r = (r + (e[i][j] * v[:, j]).astype(F)).astype(F)
+            out[:, i] = r
+    return out
+
+
+def apply_transform(box, mat):
+    """Bounding_box::apply_transform: the corners 000 001 010 011 100 101 110 111 (x slowest)
+    through multiply(point), fmin / fmax folded in that order."""
+    lo, hi = np.asarray(box[:3], F), np.asarray(box[3:], F)
+    corners = np.array([[(hi if k & 4 else lo)[0], (hi if k & 2 else lo)[1], (hi if k & 1 else lo)[2]]
+                        for k in range(8)], F)
+    p = multiply(mat, corners)
+    mn, mx = p[0].copy(), p[0].copy()
+    for k in range(1, 8):
+        mn, mx = np.fmin(mn, p[k]), np.fmax(mx, p[k])
+    return np.concatenate([mn, mx]).astype(F)
+
+
+def slab_accept(box, o, d):
+    """Bounding_box::intersect of rays (n, 3) and the callers' reject `t < 0 || t == inf`."""
+    n = len(o)
+    tmin, tmax = np.full(n, -INF, F), np.full(n, INF, F)
+    dead = np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            use = ~(np.abs(d[:, i]) < EPS) & ~dead
+            t0 = ((F(box[i]) - o[:, i]).astype(F) / d[:, i]).astype(F)
+            t1 = ((F(box[i + 3]) - o[:, i]).astype(F) / d[:, i]).astype(F)
+            neg = d[:, i] < 0
+            t0, t1 = np.where(neg, t1, t0), np.where(neg, t0, t1)
+            tmin = np.where(use & (t0 > tmin), t0, tmin)
+            tmax = np.where(use & (t1 < tmax), t1, tmax)
+            dead |= use & (tmin > tmax)
+        bt = np.where(dead, INF, np.where(tmin > 0, tmin, tmax))
+        return ~((bt < 0) | (bt == INF))
+
+
+def ray_ok(o, d):
+    """The query-ray rule: every component finite and not all three |d_i| < 1e-6."""
+    tiny = (np.abs(d) < EPS).all(axis=1)
+    return np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & ~tiny
+
+
+# ------------------------------------------------------------------ the top-level tree
+def _mid(box):
+    return ((box[3:] + box[:3]).astype(F) / F(2)).astype(F)
+
+
+def top_level_tree(boxes):
+    """The median-split BVH over `boxes` (n, 6).  Returns (order, paths): the objects in DFS leaf
+    order, and per DFS position the boxes of its ancestors from the root down."""
+    boxes = [np.asarray(b, F) for b in boxes]
+    order, paths = [], []
+    if len(boxes) == 1:
+        return [0], [[]]
+
+    def union(ids):
+        lo = np.full(3, INF, F)
+        hi = np.full(3, -INF, F)
+        for i in ids:
+            lo, hi = np.fmin(lo, boxes[i][:3]), np.fmax(hi, boxes[i][3:])
+        return np.concatenate([lo, hi]).astype(F)
+
+    def build(ids, axis, above):
+        box = union(ids)
+        split = _mid(box)[axis]
+        ids = list(ids)
+        m = 0
+        for i in range(len(ids)):
+            if _mid(boxes[ids[i]])[axis] < split:
+                ids[i], ids[m] = ids[m], ids[i]
+                m += 1
+        if m == 0 or m == len(ids):
+            m = len(ids) // 2
+        here = above + [box]
+        for part in (ids[:m], ids[m:]):
+            if len(part) == 1:
+                order.append(part[0])
+                paths.append(here)
+            else:
+                build(part, (axis + 1) % 3, here)
+
+    build(list(range(len(boxes))), 0, [])
+    return order, paths
+
+
+# ------------------------------------------------------------------ scenes
+@dataclass
+class InstSpec:
+    """Base meshes (lists of 0-based vertex triples), instances (mesh, material, 4x4), loose
+    triangles (material, (i0, i1, i2)) and spheres (material, centre vertex, radius) over one
+    vertex list; materials and lights as tools/gen_scene.py takes them (material ids 0-based)."""
+    vertices: list
+    meshes: list
+    instances: list
+    triangles: list = field(default_factory=list)
+    spheres: list = field(default_factory=list)
+    materials: list = field(default_factory=lambda: [G.Material((1, 1, 1), (0.8, 0.6, 0.4), (0.2, 0.2, 0.2), phong=4)])
+    lights: list = field(default_factory=lambda: [((1.0, 2.0, 5.0), (200, 200, 200))])
+    camera: object = None
+    max_depth: int = 0
+
+    def _spec(self, meshes, triangles, spheres):
+        cam = self.camera or G.Camera((0, 0, 5), (0, 0, -1), (0, 1, 0), (-1, 1, -1, 1), 1, 17, 9, "i.png")
+        text = "\n".join(" ".join(repr(float(x)) for x in v) for v in self.vertices)
+        return G.SceneSpec(
+            cameras=[cam], ambient=(20, 20, 20), lights=self.lights, materials=self.materials,
+            vertex_text=text, max_depth=self.max_depth,
+            meshes=[(1, "\n".join(" ".join(str(i + 1) for i in f) for f in m)) for m in meshes],
+            triangles=[(m + 1, tuple(i + 1 for i in t)) for m, t in triangles],
+            spheres=[(m + 1, c + 1, r) for m, c, r in spheres])
+
+    def write(self, directory, tag):
+        """XML files under `directory`: <tag>_all.xml (every mesh and loose primitive, flat: the
+        description's geometry), <tag>_mesh<k>.xml and <tag>_loose<k>.xml (one object each)."""
+        def put(name, spec):
+            path = os.path.join(directory, f"{tag}_{name}.xml")
+            with open(path, "w") as f:
+                f.write(spec.to_xml())
+            return path
+        self.all_xml = put("all", self._spec(self.meshes, self.triangles, self.spheres))
+        self.mesh_xml = [put(f"mesh{k}", self._spec([m], [], [])) for k, m in enumerate(self.meshes)]
+        loose = [([t], []) for t in self.triangles] + [([], [s]) for s in self.spheres]
+        self.loose_xml = [put(f"loose{k}", self._spec([], t, s)) for k, (t, s) in enumerate(loose)]
+        return self
+
+    def arrays(self):
+        return (np.array([i[0] for i in self.instances], np.int32),
+                np.array([i[1] for i in self.instances], np.int32),
+                np.array([i[2] for i in self.instances], F).reshape(-1, 4, 4))
+
+    def baked(self):
+        """The same geometry as a flat InstSpec-free SceneSpec: every instance's mesh as a <Mesh>
+        of its own, vertices as they are — only right when every transformation is the identity."""
+        return self._spec([self.meshes[i[0]] for i in self.instances], self.triangles, self.spheres)
+
+
+@dataclass
+class Hits:
+    hit: np.ndarray
+    t: np.ndarray
+    object: np.ndarray
+    material: np.ndarray
+    leaf: np.ndarray
+    inst: np.ndarray    # rt_ray_hit::pad: the instance, -1 for a loose primitive
+    top: np.ndarray     # the winning top-level DFS position
+    normal: np.ndarray
+
+
+class Composite:
+    """The reference for one written InstSpec."""
+
+    def __init__(self, spec: InstSpec):
+        from oracle.cpu_ref import OracleScene
+        import ceng795_amd
+        self.spec = spec
+        self.desc = desc_xml.Desc(spec.all_xml)
+        self.mesh_orc = [OracleScene(x) for x in spec.mesh_xml]
+        self.loose_orc = [OracleScene(x) for x in spec.loose_xml]
+        V = np.array(spec.vertices, F)
+        self.inverse, self.inst_box, boxes = [], [], []
+        self.mesh_box = []
+        for m in spec.meshes:
+            pts = V[np.array(m).reshape(-1)]
+            self.mesh_box.append(np.concatenate([pts.min(0), pts.max(0)]).astype(F))
+        for mesh, _, mat in spec.instances:
+            self.inverse.append(invert_matrix(mat))
+            self.inst_box.append(apply_transform(self.mesh_box[mesh], mat))
+            boxes.append(self.inst_box[-1])
+        for _, t in spec.triangles:
+            pts = V[list(t)]
+            boxes.append(np.concatenate([pts.min(0), pts.max(0)]).astype(F))
+        for _, c, r in spec.spheres:
+            boxes.append(np.concatenate([(V[c] - F(r)).astype(F), (V[c] + F(r)).astype(F)]))
+        self.order, self.paths = top_level_tree(boxes)
+        self.top_of = {obj: pos for pos, obj in enumerate(self.order)}
+        # scene-wide leaf ids: each mesh's leaves in its DFS order, then the loose primitives
+        self.face_base, self.leaf_base, self.leaf_of_face = [], [], []
+        faces = leaves = 0
+        for k, m in enumerate(spec.meshes):
+            alone = desc_xml.Desc(spec.mesh_xml[k])  # (owns the arrays its .d points at)
+            lo = ceng795_amd.host_leaf_objects(alone.d)
+            inv = np.zeros(len(lo), np.int32)
+            inv[lo] = np.arange(len(lo), dtype=np.int32)
+            self.face_base.append(faces)
+            self.leaf_base.append(leaves)
+            self.leaf_of_face.append(inv)
+            faces += len(m)
+            leaves += len(m)
+        self.total_faces, self.mesh_leaves = faces, leaves
+
+    def close(self):
+        for o in self.mesh_orc + self.loose_orc:
+            o.close()
+
+    def reach(self, pos, o, d):
+        ok = np.ones(len(o), bool)
+        for box in self.paths[pos]:
+            ok &= slab_accept(box, o, d)
+        return ok
+
+    def local_rays(self, i, o, d):
+        return multiply(self.inverse[i], o), multiply(self.inverse[i], d, True)
+
+    def object_hits(self, obj, o, d):
+        """(hit, t, object, material, leaf, inst, normal) of every ray against top-level object
+        `obj` by its own rule (no ancestor boxes)."""
+        n = len(o)
+        spec = self.spec
+        ni = len(spec.instances)
+        if obj < ni:
+            mesh, material, _ = spec.instances[obj]
+            lo, ld = self.local_rays(obj, o, d)
+            go = slab_accept(self.inst_box[obj], o, d) & ray_ok(lo, ld)
+            rec, shape = self.mesh_orc[mesh].intersect_rays(np.where(go[:, None], lo, F(0)),
+                                                            np.where(go[:, None], ld, F(1)))
+            hit = go & (rec[:, 7] == 1.0)
+            nrm = multiply(np.asarray(self.inverse[obj]).T, rec[:, 4:7], True)
+            with np.errstate(all="ignore"):
+                ln = np.sqrt(((nrm[:, 0] * nrm[:, 0]).astype(F) + (nrm[:, 1] * nrm[:, 1]).astype(F)).astype(F)
+                             + (nrm[:, 2] * nrm[:, 2]).astype(F)).astype(F)
+                nrm = (nrm / ln[:, None]).astype(F)
+            face = np.where(hit, shape, 0)
+            return (hit, rec[:, 3], self.face_base[mesh] + face, np.full(n, material, np.int32),
+                    self.leaf_base[mesh] + self.leaf_of_face[mesh][face], np.full(n, obj, np.int32), nrm)
+        k = obj - ni
+        rec, _ = self.loose_orc[k].intersect_rays(o, d)
+        mat = (spec.triangles[k][0] if k < len(spec.triangles)
+               else spec.spheres[k - len(spec.triangles)][0])
+        return (rec[:, 7] == 1.0, rec[:, 3], np.full(n, self.total_faces + k, np.int32),
+                np.full(n, mat, np.int32), np.full(n, self.mesh_leaves + k, np.int32),
+                np.full(n, -1, np.int32), rec[:, 4:7])
+
+    def intersect(self, o, d) -> Hits:
+        o = np.ascontiguousarray(o, F).reshape(-1, 3)
+        d = np.ascontiguousarray(d, F).reshape(-1, 3)
+        n = len(o)
+        valid = ray_ok(o, d)
+        best = Hits(np.zeros(n, bool), np.full(n, INF, F), np.full(n, -1, np.int32),
+                    np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.full(n, -1, np.int32),
+                    np.full(n, -1, np.int32), np.zeros((n, 3), F))
+        lone = len(self.order) == 1
+        so, sd = np.where(valid[:, None], o, F(0)), np.where(valid[:, None], d, F(1))
+        for pos, obj in enumerate(self.order):
+            hit, t, object_, material, leaf, inst, normal = self.object_hits(obj, so, sd)
+            hit = hit & valid
+            if not lone:  # the leaf rule of BVH::intersect, under every ancestor box
+                hit = hit & (t > 0) & (t < INF) & self.reach(pos, so, sd)
+            win = hit & (~best.hit | (t < best.t))  # positions ascend: an equal t keeps the earlier
+            for name, val in (("t", t), ("object", object_), ("material", material), ("leaf", leaf),
+                              ("inst", inst), ("normal", normal)):
+                getattr(best, name)[win] = val[win]
+            best.top[win] = pos
+            best.hit |= win
+        return best
+
+    def occluded(self, o, d, tmax):
+        """1 where some reachable primitive has 0 < t < tmax.  Under an instance the mesh's closest
+        hit decides: its t is the smallest positive one among the mesh's reachable leaves."""
+        o = np.ascontiguousarray(o, F).reshape(-1, 3)
+        d = np.ascontiguousarray(d, F).reshape(-1, 3)
+        tmax = np.broadcast_to(np.asarray(tmax, F), (len(o),))
+        valid = ray_ok(o, d)
+        so, sd = np.where(valid[:, None], o, F(0)), np.where(valid[:, None], d, F(1))
+        occ = np.zeros(len(o), bool)
+        lone = len(self.order) == 1
+        for pos, obj in enumerate(self.order):
+            hit, t = self.object_hits(obj, so, sd)[:2]
+            if not lone:
+                hit = hit & self.reach(pos, so, sd)
+            occ |= hit & valid & (t > 0) & (t < tmax)
+        return occ.astype(np.uint8)
+
+
+def assert_hits(hits, ref: Hits, what=""):
+    """A closest-hit batch against the composite, bit for bit."""
+    b = lambda a: np.ascontiguousarray(a, F).view(np.uint32)  # noqa: E731
+    assert np.array_equal(hits["object"] >= 0, ref.hit), what
+    h = ref.hit
+    assert np.array_equal(b(hits["t"][h]), b(ref.t[h])), what
+    for name, want in (("object", ref.object), ("material", ref.material), ("leaf", ref.leaf),
+                       ("pad", ref.inst)):
+        assert np.array_equal(hits[name][h], want[h]), (what, name)
+    assert np.array_equal(b(hits["normal"][h]), b(ref.normal[h])), what
+    assert (b(hits["t"][~h]) == b(INF)).all() and (b(hits["normal"][~h]) == 0).all(), what
+    for name in ("object", "material", "leaf"):
+        assert (hits[name][~h] == -1).all(), (what, name)
+
+
+# ------------------------------------------------------------------ test geometry
+def bumpy_mesh(n=5, seed=3, z=0.0):
+    """A (n-1) x (n-1) x 2 triangle height field over [-1, 1]^2 around height z: 32 faces at
+    n = 5.  Returns (vertices, faces)."""
+    rng = np.random.default_rng(seed)
+    verts, faces = [], []
+    for j in range(n):
+        for i in range(n):
+            verts.append((-1 + 2 * i / (n - 1), -1 + 2 * j / (n - 1), z + 0.3 * float(rng.random())))
+    for j in range(n - 1):
+        for i in range(n - 1):
+            a, b2, c, e = j * n + i, j * n + i + 1, (j + 1) * n + i, (j + 1) * n + i + 1
+            faces += [(a, b2, e), (a, e, c)]
+    return verts, faces
+
+
+def scaling(x, y, z):
+    return np.diag([x, y, z, 1]).astype(F)
+
+
+def translation(x, y, z):
+    m = np.eye(4, dtype=F)
+    m[:3, 3] = (x, y, z)
+    return m
+
+
+def rotation_z(deg):
+    c, s = F(np.cos(np.radians(deg))), F(np.sin(np.radians(deg)))
+    m = np.eye(4, dtype=F)
+    m[0, 0], m[0, 1], m[1, 0], m[1, 1] = c, -s, s, c
+    return m
+
+
+def matmul(a, b):
+    """Matrix4x4::operator*: result[i][j] += a[i][k] * b[k][j], k ascending, from 0."""
+    a, b = np.asarray(a, F), np.asarray(b, F)
+    out = np.zeros((4, 4), F)
+    for i in range(4):
+        for j in range(4):
+            acc = F(0)
+            for k in range(4):
+                acc = F(acc + F(a[i][k] * b[k][j]))
+            out[i][j] = acc
+    return out
+
+
+MATERIALS = [G.Material((1, 1, 1), (0.8, 0.6, 0.4), (0.2, 0.2, 0.2), phong=4),
+             G.Material((1, 1, 1), (0.2, 0.7, 0.4), (0.3, 0.3, 0.3), phong=8),
+             G.Material((1, 1, 1), (0.3, 0.3, 0.9), (0.1, 0.1, 0.1), phong=2)]
+
+
+def _geometry():
+    """The vertex list of the test scenes: a 50-face height field (mesh 0), one triangle (mesh
+    1), a loose triangle and a sphere centre."""
+    verts, faces = bumpy_mesh(6)
+    base = len(verts)
+    verts += [(-0.5, -0.5, 0.0), (0.5, -0.5, 0.1), (0.0, 0.6, 0.2),   # mesh 1
+              (-3.0, -2.0, -1.0), (-2.0, -2.0, -1.2), (-2.5, -1.0, -0.8),  # the loose triangle
+              (2.5, -1.5, -0.5)]  # the sphere's centre
+    return verts, faces, [(base, base + 1, base + 2)], (base + 3, base + 4, base + 5), base + 6
+
+
+def chain_matrix():
+    """translate . rotate . non-uniform scale, composed as the loader's `s t r` lists do (each
+    element left-multiplying)."""
+    return matmul(translation(2.5, 1.0, -0.5), matmul(rotation_z(30.0), scaling(0.7, 1.3, 0.9)))
+
+
+def mirror_matrix():
+    """A negative determinant: x mirrored, moved to the left."""
+    return matmul(translation(-2.5, 1.2, 0.3), scaling(-1.0, 1.0, 1.2))
+
+
+def scene_three():
+    """Three instances of the height field (identity; translate . rotate . non-uniform scale;
+    mirrored), the one-triangle mesh instanced once (the lone-root rule), a loose triangle and a
+    sphere."""
+    verts, faces, one, tri, centre = _geometry()
+    lift = translation(0.3, -2.2, 0.8)
+    return InstSpec(verts, [faces, one],
+                    [(0, 0, np.eye(4, dtype=F)), (0, 1, chain_matrix()), (0, 2, mirror_matrix()),
+                     (1, 0, lift)],
+                    triangles=[(1, tri)], spheres=[(2, centre, 0.6)], materials=MATERIALS)
+
+
+def scene_ties(swapped=False):
+    """Two instances of one mesh with the same matrix and different materials: every hit ties in
+    t and the earlier top-level DFS leaf wins.  A loose triangle keeps the list a tree."""
+    verts, faces, one, tri, centre = _geometry()
+    m = chain_matrix()
+    mats = (2, 1) if swapped else (1, 2)
+    return InstSpec(verts, [faces], [(0, mats[0], m), (0, mats[1], m)], triangles=[(0, tri)],
+                    materials=MATERIALS)
+
+
+def scene_single():
+    """The top-level list is a single instance."""
+    verts, faces, one, tri, centre = _geometry()
+    return InstSpec(verts, [faces], [(0, 1, chain_matrix())], materials=MATERIALS)
+
+
+def scene_identity():
+    """Every transformation the identity: the composite must equal the plain oracle on the baked
+    scene.  Two meshes side by side (their vertices already apart) and the loose primitives."""
+    verts, faces, one, tri, centre = _geometry()
+    e = np.eye(4, dtype=F)
+    return InstSpec(verts, [faces, one], [(0, 0, e), (1, 0, e)], triangles=[(0, tri)],
+                    spheres=[(0, centre, 0.6)], materials=MATERIALS)
+
+
+def scene_scaled():
+    """Scalings by 1e7: along x alone (a world direction with every axis in use has a local x
+    below 1e-6, skipped locally), along all three (every local ray is all-tiny and misses), and
+    by 1e-3 along x (a world direction whose x is skipped has a local x that is not)."""
+    verts, faces, one, tri, centre = _geometry()
+    return InstSpec(verts, [faces],
+                    [(0, 0, scaling(1e7, 1.0, 1.0)), (0, 1, scaling(1e7, 1e7, 1e7)),
+                     (0, 2, matmul(translation(0.0, 0.0, 2.0), scaling(1e-3, 1.0, 1.0)))],
+                    triangles=[(1, tri)], materials=MATERIALS)
+
+
+SCENES = {"scaled": scene_scaled, "three": scene_three, "ties": scene_ties, "ties_swapped": lambda: scene_ties(True),
+          "single": scene_single, "identity": scene_identity}
+
+
+def written(name, directory):
+    return SCENES[name]().write(directory, name)
+
+
+def camera_rays(width=17, height=9, eye=(0.2, -0.4, 6.0), half=4.0):
+    """The rays of a pinhole frame looking down -z at the scenes above: (o, d) float32, d
+    normalised in fp32."""
+    xs = (np.arange(width, dtype=F) + F(0.5)) / F(width) * F(2 * half) - F(half)
+    ys = F(half) * F(height / width) - (np.arange(height, dtype=F) + F(0.5)) / F(height) * F(2 * half * height / width)
+    px, py = np.meshgrid(xs, ys)
+    d = np.stack([px, py, np.full_like(px, -6.0)], -1).reshape(-1, 3).astype(F)
+    d = (d / np.sqrt((d * d).sum(1, dtype=F))[:, None]).astype(F)
+    o = np.broadcast_to(np.array(eye, F), d.shape).copy()
+    return o, d
+
+
+def random_rays(n, seed):
+    """Rays from a shell around the scenes toward points inside them."""
+    rng = np.random.default_rng(seed)
+    o = (rng.normal(size=(n, 3)) * 4).astype(F)
+    target = (rng.uniform(-1, 1, size=(n, 3)) * (3.0, 2.5, 1.0)).astype(F)
+    d = (target - o).astype(F)
+    return o, d
+
+
+# ------------------------------------------------------------------ the XML dialect
+XML_TRANSFORMS = """  <Transformations>
+    <Scaling id="1">0.7 1.3 0.9</Scaling>
+    <Scaling id="2">-1 1 1.2</Scaling>
+    <Translation id="1">2.5 1 -0.5</Translation>
+    <Translation id="2">-2.5 1.2 0.3</Translation>
+    <Translation id="3">0.3 -2.2 0.8</Translation>
+    <Rotation id="1">30 0 0 1</Rotation>
+    <Rotation id="2">-75 1 2 -0.5</Rotation>
+  </Transformations>
+"""
+
+
+def xml_three(directory, edit=None, tag="xml_three"):
+    """Scene "three"'s geometry as an HW3 scene file: mesh 1 placed by `s1 r1 t1`, mesh 2 (the
+    one-face mesh, written with vertexOffset) by `t3`, a <MeshInstance> of mesh 1 with
+    resetTransform and `s2 t2`, one that keeps mesh 1's transformation and adds `r2`, and one with
+    a bare rotation.  `edit(text) -> text` changes the file before it is written.  Returns
+    (path, spec): spec is the flat geometry (its all_xml has no offset and no transformations)."""
+    spec = scene_three().write(directory, tag + "_flat")
+    text = open(spec.all_xml).read()
+    text = text.replace("  <VertexData>", XML_TRANSFORMS + "  <VertexData>", 1)
+    head, rest = text.split('<Mesh id="1">', 1)
+    rest = rest.replace("</Faces>", "</Faces>\n      <Transformations>s1 r1 t1</Transformations>", 1)
+    one, tail = rest.split('<Mesh id="2">', 1)
+    base = len(bumpy_mesh(6)[0])  # mesh 2's vertices follow the height field's
+    faces_a, faces_b = tail.split("<Faces>", 1)[1].split("</Faces>", 1)
+    ids = [int(x) - base for x in faces_a.split()]
+    tail = (tail.split("<Faces>", 1)[0] + f'<Faces vertexOffset="{base}">\n' + " ".join(map(str, ids))
+            + "\n      </Faces>\n      <Transformations>t3</Transformations>\n      <MotionBlur>0 0 0</MotionBlur>" + faces_b)
+    extra = """    <MeshInstance id="3" baseMeshId="1" resetTransform="true">
+      <Material>3</Material>
+      <Transformations>s2 t2</Transformations>
+    </MeshInstance>
+    <MeshInstance id="4" baseMeshId="1">
+      <Material>2</Material>
+      <Transformations>r2</Transformations>
+    </MeshInstance>
+    <MeshInstance id="5" baseMeshId="2" resetTransform="true">
+      <Material>1</Material>
+      <Transformations>r1</Transformations>
+    </MeshInstance>
+"""
+    text = head + '<Mesh id="1">' + one + '<Mesh id="2">' + tail
+    text = text.replace("    <Triangle ", extra + "    <Triangle ", 1)
+    if edit:
+        text = edit(text)
+    path = os.path.join(directory, tag + ".xml")
+    with open(path, "w") as f:
+        f.write(text)
+    return path, spec
+
+
+def rotation64(deg, axis):
+    """Rodrigues' rotation in float64: what Rotation::Rotation computes up to rounding."""
+    a = np.radians(np.float64(deg))
+    u = np.asarray(axis, np.float64)
+    u = u / np.linalg.norm(u)
+    K = np.array([[0, -u[2], u[1]], [u[2], 0, -u[0]], [-u[1], u[0], 0]])
+    m = np.eye(4)
+    m[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    return m
+
+
+# ------------------------------------------------------------------ shading: Scene::trace_ray
+class _CompositeOracle:
+    """The composite behind OracleScene.intersect_rays' interface: records {d, t, normal, hit}
+    with the instance's normal, and as `shape` the hit's material (the tracer's object table is
+    then the identity over the materials)."""
+
+    def __init__(self, comp):
+        self.comp = comp
+
+    def intersect_rays(self, origins, directions):
+        o = np.ascontiguousarray(origins, F).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, F).reshape(-1, 3)
+        ref = self.comp.intersect(o, d)
+        rec = np.zeros((len(o), 8), F)
+        rec[:, 0:3] = d
+        rec[:, 3] = np.where(ref.hit, ref.t, F(0))
+        rec[:, 4:7] = np.where(ref.hit[:, None], ref.normal, F(0))
+        rec[:, 7] = ref.hit
+        return rec, np.where(ref.hit, ref.material, -1).astype(np.int32)
+
+    def close(self):
+        pass
+
+
+def _tracer_class():
+    import smooth_util as su
+    from types import SimpleNamespace
+
+    class InstTracer(su.Tracer):
+        """smooth_util.Tracer (all of Scene::trace_ray in numpy fp32) over the composite: its
+        oracle replaced by the composite, Hit_data::normal by the instance normal."""
+
+        def __init__(self, comp):
+            super().__init__(comp.spec.all_xml)
+            self.orc.close()
+            self.orc = _CompositeOracle(comp)
+            nm = comp.desc.d.num_materials
+            self.ob = SimpleNamespace(mat=np.arange(nm, dtype=np.int64), smooth=np.zeros(nm, bool))
+
+        def hit_normals(self, o, d, rec, shape, idx):
+            return rec[idx, 4:7].copy()
+
+    return InstTracer
+
+
+def trace(comp, o, d, depth=-1, in_medium=False):
+    """Scene::trace_ray(Ray(o, d, in_medium), depth) of every ray over the instanced scene; depth
+    -1: the scene's maximum.  Returns ((n, 3) colours as a zeroed Pixel holds them, (n,) first-hit
+    t or +inf, ray counts), as smooth_util.trace."""
+    tr = _tracer_class()(comp)
+    o = np.ascontiguousarray(o, F)
+    d = np.ascontiguousarray(d, F)
+    if depth < 0:
+        depth = tr.max_depth
+    with np.errstate(all="ignore"):
+        color, t = tr.trace(o, d, np.full(len(o), bool(in_medium)), depth)
+    tr.counts["primary_rays"] = len(o)
+    out = F(0) + color
+    assert out.dtype == F and t.dtype == F
+    return out, t, tr.counts
+
+
+def restate_lit(comp, o, d, own):
+    """lit_util.restate (depth-0 shading with the caller's light records) over the composite: for
+    the length of the call its OracleScene is the composite and its object table the materials."""
+    import lit_util
+    import oracle.cpu_ref as cpu_ref
+    import rq_util
+    plain, plain_list = cpu_ref.OracleScene, rq_util.object_list
+    nm = comp.desc.d.num_materials
+    cpu_ref.OracleScene = lambda xml: _CompositeOracle(comp)
+    rq_util.object_list = lambda desc: [("M", m) for m in range(nm)]
+    try:
+        return lit_util.restate(comp.spec.all_xml, o, d, own)
+    finally:
+        cpu_ref.OracleScene, rq_util.object_list = plain, plain_list
+
+
+def scene_shiny(samples=None, width=33, height=31):
+    """Scene "three" with a mirror instance and a glass instance, MaxRecursionDepth 3, two lights,
+    under a 33 x 31 camera (or, with `samples`, an MSAA camera)."""
+    spec = scene_three()
+    spec.materials = MATERIALS + [
+        G.Material((1, 1, 1), (0.1, 0.1, 0.1), (0.4, 0.4, 0.4), mirror=(0.8, 0.8, 0.7), phong=16),
+        G.Material((1, 1, 1), (0.05, 0.05, 0.05), (0.3, 0.3, 0.3), phong=32,
+                   transparency=(0.9, 0.8, 0.85), refraction_index=1.5)]
+    spec.instances = [(m, {1: 3, 2: 4}.get(i, mat), x) for i, (m, mat, x) in enumerate(spec.instances)]
+    spec.lights = [((1.0, 2.0, 5.0), (200, 200, 200)), ((-3.0, -2.5, 4.0), (120, 100, 160))]
+    spec.max_depth = 3
+    spec.camera = G.Camera((0.2, -0.4, 6.0), (0, 0, -1), (0, 1, 0), (-1, 1, -1, 1), 1.5, width, height,
+                           "shiny.png", num_samples=samples)
+    return spec
+
+
+SCENES["shiny"] = scene_shiny
+SCENES["shiny_msaa"] = lambda: scene_shiny(samples=4, width=17, height=9)

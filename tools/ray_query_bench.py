@@ -123,6 +123,9 @@ def main(argv=None) -> int:
                    help="with --radiance: the cost of caller light records (LIGHT_CASES)")
     p.add_argument("--smooth", action="store_true",
                    help="C3 flat against C3 with its mesh smooth (SMOOTH_CASES)")
+    p.add_argument("--instances", type=int, default=0, metavar="K",
+                   help="a generated mesh (--n grid) placed K times as instances against the same "
+                        "geometry baked to world space in a flat scene: closest hit, occlusion and radiance")
     p.add_argument("--dry-run", action="store_true",
                    help="with --radiance --lights or --smooth: write the case list and stop (no GPU)")
     p.add_argument("--check", action="store_true",
@@ -139,6 +142,10 @@ def main(argv=None) -> int:
                              "smooth_query.json" if a.smooth else
                              "radiance_lights.json" if a.lights else
                              "radiance_query.json" if a.radiance else "ray_query.json")
+    if a.instances:
+        if a.out.endswith("ray_query.json"):
+            a.out = os.path.join(ROOT, "profiles", f"instances_k{a.instances}.json")
+        return instances_main(a)
     if a.smooth:
         return smooth_main(a)
     if a.lights:
@@ -358,6 +365,151 @@ def radiance_main(a) -> int:
         f.write("\n")
     print(json.dumps(result))
     return 0 if all(checks.values()) else 1
+
+
+def instances_main(a) -> int:
+    """--instances K: a height field of --n x --n vertices placed K times on a square grid, each
+    copy scaled, turned about z and moved; the same rays (from a shell around the grid toward
+    points on it, shuffled) through the instanced scene's two-level walk and through a flat scene
+    of the same geometry baked to world space (fp32 vertices: its bits differ, its hits agree up
+    to rounding).  Device bytes: what creating each scene took from the device's free memory."""
+    import ctypes as C
+    import torch
+    import ceng795_amd
+    from ceng795_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU")
+    f = np.float32
+    k, g = a.instances, a.n
+    rng = np.random.default_rng(a.seed)
+    xs = np.linspace(-1, 1, g, dtype=f)
+    vx, vy = np.meshgrid(xs, xs)
+    base = np.stack([vx, vy, (0.15 * rng.random((g, g))).astype(f)], -1).reshape(-1, 3).astype(f)
+    i, j = np.meshgrid(np.arange(g - 1), np.arange(g - 1))
+    q = (j * g + i).reshape(-1)
+    faces = np.stack([q, q + 1, q + g + 1, q, q + g + 1, q + g], 1).reshape(-1, 3).astype(np.int32)
+    side = int(np.ceil(np.sqrt(k)))
+    xf = np.zeros((k, 4, 4), f)
+    for c in range(k):
+        ang, sc = rng.uniform(0, 2 * np.pi), rng.uniform(0.7, 1.1)
+        m = np.eye(4)
+        m[:2, :2] = sc * np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
+        m[2, 2] = rng.uniform(0.5, 2.0)
+        m[:3, 3] = (2.4 * (c % side - (side - 1) / 2), 2.4 * (c // side - (side - 1) / 2), rng.uniform(-0.2, 0.2))
+        xf[c] = m.astype(f)
+    material = _lib.rt_material()
+    material.ambient = (C.c_float * 3)(1.0, 1.0, 1.0)
+    material.diffuse = (C.c_float * 3)(0.8, 0.6, 0.4)
+    material.specular = (C.c_float * 3)(0.2, 0.2, 0.2)
+    material.phong_exponent = 4.0
+    material.refraction_index = 1.0
+    light = _lib.rt_point_light((C.c_float * 3)(0.3 * side, 0.5 * side, 3.0 * side),
+                                (C.c_float * 3)(*[200.0 * side * side] * 3))
+
+    def desc_of(verts, counts, all_faces):
+        d = _lib.rt_scene_desc()
+        keep = [np.ascontiguousarray(verts, f), np.array(counts, np.int32),
+                np.ascontiguousarray(all_faces, np.int32), np.zeros(len(counts), np.int32), material]
+        d.vertices = keep[0].ctypes.data_as(C.POINTER(C.c_float))
+        d.num_vertices = len(keep[0])
+        d.materials, d.num_materials = C.pointer(material), 1
+        d.lights, d.num_lights = C.pointer(light), 1
+        d.ambient_light = (C.c_float * 3)(20.0, 20.0, 20.0)
+        d.num_meshes = len(counts)
+        d.mesh_material = keep[3].ctypes.data_as(C.POINTER(C.c_int))
+        d.mesh_face_count = keep[1].ctypes.data_as(C.POINTER(C.c_int))
+        d.mesh_faces = keep[2].ctypes.data_as(C.POINTER(C.c_int))
+        d.shadow_ray_epsilon = 1e-3
+        return d, keep
+
+    def created(make):
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        s = make()
+        torch.cuda.synchronize()
+        return s, int(free0 - torch.cuda.mem_get_info()[0])
+
+    d_inst, keep1 = desc_of(base, [len(faces)], faces)
+    # (a first scene, closed again: the runtime's own first allocations are not the scene's)
+    created(lambda: ceng795_amd.Scene.create(d_inst, device=0))[0].close()
+    inst, inst_bytes = created(lambda: ceng795_amd.Scene.create(
+        d_inst, instance_mesh=np.zeros(k, np.int32), instance_material=np.zeros(k, np.int32),
+        instance_transform=xf, device=0))
+    world = np.concatenate([(base @ m[:3, :3].T + m[:3, 3]).astype(f) for m in xf])
+    baked_faces = np.concatenate([faces + c * len(base) for c in range(k)])
+    d_flat, keep2 = desc_of(world, [len(faces)] * k, baked_faces)
+    flat, flat_bytes = created(lambda: ceng795_amd.Scene.create(d_flat, device=0))
+
+    n = a.width * a.height
+    half = 1.2 * side
+    o = (rng.normal(size=(n, 3)) * (half, half, 0.3 * half) + (0, 0, 1.5 * half)).astype(f)
+    target = (rng.uniform(-1, 1, size=(n, 3)) * (half, half, 0.1)).astype(f)
+    packed = ceng795_amd.pack_rays(o, (target - o).astype(f), np.inf)
+    rays = torch.from_numpy(packed.view(np.uint8).reshape(-1)).cuda()
+    hits = torch.zeros(n * 32, dtype=torch.uint8, device="cuda")
+    occ = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    rad = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    scenes = {"instanced": inst, "baked": flat}
+    cases = [(sc, kind, flag) for kind in ("closest", "occluded", "radiance")
+             for flag in (False, True) for sc in scenes]
+
+    def run(sc, kind, flag):
+        if kind == "closest":
+            scenes[sc].trace_rays_device(rays.data_ptr(), n, hits.data_ptr(), reorder=flag, stream=stream)
+        elif kind == "radiance":  # one point light: a shadow ray per hit
+            scenes[sc].shade_rays_device(rays.data_ptr(), n, rad.data_ptr(), reorder=flag, stream=stream)
+        else:
+            scenes[sc].occluded_device(rays.data_ptr(), n, occ.data_ptr(), reorder=flag, stream=stream)
+
+    got = {}
+    for sc in scenes:
+        run(sc, "closest", False)
+        torch.cuda.synchronize()
+        got[sc] = hits.cpu().numpy().view(ceng795_amd.HIT_DTYPE).copy()
+    hit_i, hit_b = got["instanced"]["object"] >= 0, got["baked"]["object"] >= 0
+    both = hit_i & hit_b
+    # the baked scene numbers instance c's faces from c * faces on
+    same = ((got["instanced"]["object"][both] == got["baked"]["object"][both] % len(faces)) &
+            (got["instanced"]["pad"][both] == got["baked"]["object"][both] // len(faces)))
+    agree = {"hit_share_instanced": float(hit_i.mean()), "hit_share_baked": float(hit_b.mean()),
+             "same_hit_or_miss": float((hit_i == hit_b).mean()),
+             "same_face_and_instance_where_both_hit": float(same.mean()),
+             "max_rel_t_diff_where_same_face": float(np.max(np.abs(
+                 got["instanced"]["t"][both] / got["baked"]["t"][both] - 1)[same], initial=0.0))}
+
+    times = {c: [] for c in cases}
+    for rnd in range(a.warmup + a.calls):
+        marks = []
+        for c in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(*c)
+            e1.record()
+            marks.append((c, e0, e1))
+        torch.cuda.synchronize()
+        if rnd >= a.warmup:
+            for c, e0, e1 in marks:
+                times[c].append(e0.elapsed_time(e1))
+    result = {"lib_sha256": file_sha256(_lib.LIB_PATH), "device": torch.cuda.get_device_name(0),
+              "scene": f"height field {g}x{g} ({len(faces)} faces) x {k} instances on a "
+                       f"{side}x{side} grid; baked: {len(baked_faces)} world-space faces",
+              "rays": n, "calls": a.calls, "warmup": a.warmup,
+              "timing": "device events around each call; cases alternated within every round",
+              "device_bytes": {"instanced": inst_bytes, "baked": flat_bytes},
+              "agreement": agree, "cases": {}}
+    for (sc, kind, flag), ms in times.items():
+        qq = quartiles(ms)
+        qq["mrays_per_s"] = n / qq["ms_median"] / 1e3
+        result["cases"][f"{sc}/{kind}/{'reorder' if flag else 'plain'}"] = qq
+    c = result["cases"]
+    result["ratios"] = {f"instanced_over_baked/{kind}/{fl}":
+                        c[f"instanced/{kind}/{fl}"]["ms_median"] / c[f"baked/{kind}/{fl}"]["ms_median"]
+                        for kind in ("closest", "occluded", "radiance") for fl in ("plain", "reorder")}
+    inst.close()
+    flat.close()
+    write_result(a.out, result)
+    return 0
 
 
 def write_result(path: str, result: dict) -> None:
