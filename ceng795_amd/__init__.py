@@ -23,11 +23,12 @@ Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, RADIANCE_DTYPE,  # noqa: F401
                     LIGHT_SAMPLE_DTYPE, HIT_ATTR_DTYPE, pack_rays, host_leaf_objects,
                     host_vertex_normals, host_mesh_smooth, host_instance_info,
-                    host_instances_xml)
+                    host_instances_xml, host_motion_info, host_motion_xml)
 from .film import Film  # noqa: F401
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
 __all__ = ["Scene", "Film", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_FAST",
            "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "LIGHT_SAMPLE_DTYPE",
            "HIT_ATTR_DTYPE", "pack_rays", "host_leaf_objects", "host_vertex_normals",
-           "host_mesh_smooth", "host_instance_info", "host_instances_xml"]
+           "host_mesh_smooth", "host_instance_info", "host_instances_xml",
+           "host_motion_info", "host_motion_xml"]

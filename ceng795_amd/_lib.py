@@ -29,6 +29,7 @@ RT_QUERY_REORDER = 1  # flags of the ray queries
 RT_QUERY_IN_MEDIUM = 2  # radiance queries only: every ray starts inside a dielectric
 RT_QUERY_LIGHTS_SHARED = 4  # the `_lit` entries only: one light list for every ray
 RT_QUERY_NO_SCENE_LIGHTS = 8  # the `_lit` entries only: the scene's own lights stay dark
+RT_QUERY_RAY_TIME = 32  # every ray entry: rt_ray.pad is the ray's time (scenes with motion)
 
 RT_FILM_GAUSSIAN = 0  # rt_film_create filters
 RT_FILM_BOX = 1
@@ -108,6 +109,13 @@ class rt_instance_desc(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("num_instances", C.c_int),
                 ("instance_mesh", C.POINTER(C.c_int)), ("instance_material", C.POINTER(C.c_int)),
                 ("instance_transform", C.POINTER(C.c_float))]
+
+
+class rt_motion_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("num_instances", C.c_int), ("num_spheres", C.c_int),
+                ("instance_velocity", C.POINTER(C.c_float)),
+                ("sphere_transform", C.POINTER(C.c_float)),
+                ("sphere_velocity", C.POINTER(C.c_float))]
 
 
 RT_ATTR_HIT, RT_ATTR_TRIANGLE, RT_ATTR_SMOOTH = 1, 2, 4  # rt_hit_attr::flags
@@ -246,6 +254,20 @@ SIGNATURES = {
     "rt_host_instance_info_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
                                              C.POINTER(C.c_float), C.POINTER(C.c_float),
                                              C.POINTER(C.c_int)]),
+    "rt_motion_version": (C.c_int, []),
+    "rt_scene_create_moving": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
+                                         C.POINTER(rt_motion_desc), C.c_int,
+                                         C.POINTER(C.c_void_p)]),
+    "rt_scene_load_xml_moving": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_scene_has_motion": (C.c_int, [C.c_void_p]),
+    "rt_host_motion_info_desc": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
+                                           C.POINTER(rt_motion_desc), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int)]),
+    "rt_host_motion_xml": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
+    "rt_debug_motion_inverse": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_longlong,
+                                          C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -111,6 +111,14 @@ struct InstHost {
   float top_box[6] = {0, 0, 0, 0, 0, 0};
   bool has_spheres = false;
   int leaves = 0;                     // scene-wide leaf ids
+  // a scene with motion (build_moving): some instance or sphere has a velocity,
+  // or some sphere a matrix other than the identity
+  bool has_motion = false;
+  std::vector<DevMotionInstance> motion_instances;  // per instance (scenes with motion)
+  std::vector<DevMotionSphere> motion_spheres;      // the kPrimMovingSphere records
+  std::vector<float> sphere_inverse;  // 16 per sphere: the whole inverse of its matrix
+  std::vector<float> sphere_box;      // 6 per sphere: its box in the top-level tree
+  std::vector<int> object_top_dfs;    // per top-level object: its top-level DFS position
 };
 // Builds `out` from the description's meshes (bases only) and the instance descriptor; treelets:
 // build_accel's K for every base mesh, each checked with check_accel.  Throws
@@ -118,6 +126,16 @@ struct InstHost {
 // on what instanced scenes do not take (the caller's own BVH, trees deeper than the wave stack).
 void build_instanced(const rt_scene_desc& desc, const rt_instance_desc& inst, int treelets,
                      InstHost& out);
+// build_instanced with the motion descriptor's velocities and sphere matrices (either descriptor
+// may be null; no instance: the top level is the loose primitives).  Checks the motion descriptor
+// (struct_size, counts, finite entries, invertible sphere matrices: std::invalid_argument).  The
+// boxes of moving objects are expanded by +-velocity (Mesh.h:104-110, Sphere.h:30-36).
+void build_moving(const rt_scene_desc& desc, const rt_instance_desc* inst,
+                  const rt_motion_desc* motion, int treelets, InstHost& out);
+// Every velocity zero and every sphere matrix the identity (or the arrays null).  Checks the
+// descriptor as build_moving does.
+bool motion_trivial(const rt_scene_desc& desc, const rt_instance_desc* inst,
+                    const rt_motion_desc* motion);
 
 // load_scene_xml plus the file's instances (instances_xml.cpp): the root <Transformations> block,
 // every <Mesh> as an instance with its own transformation list, then the <MeshInstance>s;
@@ -128,9 +146,14 @@ struct XmlSceneStorage;
 struct XmlInstances {
   std::vector<int> mesh, material;
   std::vector<float> transform;  // 16 per instance, row-major
+  // load_instances_xml(..., motion = true) only (rt_scene_load_xml_moving): <MotionBlur> per
+  // instance and per <Sphere>, and the <Sphere>s' composed <Transformations>
+  std::vector<float> velocity;          // 3 per instance
+  std::vector<float> sphere_transform;  // 16 per sphere
+  std::vector<float> sphere_velocity;   // 3 per sphere
 };
 void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc& desc,
-                        XmlInstances& out);
+                        XmlInstances& out, bool motion = false);
 
 // Preorder dump in oracle/ref/ref_harness.cpp's format (without the Mesh "M" markers, which
 // the flattened layout splices away).

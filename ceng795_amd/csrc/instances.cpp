@@ -107,16 +107,98 @@ struct TopBuilder {
   }
 };
 
+// Mesh_instance::Mesh_instance / Sphere::Sphere with velocity != 0 (Mesh.h:104-110,
+// Sphere.h:30-36): (min, max) expanded by (min + v, max + v), then by (min - v, max - v).
+void expand_by_velocity(Box& b, const float v[3]) {
+  for (int a = 0; a < 3; a++) {
+    const float lo = b.lo[a], hi = b.hi[a];
+    b.lo[a] = std::fmin(b.lo[a], lo + v[a]);
+    b.hi[a] = std::fmax(b.hi[a], hi + v[a]);
+    b.lo[a] = std::fmin(b.lo[a], lo - v[a]);
+    b.hi[a] = std::fmax(b.hi[a], hi - v[a]);
+  }
+  b.set_mid();
+}
+
+bool nonzero3(const float* v) { return v && !(v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f); }
+
+// The motion descriptor against the other two: what build_moving and motion_trivial refuse.
+void check_motion_desc(const rt_scene_desc& d, const rt_instance_desc* in,
+                       const rt_motion_desc* mo) {
+  if (!mo) return;
+  if (mo->struct_size < sizeof(rt_motion_desc)) fail("rt_motion_desc::struct_size too small");
+  const int ni = in ? in->num_instances : 0;
+  if (mo->num_instances != ni && !(mo->num_instances == 0 && !mo->instance_velocity))
+    fail("rt_motion_desc::num_instances differs from the instance descriptor's");
+  if (mo->num_spheres != d.num_spheres &&
+      !(mo->num_spheres == 0 && !mo->sphere_transform && !mo->sphere_velocity))
+    fail("rt_motion_desc::num_spheres differs from the scene description's");
+  auto finite = [](const float* p, size_t count, const char* what) {
+    for (size_t k = 0; p && k < count; k++)
+      if (!std::isfinite(p[k])) fail(std::string(what) + ": a non-finite entry");
+  };
+  finite(mo->instance_velocity, 3 * (size_t)std::max(mo->num_instances, 0), "instance_velocity");
+  finite(mo->sphere_transform, 16 * (size_t)std::max(mo->num_spheres, 0), "sphere_transform");
+  finite(mo->sphere_velocity, 3 * (size_t)std::max(mo->num_spheres, 0), "sphere_velocity");
+  for (int k = 0; mo->sphere_transform && k < mo->num_spheres; k++) {
+    Mat4 m, inv;
+    std::memcpy(m.a, mo->sphere_transform + 16 * (size_t)k, sizeof m.a);
+    if (!m.inverse(inv))
+      fail("sphere " + std::to_string(k) + ": the transformation is not invertible");
+  }
+}
+
+void build_impl(const rt_scene_desc& d, const rt_instance_desc* inp, const rt_motion_desc* mo,
+                int treelets, InstHost& out);
+
 }  // namespace
 
 void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int treelets,
                      InstHost& out) {
   if (d.bvh_num_leaves > 0 || d.bvh_num_nodes > 0)
     throw std::domain_error("instanced scenes do not take the caller's own BVH (bvh_*)");
+  if (in.num_instances <= 0) fail("num_instances <= 0");
+  build_impl(d, &in, nullptr, treelets, out);
+}
+
+bool motion_trivial(const rt_scene_desc& d, const rt_instance_desc* in, const rt_motion_desc* mo) {
+  check_motion_desc(d, in, mo);
+  if (!mo) return true;
+  for (int i = 0; mo->instance_velocity && i < mo->num_instances; i++)
+    if (nonzero3(mo->instance_velocity + 3 * (size_t)i)) return false;
+  for (int k = 0; k < mo->num_spheres; k++) {
+    if (mo->sphere_velocity && nonzero3(mo->sphere_velocity + 3 * (size_t)k)) return false;
+    if (mo->sphere_transform) {
+      Mat4 m;
+      std::memcpy(m.a, mo->sphere_transform + 16 * (size_t)k, sizeof m.a);
+      if (!m.identity_p()) return false;
+    }
+  }
+  return true;
+}
+
+void build_moving(const rt_scene_desc& d, const rt_instance_desc* in, const rt_motion_desc* mo,
+                  int treelets, InstHost& out) {
+  if (d.bvh_num_leaves > 0 || d.bvh_num_nodes > 0)
+    throw std::domain_error("instanced scenes do not take the caller's own BVH (bvh_*)");
+  check_motion_desc(d, in, mo);
+  build_impl(d, in, mo, treelets, out);
+}
+
+namespace {
+
+void build_impl(const rt_scene_desc& d, const rt_instance_desc* inp, const rt_motion_desc* mo,
+                int treelets, InstHost& out) {
+  const rt_instance_desc none{sizeof(rt_instance_desc), 0, nullptr, nullptr, nullptr};
+  const rt_instance_desc& in = inp ? *inp : none;
   const int n = in.num_instances;
-  if (n <= 0) fail("num_instances <= 0");
-  if (!in.instance_mesh || !in.instance_material || !in.instance_transform)
+  if (n < 0) fail("num_instances < 0");
+  if (n > 0 && (!in.instance_mesh || !in.instance_material || !in.instance_transform))
     fail("instance_mesh / instance_material / instance_transform == NULL");
+  const float* inst_vel = mo && mo->num_instances == n ? mo->instance_velocity : nullptr;
+  const bool sphere_motion = mo && mo->num_spheres == d.num_spheres;
+  const float* sph_vel = sphere_motion ? mo->sphere_velocity : nullptr;
+  const float* sph_xf = sphere_motion ? mo->sphere_transform : nullptr;
   if (d.num_meshes < 0 || d.num_triangles < 0 || d.num_spheres < 0 || d.num_vertices < 0 ||
       d.num_materials < 0)
     fail("negative count in scene description");
@@ -213,9 +295,20 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
         root_box[a + 3] = std::fmax(std::fmax(v0, v1), v2);
       }
     }
-    const Box b = transformed_box(root_box, m);
+    Box b = transformed_box(root_box, m);
+    const bool moves = inst_vel && nonzero3(inst_vel + 3 * (size_t)i);
+    if (moves) expand_by_velocity(b, inst_vel + 3 * (size_t)i);
+    if (mo) {
+      DevMotionInstance mi;
+      std::memset(&mi, 0, sizeof mi);
+      std::memcpy(mi.fwd, m.a, sizeof mi.fwd);
+      if (moves) std::memcpy(mi.vel, inst_vel + 3 * (size_t)i, sizeof mi.vel);
+      out.motion_instances.push_back(mi);
+      out.has_motion = out.has_motion || moves;
+    }
     DevInstance& di = out.instances[(size_t)i];
     std::memset(&di, 0, sizeof di);
+    di.moving = moves ? 1 : 0;
     std::memcpy(di.inv, inv.a, sizeof di.inv);  // rows 0..2
     std::memcpy(di.box, b.lo, 12);
     std::memcpy(di.box + 3, b.hi, 12);
@@ -239,6 +332,8 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
     b.set_mid();
     boxes.push_back(b);
   }
+  std::vector<int> sphere_record((size_t)d.num_spheres, -1);  // its DevMotionSphere, if any
+  out.sphere_inverse.assign(16 * (size_t)d.num_spheres, 0.0f);
   for (int k = 0; k < d.num_spheres; k++) {
     Box b;
     for (int a = 0; a < 3; a++) {
@@ -247,12 +342,43 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
       b.hi[a] = c + r;
     }
     b.set_mid();
+    // Sphere::Sphere (Sphere.h:18-37): through apply_transform unless the matrix is the identity,
+    // then expanded by the velocity
+    Mat4 m = Mat4::identity(), inv = Mat4::identity();
+    if (sph_xf) std::memcpy(m.a, sph_xf + 16 * (size_t)k, sizeof m.a);
+    const bool placed = !m.identity_p();
+    const bool moves = sph_vel && nonzero3(sph_vel + 3 * (size_t)k);
+    if (placed) {
+      const float flat[6] = {b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2]};
+      b = transformed_box(flat, m);
+      if (!m.inverse(inv))
+        fail("sphere " + std::to_string(k) + ": the transformation is not invertible");
+    }
+    if (moves) expand_by_velocity(b, sph_vel + 3 * (size_t)k);
+    std::memcpy(&out.sphere_inverse[16 * (size_t)k], inv.a, sizeof inv.a);
+    if (placed || moves) {
+      DevMotionSphere ms;
+      std::memset(&ms, 0, sizeof ms);
+      std::memcpy(ms.fwd, m.a, sizeof ms.fwd);
+      std::memcpy(ms.inv, inv.a, sizeof ms.inv);  // rows 0..2
+      if (moves) std::memcpy(ms.vel, sph_vel + 3 * (size_t)k, sizeof ms.vel);
+      ms.moving = moves ? 1 : 0;
+      for (int a = 0; a < 3; a++) ms.center[a] = vertex(d.sphere_center[k], a);
+      ms.radius = d.sphere_radius[k];
+      ms.material = d.sphere_material[k];
+      sphere_record[(size_t)k] = (int)out.motion_spheres.size();
+      out.motion_spheres.push_back(ms);
+      out.has_motion = true;
+    }
+    out.sphere_box.insert(out.sphere_box.end(), b.lo, b.lo + 3);
+    out.sphere_box.insert(out.sphere_box.end(), b.hi, b.hi + 3);
     boxes.push_back(b);
     out.has_spheres = true;
   }
 
   // ---- the top-level tree
   const int objects = n + loose;
+  if (objects == 0) fail("no instance, loose triangle or sphere");
   std::vector<int> ids((size_t)objects), order;
   for (int i = 0; i < objects; i++) ids[(size_t)i] = i;
   if (objects == 1) {  // create_bvh, size 1: the object itself
@@ -271,6 +397,7 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
                               " levels is not supported");
   }
   out.inst_top_dfs.assign((size_t)n, -1);
+  out.object_top_dfs.assign((size_t)objects, -1);
   out.top_prims.assign(order.size(), DevPrim{});
   out.top_normals.assign(4 * order.size(), 0.0f);
   out.top_info.assign(2 * order.size(), -1);
@@ -278,6 +405,7 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
   for (size_t pos = 0; pos < order.size(); pos++) {
     const int obj = order[pos];
     DevPrim& p = out.top_prims[pos];
+    out.object_top_dfs[(size_t)obj] = (int)pos;
     if (obj < n) {
       p.kind = kPrimInstance;
       p.material = obj;
@@ -288,9 +416,16 @@ void build_instanced(const rt_scene_desc& d, const rt_instance_desc& in, int tre
       std::memcpy(&out.top_normals[4 * pos], &ls.normals[4 * (size_t)leaf], 16);
       out.top_info[2 * pos] = total_faces + k;
       out.top_info[2 * pos + 1] = leaf_base + k;
+      const int sphere = k - d.num_triangles;
+      if (sphere >= 0 && sphere_record[(size_t)sphere] >= 0) {  // a kind of its own (§4.17)
+        p.kind = kPrimMovingSphere;
+        p.material = sphere_record[(size_t)sphere];
+      }
     }
   }
   out.leaves = leaf_base + loose;
 }
+
+}  // namespace
 
 }  // namespace rt

@@ -101,20 +101,26 @@ Mat4 apply_list(std::stringstream& ss, const Node* n, const Lists& T, Mat4 m) {
   return m;
 }
 
-void check_motion_blur(std::stringstream& ss, const Node* object) {
+// <MotionBlur>x y z</MotionBlur> (Scene.cpp:666-672, 752-758, 856-862): appended to `velocity`
+// when the loader reads motion, else refused unless zero.
+void read_motion_blur(std::stringstream& ss, const Node* object, std::vector<float>* velocity) {
   const Node* mb = object->first("MotionBlur");
-  if (!mb) return;
   float v[3] = {0, 0, 0};
-  ss << node_text(mb, "MotionBlur") << std::endl;
-  ss >> v[0] >> v[1] >> v[2];
-  ss.clear();
-  if (v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f) unsupported("a non-zero <MotionBlur>");
+  if (mb) {
+    ss << node_text(mb, "MotionBlur") << std::endl;
+    ss >> v[0] >> v[1] >> v[2];
+    ss.clear();
+  }
+  if (velocity)
+    velocity->insert(velocity->end(), v, v + 3);
+  else if (v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f)
+    unsupported("a non-zero <MotionBlur>");
 }
 
 }  // namespace
 
 void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc& d,
-                        XmlInstances& out) {
+                        XmlInstances& out, bool motion) {
   load_scene_xml(path, st, d);
   const std::unique_ptr<Node> root = parse_xml_file(path);
   std::stringstream ss;
@@ -155,7 +161,7 @@ void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_d
   for (const Node* m : objs->each("Mesh")) {
     const Node* faces = m->first("Faces");
     if (faces && faces->attr("plyFile")) unsupported("plyFile");
-    check_motion_blur(ss, m);
+    read_motion_blur(ss, m, motion ? &out.velocity : nullptr);
     // vertexOffset (text faces; load_scene_xml has applied a binary list's already)
     const size_t count = 3 * (size_t)st.mesh_face_count[(size_t)k];
     if (faces && !faces->attr("binaryFile")) {
@@ -174,7 +180,7 @@ void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_d
     ss << node_text(e->first("Material"), "Material") << std::endl;
     ss >> material;
     ss.clear();
-    check_motion_blur(ss, e);
+    read_motion_blur(ss, e, motion ? &out.velocity : nullptr);  // (its own, not its base's)
     Mat4 m = base[(size_t)id];
     const char* reset = e->attr("resetTransform");
     if (reset && std::string(reset) == "true") m = Mat4::identity();
@@ -182,8 +188,15 @@ void load_instances_xml(const std::string& path, XmlSceneStorage& st, rt_scene_d
   }
   for (const char* kind : {"Triangle", "Sphere"})
     for (const Node* e : objs->each(kind)) {
+      const bool sphere = std::string(kind) == "Sphere";
+      if (motion && sphere) {  // Scene.cpp:838-863: its own list onto the identity, its velocity
+        const Mat4 m = apply_list(ss, e->first("Transformations"), T, Mat4::identity());
+        out.sphere_transform.insert(out.sphere_transform.end(), &m.a[0][0], &m.a[0][0] + 16);
+        read_motion_blur(ss, e, &out.sphere_velocity);
+        continue;
+      }
       if (e->first("Transformations")) unsupported(std::string("<Transformations> on a <") + kind + ">");
-      check_motion_blur(ss, e);
+      read_motion_blur(ss, e, nullptr);
     }
 }
 

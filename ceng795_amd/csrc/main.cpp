@@ -1,4 +1,4 @@
-// `raytracer [--gpus N] [--reference-traversal] [--smooth] [--instanced] <scene.xml>` — the host driver of
+// `raytracer [--gpus N] [--reference-traversal] [--smooth] [--instanced | --moving] <scene.xml>` — the host driver of
 // HW2/main.cpp:10-70 on top of the C ABI: parse the scene, then for every <Camera> render
 // (timed), quantise and write <ImageName>.  The reference spawns hardware_concurrency()
 // threads on render_image (main.cpp:33-36); here one rt_render call renders every row on the
@@ -6,7 +6,8 @@
 // devices, RCCL gather onto the first).  --smooth honours <Mesh shadingMode="smooth"> as the HW3
 // loader does (rt_scene_load_xml_surface; one GPU); without it the attribute is ignored, as in HW2.
 // --instanced honours HW3's <Transformations> and <MeshInstance> (rt_scene_load_xml_instanced; one
-// GPU, flat shading).
+// GPU, flat shading).  --moving also honours <MotionBlur> and a <Sphere>'s <Transformations>
+// (rt_scene_load_xml_moving); the frame is rendered with every ray at time 0.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -17,7 +18,7 @@
 
 int main(int argc, char** argv) {
   int mode = RT_TRAVERSAL_FAST, gpus = 0;
-  bool smooth = false, instanced = false;
+  bool smooth = false, instanced = false, moving = false;
   const char* xml = nullptr;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -27,6 +28,8 @@ int main(int argc, char** argv) {
       smooth = true;
     } else if (a == "--instanced") {
       instanced = true;
+    } else if (a == "--moving") {
+      instanced = moving = true;
     } else if (a == "--gpus" && i + 1 < argc) {
       gpus = std::atoi(argv[++i]);
     } else {
@@ -42,11 +45,13 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (instanced && (gpus > 0 || smooth)) {
-    std::fprintf(stderr, "--instanced renders on one GPU, flat-shaded (no --gpus, no --smooth)\n");
+    std::fprintf(stderr,
+                 "--instanced and --moving render on one GPU, flat-shaded (no --gpus, no --smooth)\n");
     return 1;
   }
   rt_scene* scene = nullptr;
   const int rc = gpus > 0 ? rt_scene_load_xml_multi(xml, gpus, nullptr, &scene)
+                 : moving ? rt_scene_load_xml_moving(xml, -1, &scene)
                  : instanced ? rt_scene_load_xml_instanced(xml, -1, &scene)
                  : smooth ? rt_scene_load_xml_surface(xml, -1, &scene)
                           : rt_scene_load_xml(xml, -1, &scene);

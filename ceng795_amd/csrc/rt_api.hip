@@ -27,7 +27,9 @@
 namespace rt {
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
                          const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
-                         hipStream_t stream);
+                         const MotionParams* motion, hipStream_t stream);
+hipError_t launch_motion_inverse(const float* fwd, const float* vel, const float* times,
+                                 long long n, float* out12, hipStream_t stream);
 int max_supported_depth();
 hipError_t launch_msaa_resolve(const MsaaResolveParams& M, hipStream_t stream);
 hipError_t launch_untile(const UntileParams& U, hipStream_t stream);
@@ -49,11 +51,11 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
 hipError_t launch_query_sort(QueryParams Q, hipStream_t stream);
 hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstParams& T,
                              bool occlusion, bool reorder, bool fast, bool spheres,
-                             hipStream_t stream);
+                             const MotionParams* motion, hipStream_t stream);
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
                            bool spheres, const SurfParams* surf, const InstParams* inst,
-                           hipStream_t stream);
+                           const MotionParams* motion, hipStream_t stream);
 hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, const AttrParams& A,
                                  hipStream_t stream);
 hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
@@ -194,6 +196,10 @@ struct Replica {
   DevBuf<float> d_top_normals;
   DevBuf<int> d_top_info;
   InstParams inst{};
+  // a scene with motion: the moving objects' tables; `motion` points at them
+  DevBuf<DevMotionInstance> d_motion_instances;
+  DevBuf<DevMotionSphere> d_motion_spheres;
+  MotionParams motion{};
   DevBuf<unsigned long long> d_counters;
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
   // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
@@ -687,6 +693,24 @@ const SurfParams* smooth_surface(const rt_scene* s) {
 }
 // What the INST kernels take: an instanced scene's tables (single-device), else null.
 const InstParams* inst_params(const rt_scene* s) { return s->inst ? &s->rep[0]->inst : nullptr; }
+// What the motion kernels take beside them: the scene's motion tables with the call's traversal
+// mode and whether its rays carry a time (RT_QUERY_RAY_TIME); a scene without motion: null, and
+// the flag has no effect.
+struct MotionCall {
+  MotionParams m;
+  bool on;
+  const MotionParams* get() const { return on ? &m : nullptr; }
+};
+MotionCall motion_call(const rt_scene* s, int flags) {
+  MotionCall c{};
+  c.on = s->inst && s->inst->has_motion;
+  if (c.on) {
+    c.m = s->rep[0]->motion;
+    c.m.fast = s->mode != RT_TRAVERSAL_REFERENCE ? 1 : 0;
+    c.m.ray_time = (flags & RT_QUERY_RAY_TIME) ? 1 : 0;
+  }
+  return c;
+}
 
 // The sample passes of an MSAA camera (HW2/Scene.cpp:32-69) over P's rows: pass k renders
 // sample k of every selected pixel into d_samples[k] (row-major, full-frame positions).
@@ -704,7 +728,8 @@ void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_s
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
     hip_check(launch_render(Q, fast, s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr,
-                            smooth_surface(s), inst_params(s), stream), "render launch");
+                            smooth_surface(s), inst_params(s), motion_call(s, 0).get(), stream),
+              "render launch");
   }
 }
 
@@ -732,7 +757,8 @@ void enqueue_frame(rt_scene* s, const RenderParams& P, int samples, float* d_sam
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
     hip_check(launch_render(P, fast, s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr,
-                            smooth_surface(s), inst_params(s), stream), "render launch");
+                            smooth_surface(s), inst_params(s), motion_call(s, 0).get(), stream),
+              "render launch");
     return;
   }
   enqueue_samples(s, P, samples, d_samples, stream, timed);
@@ -1283,7 +1309,8 @@ void enqueue_hits(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws
     if (reorder) carve_reorder(Q, ws, Q.n);
     if (s->inst) {
       hip_check(launch_inst_query(P, Q, r.inst, OCCLUSION, reorder,
-                                  s->mode != RT_TRAVERSAL_REFERENCE, s->has_spheres, stream),
+                                  s->mode != RT_TRAVERSAL_REFERENCE, s->has_spheres,
+                                  motion_call(s, q.flags).get(), stream),
                 "query launch");
       continue;
     }
@@ -1351,19 +1378,23 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
       C.n = std::min(part, R.first + chunk);
       hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
                                 s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres,
-                                smooth_surface(s), inst_params(s), stream),
+                                smooth_surface(s), inst_params(s), motion_call(s, q.flags).get(),
+                                stream),
                 "radiance query launch");
     }
   }
 }
 
-const QueryKind kClosestHit{sizeof(rt_ray_hit), true, RT_QUERY_REORDER, false, enqueue_hits<false>};
-const QueryKind kOcclusion{1, false, RT_QUERY_REORDER, false, enqueue_hits<true>};
-const QueryKind kRadiance{sizeof(rt_radiance), true, RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM, true,
+const QueryKind kClosestHit{sizeof(rt_ray_hit), true, RT_QUERY_REORDER | RT_QUERY_RAY_TIME, false,
+                            enqueue_hits<false>};
+const QueryKind kOcclusion{1, false, RT_QUERY_REORDER | RT_QUERY_RAY_TIME, false,
+                           enqueue_hits<true>};
+const QueryKind kRadiance{sizeof(rt_radiance), true,
+                          RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM | RT_QUERY_RAY_TIME, true,
                           enqueue_radiance};
 const QueryKind kRadianceLit{sizeof(rt_radiance), true,
-                             RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM | kLitFlags, true,
-                             enqueue_radiance};
+                             RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM | RT_QUERY_RAY_TIME | kLitFlags,
+                             true, enqueue_radiance};
 
 // The front end of the `_device` entries: rays and results in device memory, enqueued on the
 // caller's stream with its working set; the ray counts go to the scene's counters.
@@ -1714,6 +1745,12 @@ static void upload_instanced(rt_scene* s, Replica& r) {
   r.inst.top_root_kind = ih.top_root_kind;
   r.inst.top_quot_ok = ih.top_quot_ok;
   std::memcpy(r.inst.top_box, ih.top_box, sizeof r.inst.top_box);
+  if (ih.has_motion) {  // (a table may be empty: nothing of that kind moves, and nothing reads it)
+    r.d_motion_instances = upload(ih.motion_instances, "upload moving instances", kPad);
+    r.d_motion_spheres = upload(ih.motion_spheres, "upload moving spheres", kPad);
+    r.motion.instances = r.d_motion_instances.p;
+    r.motion.spheres = r.d_motion_spheres.p;
+  }
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
 }
@@ -1828,6 +1865,157 @@ int rt_host_instance_info_desc(const rt_scene_desc* desc, const rt_instance_desc
       if (box6) std::memcpy(box6 + 6 * i, ih.instances[i].box, 6 * sizeof(float));
       if (top_dfs) top_dfs[i] = ih.inst_top_dfs[i];
     }
+    return RT_OK;
+  });
+}
+
+// ---- scenes with motion
+int rt_motion_version(void) { return 1; }
+
+int rt_scene_has_motion(const rt_scene* s) { return s && s->inst && s->inst->has_motion ? 1 : 0; }
+
+int rt_scene_create_moving(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                           const rt_motion_desc* motion, int device, rt_scene** out) {
+  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_moving: NULL argument");
+  *out = nullptr;
+  bool trivial = false;
+  const int checked = guarded([&] {
+    check_instance_desc("rt_scene_create_moving", instances);
+    trivial = motion_trivial(*desc, instances, motion);
+    return RT_OK;
+  });
+  if (checked != RT_OK) return checked;
+  if (trivial) return rt_scene_create_instanced(desc, instances, device, out);
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    s->inst = std::make_unique<InstHost>();
+    build_host_globals(*desc, s->host);
+    build_moving(*desc, instances, motion, kDefaultTreeletLeaves, *s->inst);
+    return create_instanced(s.get(), device);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+namespace {
+// The motion descriptor of what load_instances_xml(..., motion) read.
+rt_motion_desc xml_motion_desc(const XmlInstances& xi, const rt_scene_desc& d) {
+  return rt_motion_desc{sizeof(rt_motion_desc), (int)xi.mesh.size(), d.num_spheres,
+                        xi.velocity.data(), xi.sphere_transform.data(), xi.sphere_velocity.data()};
+}
+}  // namespace
+
+int rt_scene_load_xml_moving(const char* xml_path, int device, rt_scene** out) {
+  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_moving: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    XmlSceneStorage st;
+    XmlInstances xi;
+    rt_scene_desc d;
+    load_instances_xml(xml_path, st, d, xi, true);
+    s->host.image_names = st.image_names;
+    const rt_instance_desc in{sizeof(rt_instance_desc), (int)xi.mesh.size(), xi.mesh.data(),
+                              xi.material.data(), xi.transform.data()};
+    const rt_motion_desc mo = xml_motion_desc(xi, d);
+    if (motion_trivial(d, &in, &mo)) {  // rt_scene_load_xml_instanced's scene
+      if (xi.mesh.empty()) {
+        build_host_scene(d, s->host);
+        return create_from_host(s.get(), single_device(device), false);
+      }
+      s->inst = std::make_unique<InstHost>();
+      build_host_globals(d, s->host);
+      build_instanced(d, in, kDefaultTreeletLeaves, *s->inst);
+      return create_instanced(s.get(), device);
+    }
+    s->inst = std::make_unique<InstHost>();
+    build_host_globals(d, s->host);
+    build_moving(d, &in, &mo, kDefaultTreeletLeaves, *s->inst);
+    return create_instanced(s.get(), device);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_host_motion_xml(const char* xml_path, float* instance_velocity3, float* sphere_transform16,
+                       float* sphere_velocity3, int capacity, int* counts2) {
+  if (!xml_path || capacity < 0) return set_error(RT_E_INVALID, "rt_host_motion_xml: bad argument");
+  return guarded([&] {
+    XmlSceneStorage st;
+    XmlInstances xi;
+    rt_scene_desc d;
+    load_instances_xml(xml_path, st, d, xi, true);
+    const size_t ni = std::min(xi.mesh.size(), (size_t)capacity);
+    const size_t ns = std::min((size_t)d.num_spheres, (size_t)capacity);
+    if (instance_velocity3 && ni)
+      std::memcpy(instance_velocity3, xi.velocity.data(), 3 * ni * sizeof(float));
+    if (sphere_transform16 && ns)
+      std::memcpy(sphere_transform16, xi.sphere_transform.data(), 16 * ns * sizeof(float));
+    if (sphere_velocity3 && ns)
+      std::memcpy(sphere_velocity3, xi.sphere_velocity.data(), 3 * ns * sizeof(float));
+    if (counts2) {
+      counts2[0] = (int)xi.mesh.size();
+      counts2[1] = d.num_spheres;
+    }
+    return RT_OK;
+  });
+}
+
+int rt_host_motion_info_desc(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                             const rt_motion_desc* motion, float* inst_box6,
+                             float* sphere_inverse16, float* sphere_box6, int* top_dfs) {
+  if (!desc) return set_error(RT_E_INVALID, "rt_host_motion_info_desc: NULL argument");
+  return guarded([&] {
+    check_instance_desc("rt_host_motion_info_desc", instances);
+    InstHost ih;
+    build_moving(*desc, instances, motion, kDefaultTreeletLeaves, ih);
+    for (size_t i = 0; inst_box6 && i < ih.instances.size(); i++)
+      std::memcpy(inst_box6 + 6 * i, ih.instances[i].box, 6 * sizeof(float));
+    if (sphere_inverse16 && !ih.sphere_inverse.empty())
+      std::memcpy(sphere_inverse16, ih.sphere_inverse.data(),
+                  ih.sphere_inverse.size() * sizeof(float));
+    if (sphere_box6 && !ih.sphere_box.empty())
+      std::memcpy(sphere_box6, ih.sphere_box.data(), ih.sphere_box.size() * sizeof(float));
+    if (top_dfs && !ih.object_top_dfs.empty())
+      std::memcpy(top_dfs, ih.object_top_dfs.data(), ih.object_top_dfs.size() * sizeof(int));
+    return RT_OK;
+  });
+}
+
+int rt_debug_motion_inverse(rt_scene* s, int top_object, const float* times, long long n,
+                            float* out12) {
+  return guarded([&] {
+    if (!s || n < 0 || (n > 0 && (!times || !out12)))
+      throw std::invalid_argument("rt_debug_motion_inverse: bad argument");
+    if (!rt_scene_has_motion(s))
+      throw std::invalid_argument("rt_debug_motion_inverse: not a scene with motion");
+    const InstHost& ih = *s->inst;
+    if (top_object < 0 || (size_t)top_object >= ih.object_top_dfs.size())
+      throw std::invalid_argument("rt_debug_motion_inverse: top_object out of range");
+    Replica& r = *s->rep[0];
+    const DevPrim& p = ih.top_prims[(size_t)ih.object_top_dfs[(size_t)top_object]];
+    const float *fwd = nullptr, *vel = nullptr;
+    if (p.kind == kPrimInstance && ih.instances[(size_t)p.material].moving) {
+      fwd = r.d_motion_instances.p[p.material].fwd;  // (device addresses: not read here)
+      vel = r.d_motion_instances.p[p.material].vel;
+    } else if (p.kind == kPrimMovingSphere && ih.motion_spheres[(size_t)p.material].moving) {
+      fwd = r.d_motion_spheres.p[p.material].fwd;
+      vel = r.d_motion_spheres.p[p.material].vel;
+    } else {
+      throw std::invalid_argument("rt_debug_motion_inverse: the object does not move");
+    }
+    if (n == 0) return RT_OK;
+    DeviceGuard g(r.device);
+    DevBuf<float> d_times, d_out;
+    d_times.reserve((size_t)n, "alloc times");
+    d_out.reserve(12 * (size_t)n, "alloc inverses");
+    hip_check(hipMemcpy(d_times.p, times, (size_t)n * sizeof(float), hipMemcpyHostToDevice),
+              "upload times");
+    hip_check(launch_motion_inverse(fwd, vel, d_times.p, n, d_out.p, nullptr), "inverse launch");
+    hip_check(hipMemcpy(out12, d_out.p, 12 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost),
+              "download inverses");
     return RT_OK;
   });
 }
@@ -2592,7 +2780,7 @@ void film_shade_on(rt_film* f, const rt_ray* rays, const float* xy, long long n,
   film_splat_on(f, xy, ws.film_rad.p, rays, n, ws, stream);
 }
 
-constexpr int kFilmShadeFlags = RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM;
+constexpr int kFilmShadeFlags = RT_QUERY_REORDER | RT_QUERY_IN_MEDIUM | RT_QUERY_RAY_TIME;
 
 // A `_device` entry's body on the caller's stream, with that stream's working set.
 template <typename Body>

@@ -575,7 +575,8 @@ struct alignas(16) DevInstance {
   float inv[12];  // rows 0..2 of the inverse matrix, four columns each
   float box[6];   // Bounding_box::apply_transform of the base mesh's root box
   int32_t mesh, material;
-  int32_t pad[4];
+  int32_t moving;  // a scene with motion (below): the instance has a velocity; else 0
+  int32_t pad[3];
 };
 static_assert(sizeof(DevInstance) == 96, "instance record is six 16-byte words");
 struct alignas(16) DevMesh {
@@ -606,6 +607,95 @@ struct InstParams {
   int top_quot_ok;           // quot_coord_ok of every loose triangle's v0
   float top_box[6];
 };
+
+// Scenes with motion (rt_scene_create_moving).  A ray carries a time tau; an
+// instance or sphere with a velocity v is met through the inverse of A = T(tau v) * M, built per
+// ray by motion_inverse below.  What a moving object needs beyond its 96-byte DevInstance sits in
+// tables of their own, read only on the moving branch.  A sphere with a matrix other than the
+// identity, or with a velocity, is a top-level kind of its own: kPrimMovingSphere, its DevPrim's
+// `material` the index of its DevMotionSphere.  The motion kernels take MotionParams as one more
+// argument; no other kernel's argument list changes.
+constexpr int32_t kPrimMovingSphere = 3;
+struct alignas(16) DevMotionInstance {
+  float fwd[16];  // M, row-major (object -> world)
+  float vel[3];
+  int32_t pad;
+};
+static_assert(sizeof(DevMotionInstance) == 80, "");
+struct alignas(16) DevMotionSphere {
+  float fwd[16];  // M
+  float inv[12];  // rows 0..2 of Mat4::inverse(M): the walk's matrix when the sphere does not move
+  float vel[3];
+  int32_t moving;  // vel != 0
+  float center[3];
+  float radius;
+  int32_t material;
+  int32_t pad[3];
+};
+static_assert(sizeof(DevMotionSphere) == 160, "");
+struct MotionParams {
+  const DevMotionInstance* instances;  // per instance
+  const DevMotionSphere* spheres;      // per kPrimMovingSphere record
+  int fast;      // the base meshes that have a culling tree are walked through it
+  int ray_time;  // RT_QUERY_RAY_TIME: the rays' fourth direction word is their time, else 0
+};
+
+// Rows 0..2 of the inverse of T(tau * vel) * fwd, in the reference's order (HW3 Mesh.h:77-82,
+// Sphere.h:114-119): delta = tau * vel per component; Matrix4x4::operator* with T(delta) written
+// out, every result[i][j] from 0 through its four products, the ones with 0 and 1 included (they
+// turn a -0 entry into +0); then Matrix4x4::invert_matrix as Mat4::inverse restates it (mat4.h),
+// but only the twelve cofactors of rows 0..2 and the one that completes the determinant.  One
+// definition for the device's walk and the host's checks; every file that includes this compiles
+// with contraction off.  det == 0: twelve NaNs and false (the object is missed: a NaN local ray
+// is no valid ray).
+RT_HD inline bool motion_inverse(const float* fwd, const float* vel, float tau, float* inv) {
+  const float delta[3] = {tau * vel[0], tau * vel[1], tau * vel[2]};
+  float m[16];
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++) {
+      float acc = 0.0f;
+      for (int k = 0; k < 4; k++) {
+        const float tik = k == 3 ? (i < 3 ? delta[i] : 1.0f) : (i == k ? 1.0f : 0.0f);
+        acc += tik * fwd[4 * k + j];
+      }
+      m[4 * i + j] = acc;
+    }
+  float c[13];
+  c[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] +
+         m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+  c[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] -
+         m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+  c[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] +
+         m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+  c[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] -
+          m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+  c[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] -
+         m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+  c[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] +
+         m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+  c[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] -
+         m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+  c[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] +
+         m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+  c[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] -
+         m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+  c[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] +
+          m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+  c[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] -
+         m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+  c[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] +
+         m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+  c[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] -
+          m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+  float det = m[0] * c[0] + m[1] * c[4] + m[2] * c[8] + m[3] * c[12];
+  if (det == 0.0f) {
+    for (int k = 0; k < 12; k++) inv[k] = __builtin_nanf("");
+    return false;
+  }
+  det = 1.0f / det;
+  for (int k = 0; k < 12; k++) inv[k] = c[k] * det;
+  return true;
+}
 
 // rt_hit_attributes*: rays, hits and attr hold n records each.
 struct AttrParams {

@@ -1982,10 +1982,15 @@ static_assert(offsetof(DevMesh, root_kind) == 48 && offsetof(DevMesh, root_box) 
 // OCC == false: the closest hit of every valid lane's ray w — bt, and btop / bleaf (the top-level
 // position and, under an instance, the mesh leaf; -1: a miss).  OCC == true: returns whether some
 // reachable primitive has 0 < t < thr; a lane found occluded leaves the walk.
-template <bool FAST, bool SPHERES, bool OCC>
+// MOTION (the motion kernels only): the lane's ray has the time tau.  A moving
+// instance (DevInstance::moving, wave-uniform) is entered through the lane's own inverse of
+// T(tau v) * M and then exactly as a static one; a kPrimMovingSphere is tested on its local ray
+// (Sphere.h:76-154; no box of its own, as there).  Mo->fast replaces FAST at run time.
+template <bool FAST, bool SPHERES, bool OCC, bool MOTION = false>
 __device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParams& T,
                                           WaveLeafLds& L, const LaneRay& w, bool valid, float thr,
-                                          float& bt, int& btop, int& bleaf, Diag& dg) {
+                                          float& bt, int& btop, int& bleaf, Diag& dg,
+                                          const MotionParams* Mo = nullptr, float tau = 0.0f) {
   bt = RT_INF;
   btop = -1;
   bleaf = -1;
@@ -2038,6 +2043,12 @@ __device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParam
         float inv[12];
 #pragma unroll
         for (int e = 0; e < 12; e++) inv[e] = __int_as_float(ia[e]);
+        if constexpr (MOTION) {
+          if (ib[4]) {  // it moves: each lane its own inverse (NaNs where det == 0: a miss below)
+            const DevMotionInstance& mi = Mo->instances[uniform(tp->material)];
+            motion_inverse(mi.fwd, mi.vel, tau, inv);
+          }
+        }
         const float box[6] = {__int_as_float(ia[12]), __int_as_float(ia[13]),
                               __int_as_float(ia[14]), __int_as_float(ia[15]),
                               __int_as_float(ib[0]), __int_as_float(ib[1])};
@@ -2054,16 +2065,18 @@ __device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParam
         }
         const RenderParams V = mesh_view(P, ma, mb);
         const LaneRay lr = make_ray(lo, ld, V.quot_ok);
+        bool culled = FAST && V.accel_root >= 0;
+        if constexpr (MOTION) culled = culled && Mo->fast;
         if (OCC) {
           bool o;
-          if (FAST && V.accel_root >= 0)
+          if (culled)
             o = occluded<true, true, false, false>(V, V.nodes, nullptr, L, lr, go, thr, dg);
           else
             o = occluded<true, false, false, false>(V, V.nodes, nullptr, L, lr, go, thr, dg);
           occ |= go && o;
           hit = false;
         } else {
-          if (FAST && V.accel_root >= 0)
+          if (culled)
             closest_hit<true, true, false, false>(V, V.nodes, nullptr, L, lr, go, t, leaf, dg);
           else
             closest_hit<true, false, false, false>(V, V.nodes, nullptr, L, lr, go, t, leaf, dg);
@@ -2072,7 +2085,21 @@ __device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParam
           hit = go && leaf >= 0 && (lone || t < RT_INF);
         }
       } else {
-        hit = in && leaf_test<SPHERES>(T.top_prims, pos, w, t);
+        bool plain = true;
+        if constexpr (MOTION) {
+          if (kind == kPrimMovingSphere) {  // Sphere.h:76-154: sphere_test on the local ray
+            plain = false;
+            const DevMotionSphere& S = Mo->spheres[uniform(tp->material)];
+            float inv[12];
+#pragma unroll
+            for (int e = 0; e < 12; e++) inv[e] = S.inv[e];
+            if (S.moving) motion_inverse(S.fwd, S.vel, tau, inv);
+            const V3 lo = inst_point(inv, w.o), ld = inst_vector(inv, w.d);
+            const LaneRay lr = make_ray(lo, ld, 0);
+            hit = in && query_ray_ok(lo, ld) && sphere_test(ld3(S.center), S.radius, lr, t);
+          }
+        }
+        if (plain) hit = in && leaf_test<SPHERES>(T.top_prims, pos, w, t);
         // in the tree: the leaf rule 0 < t < inf; the lone object: its own answer as it is
         if (!lone) hit = hit && t > 0.0f && t < RT_INF;
         if (OCC) {
@@ -2105,11 +2132,80 @@ __device__ __forceinline__ bool inst_walk(const RenderParams& P, const InstParam
 // Hit_data::normal / the material come from the instance (Mesh.h:69) or the loose primitive.
 struct NoInst {
   static constexpr bool on = false;
+  static constexpr bool motion = false;
 };
 struct InstArg {
   static constexpr bool on = true;
+  static constexpr bool motion = false;
   InstParams T;
 };
+// A scene with motion: the lane's time too, one constant for its whole ray tree
+// (HW3/src/Scene.cpp:153, 196, 226, 258: every secondary ray inherits it).
+struct MotionArg {
+  static constexpr bool on = true;
+  static constexpr bool motion = true;
+  InstParams T;
+  MotionParams M;
+  float tau;
+};
+template <bool FAST, bool SPHERES>
+__device__ __forceinline__ bool inst_occluded(const RenderParams& P, const MotionArg& inst,
+                                              WaveLeafLds& L, const LaneRay& sr, bool active,
+                                              float thr, Diag& dg, std::bool_constant<FAST>,
+                                              std::bool_constant<SPHERES>) {
+  float t;
+  int top, leaf;
+  return inst_walk<FAST, SPHERES, true, true>(P, inst.T, L, sr, active, thr, t, top, leaf, dg,
+                                              &inst.M, inst.tau);
+}
+
+// What a motion kernel reports of the winner of inst_walk (top >= 0), computed after the walk for
+// the winner only: a moving object's inverse is built again from tau rather than carried across
+// the inner walk.  The normal is (A^-1)^T.multiply(n, true).normalize(): of the mesh's flat normal
+// (Mesh.h:69, 87), or of the local (o' + t d' - center).normalize() (Sphere.h:91, 133).
+struct MotionHit {
+  V3 n;
+  int material, object, leaf, instance;
+};
+__device__ __forceinline__ MotionHit motion_hit(const InstParams& T, const MotionParams& M,
+                                                const LaneRay& ray, float tau, float t, int top,
+                                                int mesh_leaf) {
+  const DevPrim& pr = T.top_prims[top];
+  MotionHit h;
+  if (pr.kind == kPrimInstance) {
+    const DevInstance& I = T.instances[pr.material];
+    const DevMesh& Me = T.meshes[I.mesh];
+    float inv[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) inv[e] = I.inv[e];
+    const DevMotionInstance& mi = M.instances[pr.material];  // (read only when it moves)
+    if (I.moving) motion_inverse(mi.fwd, mi.vel, tau, inv);
+    h.n = normalize(inst_normal(inv, ld3(Me.normals + 4 * mesh_leaf)));
+    h.material = I.material;
+    h.object = Me.object_base + Me.leaf_object[mesh_leaf];
+    h.leaf = Me.leaf_base + mesh_leaf;
+    h.instance = pr.material;
+    return h;
+  }
+  if (pr.kind == kPrimMovingSphere) {
+    const DevMotionSphere& S = M.spheres[pr.material];
+    float inv[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) inv[e] = S.inv[e];
+    if (S.moving) motion_inverse(S.fwd, S.vel, tau, inv);
+    const V3 lo = inst_point(inv, ray.o), ld = inst_vector(inv, ray.d);
+    h.n = normalize(inst_normal(inv, normalize((lo + ld * t) - ld3(S.center))));
+    h.material = S.material;
+  } else {
+    h.n = pr.kind == kPrimTriangle ? ld3(T.top_normals + 4 * top)
+                                   : normalize((ray.o + ray.d * t) - ld3(pr.v0));
+    h.material = pr.material;
+  }
+  h.object = T.top_info[2 * top];
+  h.leaf = T.top_info[2 * top + 1];
+  h.instance = -1;
+  return h;
+}
 // A shadow ray of an instanced scene's local shading.
 template <bool FAST, bool SPHERES>
 __device__ __forceinline__ bool inst_occluded(const RenderParams& P, const InstArg& inst,
@@ -2253,7 +2349,10 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
     float t;
     int leaf;
     [[maybe_unused]] int mesh_leaf = -1;  // INST: `leaf` is the top-level position
-    if constexpr (Inst::on)
+    if constexpr (Inst::motion)
+      inst_walk<FAST, SPHERES, false, true>(P, inst.T, L, ray, active, 0.0f, t, leaf, mesh_leaf, dg,
+                                            &inst.M, inst.tau);
+    else if constexpr (Inst::on)
       inst_walk<FAST, SPHERES, false>(P, inst.T, L, ray, active, 0.0f, t, leaf, mesh_leaf, dg);
     else if (skip)
       closest_hit<true, FAST, DEEP, SPHERES>(P, nodes, spill, L, ray, active, t, leaf, dg);
@@ -2269,7 +2368,11 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
     int mat = 0;
     if (hit) {
       p = ray.o + ray.d * t;
-      if constexpr (Inst::on) {
+      if constexpr (Inst::motion) {
+        const MotionHit h = motion_hit(inst.T, inst.M, ray, inst.tau, t, leaf, mesh_leaf);
+        n = h.n;
+        mat = h.material;
+      } else if constexpr (Inst::on) {
         const DevPrim& pr = inst.T.top_prims[leaf];
         if (pr.kind == kPrimInstance) {  // Mesh.h:69: the instance's normal matrix and material
           const DevInstance& I = inst.T.instances[pr.material];
@@ -2792,6 +2895,19 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void inst_recursive_kernel(
                                                         surf_of(), inst);
 }
 
+// ... and for a scene with motion: frames render at time 0 (inst.tau, set by the
+// host), so a moving object stands where its matrix puts it, through the moving branch's code.
+__global__ __launch_bounds__(kWavesPerBlock * 64) void motion_recursive_kernel(
+    RenderParams P, const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights,
+    MotionArg inst) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  const int sel = packet_index<kWavesPerBlock>();
+  if (sel >= P.num_sel_tiles) return;
+  recursive_packet<true, false, true, false, MotionArg>(P, nullptr, nullptr, nullptr, mats, lights,
+                                                        sel, nullptr, leaf_lds[threadIdx.x >> 6],
+                                                        surf_of(), inst);
+}
+
 // marks (nullable): 4 events recorded before the frame kernel (or the recursive kernel), after
 // it, after the order kernel and at the end (rt_set_kernel_timing).
 static inline void mark(const hipEvent_t* marks, int k, hipStream_t stream) {
@@ -3146,6 +3262,7 @@ int max_supported_depth() { return kDeepStack; }
 struct QueryRay {
   V3 o, d;
   float tmax;
+  float time;  // rt_ray::pad as it lies: read by the motion kernels alone (load_motion_ray)
   bool in;     // i < n: the lane has a result slot
   bool valid;  // ... and a ray to trace
 };
@@ -3176,6 +3293,7 @@ __device__ __forceinline__ QueryRay load_query_ray(const QueryParams& Q, long lo
   q.o = v3(a.x, a.y, a.z);
   q.d = v3(b.x, b.y, b.z);
   q.tmax = a.w;
+  q.time = b.w;
   q.valid = q.in && query_ray_ok(q.o, q.d);
   if (!q.valid) {  // an idle lane still takes part in the wave-wide steps: a harmless ray
     q.o = v3(0.0f, 0.0f, 0.0f);
@@ -3312,6 +3430,83 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void inst_occluded_kernel(Rend
     reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ scenes with motion: query kernels
+//   The INST kernels with a time per lane: rt_ray::pad with RT_QUERY_RAY_TIME
+// (M.ray_time), else 0.  A ray whose time is not finite is INVALID, as one with a non-finite
+// component.  One instantiation each: loose spheres compiled in, the traversal mode a run-time
+// choice (M.fast).
+__device__ __forceinline__ QueryRay load_motion_ray(const QueryParams& Q, const MotionParams& M,
+                                                    long long i) {
+  QueryRay q = load_query_ray(Q, i);
+  if (!M.ray_time) q.time = 0.0f;
+  if (!(__builtin_fabsf(q.time) < RT_INF)) q.valid = false;
+  if (!q.valid) {
+    q.o = v3(0.0f, 0.0f, 0.0f);
+    q.d = v3(0.0f, 0.0f, 1.0f);
+    q.time = 0.0f;
+  }
+  return q;
+}
+
+__global__ __launch_bounds__(kWavesPerBlock * 64) void motion_closest_kernel(RenderParams P,
+                                                                             QueryParams Q,
+                                                                             InstParams T,
+                                                                             MotionParams M) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_motion_ray(Q, M, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, T.top_quot_ok);
+  Diag dg;
+  float t;
+  int top, leaf;
+  inst_walk<true, true, false, true>(P, T, L, ray, q.valid, 0.0f, t, top, leaf, dg, &M, q.time);
+  f4 h0 = {RT_INF, __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)};
+  f4 h1 = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (q.valid && top >= 0) {
+    const MotionHit h = motion_hit(T, M, ray, q.time, t, top, leaf);
+    h0 = (f4){t, __int_as_float(h.object), __int_as_float(h.material), __int_as_float(h.leaf)};
+    h1 = (f4){h.n.x, h.n.y, h.n.z, __int_as_float(h.instance)};
+  }
+  const long long i = query_index();
+  if (i < Q.n) {
+    f4* out = reinterpret_cast<f4*>(Q.out) + 2 * query_slot(Q, i);
+    out[0] = h0;
+    out[1] = h1;
+  }
+}
+
+__global__ __launch_bounds__(kWavesPerBlock * 64) void motion_occluded_kernel(RenderParams P,
+                                                                              QueryParams Q,
+                                                                              InstParams T,
+                                                                              MotionParams M) {
+  __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
+  if ((query_index() & ~63ll) >= Q.n) return;
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_motion_ray(Q, M, query_index());
+  const LaneRay ray = make_ray(q.o, q.d, T.top_quot_ok);
+  Diag dg;
+  float t;
+  int top, leaf;
+  const bool occ = inst_walk<true, true, true, true>(P, T, L, ray, q.valid, q.tmax, t, top, leaf,
+                                                     dg, &M, q.time);
+  const long long i = query_index();
+  if (i < Q.n)
+    reinterpret_cast<unsigned char*>(Q.out)[query_slot(Q, i)] = (q.valid && occ) ? 1 : 0;
+}
+
+// rt_debug_motion_inverse: the walk's own motion_inverse of one moving object's record at n times.
+__global__ void motion_inverse_kernel(const float* __restrict__ fwd, const float* __restrict__ vel,
+                                      const float* __restrict__ times, long long n,
+                                      float* __restrict__ out12) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float inv[12];
+  motion_inverse(fwd, vel, times[i], inv);
+#pragma unroll
+  for (int e = 0; e < 12; e++) out12[12 * i + e] = inv[e];
+}
+
 // Radiance of caller-supplied rays (rt_shade_rays_device): the layout of
 // query_closest_kernel, and between the lane's two 16-B loads and its one 16-B store the ray tree
 // of trace_tree from (o, d, R.in_medium, R.depth).  One launch covers the rays
@@ -3400,6 +3595,48 @@ __global__ __launch_bounds__(kRadianceWaves * 64) void inst_radiance_kernel(
     own_k = lit.k;
   }
   const V3 c = trace_tree<FAST, false, SPHERES, RECURSE, LIT, false, InstArg>(
+      P, nullptr, nullptr, nullptr, mats, lights, nullptr, L, RECURSE ? R.frames + slot : nullptr,
+      (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, surf_of(), own, own_k,
+      inst);
+  if (i < Q.n) {
+    const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
+    reinterpret_cast<f4*>(Q.out)[query_slot(Q, i)] = out;
+  }
+  if (P.counters) {
+    unsigned long long* row = counter_row(P, (int)((i >> 6) % kCounterSlots));
+    if (cnt.secondary) atomicAdd(&row[kCntSecondary], cnt.secondary);
+    if (lane_id() == 0) {
+      atomicAdd(&row[kCntPrimary], n_primary);
+      atomicAdd(&row[kCntHits], cnt.hits);
+      atomicAdd(&row[kCntShadow], cnt.shadow);
+    }
+  }
+}
+
+// inst_radiance_kernel for a scene with motion: the lane's time goes with the
+// scene's tables into every walk of its ray tree.
+template <bool RECURSE, bool LIT>
+__global__ __launch_bounds__(kRadianceWaves * 64) void motion_radiance_kernel(
+    RenderParams P, QueryParams Q, RadianceParams R, const DevMaterial* __restrict__ mats,
+    const DevLight* __restrict__ lights, LitArg<LIT> lit, InstParams T, MotionParams M) {
+  __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
+  const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;
+  const long long i = R.first + slot;
+  if ((i & ~63ll) >= Q.n) return;  // the whole wave is past the batch
+  WaveLeafLds& L = leaf_lds[threadIdx.x >> 6];
+  const QueryRay q = load_motion_ray(Q, M, i);
+  const unsigned long long n_primary = __builtin_popcountll(ballot(q.valid));
+  float t;
+  TreeCounts cnt;
+  const f4* own = nullptr;
+  int own_k = 0;
+  if constexpr (LIT) {
+    const long long ray = q.in && !lit.shared ? query_slot(Q, i) : 0;
+    own = reinterpret_cast<const f4*>(lit.lights) + 3 * (size_t)ray * (size_t)lit.k;
+    own_k = lit.k;
+  }
+  const MotionArg inst{T, M, q.time};
+  const V3 c = trace_tree<true, false, true, RECURSE, LIT, false, MotionArg>(
       P, nullptr, nullptr, nullptr, mats, lights, nullptr, L, RECURSE ? R.frames + slot : nullptr,
       (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, surf_of(), own, own_k,
       inst);
@@ -3608,7 +3845,7 @@ hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nod
 // culling tree are walked through it; spheres: the top level holds a loose sphere.
 hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstParams& T,
                              bool occlusion, bool reorder, bool fast, bool spheres,
-                             hipStream_t stream) {
+                             const MotionParams* motion, hipStream_t stream) {
   if (Q.n <= 0) return hipSuccess;
   Q.perm = nullptr;
   if (reorder) {
@@ -3617,6 +3854,15 @@ hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstPar
     Q.perm = Q.perm_out;
   }
   const dim3 grid((unsigned)((Q.n + kWavesPerBlock * 64 - 1) / (kWavesPerBlock * 64)));
+  if (motion) {  // a scene with motion: its own kernels (motion->fast: the traversal mode)
+    if (occlusion)
+      hipLaunchKernelGGL(motion_occluded_kernel, grid, dim3(kWavesPerBlock * 64), 0, stream, P, Q,
+                         T, *motion);
+    else
+      hipLaunchKernelGGL(motion_closest_kernel, grid, dim3(kWavesPerBlock * 64), 0, stream, P, Q,
+                         T, *motion);
+    return hipGetLastError();
+  }
   dispatch_variant(fast, false, spheres, [&](auto fa, auto, auto sp) {
     constexpr bool F = decltype(fa)::value, S = decltype(sp)::value;
     if (occlusion)
@@ -3653,9 +3899,31 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
                            bool spheres, const SurfParams* surf, const InstParams* inst,
-                           hipStream_t stream) {
+                           const MotionParams* motion, hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
   const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
+  if (inst && motion) {  // a scene with motion: its own kernels
+    auto launch = [&](auto re, auto li, auto arg) {
+      hipLaunchKernelGGL((motion_radiance_kernel<decltype(re)::value, decltype(li)::value>), grid,
+                         dim3(kRadianceWaves * 64), 0, stream, P, Q, R, P.materials, P.lights, arg,
+                         *inst, *motion);
+    };
+    using T = std::true_type;
+    using N = std::false_type;
+    if (lit) {
+      LitArg<true> arg;
+      static_cast<LitParams&>(arg) = *lit;
+      if (R.frames == nullptr)
+        launch(N{}, T{}, arg);
+      else
+        launch(T{}, T{}, arg);
+    } else if (R.frames == nullptr) {
+      launch(N{}, N{}, LitArg<false>{});
+    } else {
+      launch(T{}, N{}, LitArg<false>{});
+    }
+    return hipGetLastError();
+  }
   if (inst) {  // an instanced scene: the INST kernels (fast: the base meshes' culling trees)
     const InstArg ia{*inst};
     dispatch_variant(fast, false, spheres, [&](auto fa, auto, auto sp) {
@@ -3886,11 +4154,30 @@ hipError_t launch_quot_check(int mode, unsigned long long seed, long long count,
   return hipGetLastError();
 }
 
+hipError_t launch_motion_inverse(const float* fwd, const float* vel, const float* times,
+                                 long long n, float* out12, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(motion_inverse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     fwd, vel, times, n, out12);
+  return hipGetLastError();
+}
+
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
                          const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
-                         hipStream_t stream) {
+                         const MotionParams* motion, hipStream_t stream) {
   if (P.num_sel_tiles <= 0) return hipSuccess;
   const int blocks = (P.num_sel_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (inst && motion) {  // a scene with motion: every ray of the frame at time 0
+    if (!P.frames) return hipErrorInvalidValue;
+    const MotionArg ma{*inst, *motion, 0.0f};
+    mark(marks, 0, stream);
+    hipLaunchKernelGGL(motion_recursive_kernel, dim3(blocks), dim3(kWavesPerBlock * 64), 0, stream,
+                       P, P.materials, P.lights, ma);
+    mark(marks, 1, stream);
+    mark(marks, 2, stream);
+    mark(marks, 3, stream);
+    return hipGetLastError();
+  }
   if (inst) {  // an instanced scene renders on the ray-tree path (P.frames: the host sees to it)
     if (!P.frames) return hipErrorInvalidValue;
     const InstArg ia{*inst};

@@ -92,30 +92,35 @@ class Film:
         check(lib().rt_film_splat(self._h, pos.ctypes.data, rad.ctypes.data, len(src)))
 
     def shade_rays(self, origins, directions, xy, *, depth: Optional[int] = None,
-                   in_medium: bool = False, reorder: bool = False, stats: bool = False):
+                   in_medium: bool = False, reorder: bool = False, stats: bool = False,
+                   time=None):
         """``Scene.shade_rays`` of the rays, splatted at ``xy`` without leaving the GPU.  With
-        ``stats`` returns the call's rt_stats."""
-        rays = pack_rays(origins, directions)
+        ``stats`` returns the call's rt_stats.  ``time``: the rays' times (motion blur: one
+        sample per ray, each at its own time)."""
+        rays = pack_rays(origins, directions, time=time)
         pos = _positions(xy, len(rays))
         st = _lib.rt_stats()
         check(lib().rt_film_shade_rays(self._h, rays.ctypes.data, pos.ctypes.data, len(rays),
                                        -1 if depth is None else int(depth),
-                                       Scene._radiance_flags(in_medium, reorder), C.byref(st)))
+                                       Scene._radiance_flags(in_medium, reorder, time is not None),
+                                       C.byref(st)))
         return st if stats else None
 
     def shade_rays_lit(self, origins, directions, xy, lights, *, shared: bool = False,
                        scene_lights: bool = True, depth: Optional[int] = None,
-                       in_medium: bool = False, reorder: bool = False, stats: bool = False):
+                       in_medium: bool = False, reorder: bool = False, stats: bool = False,
+                       time=None):
         """``Scene.shade_rays_lit`` of the rays (``lights``: (n, k) LIGHT_SAMPLE_DTYPE records,
         or (k,) with ``shared``), splatted at ``xy`` without leaving the GPU."""
-        rays = pack_rays(origins, directions)
+        rays = pack_rays(origins, directions, time=time)
         pos = _positions(xy, len(rays))
         lit, k = pack_lights(lights, len(rays), shared)
         st = _lib.rt_stats()
         check(lib().rt_film_shade_rays_lit(
             self._h, rays.ctypes.data, pos.ctypes.data, len(rays),
             -1 if depth is None else int(depth), lit.ctypes.data, k,
-            Scene._lit_flags(in_medium, reorder, shared, scene_lights), C.byref(st)))
+            Scene._lit_flags(in_medium, reorder, shared, scene_lights, time is not None),
+            C.byref(st)))
         return st if stats else None
 
     def resolve(self) -> np.ndarray:
@@ -148,24 +153,26 @@ class Film:
 
     def shade_rays_device(self, rays_ptr: int, xy_ptr: int, n: int, *,
                           depth: Optional[int] = None, in_medium: bool = False,
-                          reorder: bool = False, stream: int = 0) -> None:
+                          reorder: bool = False, stream: int = 0, ray_time: bool = False) -> None:
         """rt_film_shade_rays_device: n rt_ray records and their n x 2 positions in device
         memory; the ray counts go to the scene's collect_stats()."""
         check(lib().rt_film_shade_rays_device(self._h, C.c_void_p(rays_ptr), C.c_void_p(xy_ptr), n,
                                               -1 if depth is None else int(depth),
-                                              Scene._radiance_flags(in_medium, reorder),
+                                              Scene._radiance_flags(in_medium, reorder, ray_time),
                                               C.c_void_p(stream)))
 
     def shade_rays_lit_device(self, rays_ptr: int, xy_ptr: int, n: int, lights_ptr: int, k: int, *,
                               shared: bool = False, scene_lights: bool = True,
                               depth: Optional[int] = None, in_medium: bool = False,
-                              reorder: bool = False, stream: int = 0) -> None:
+                              reorder: bool = False, stream: int = 0,
+                              ray_time: bool = False) -> None:
         """rt_film_shade_rays_lit_device: as shade_rays_device, with the rays' n x k (shared: k)
         rt_light_sample records in device memory at ``lights_ptr``."""
         check(lib().rt_film_shade_rays_lit_device(
             self._h, C.c_void_p(rays_ptr), C.c_void_p(xy_ptr), n,
             -1 if depth is None else int(depth), C.c_void_p(lights_ptr), int(k),
-            Scene._lit_flags(in_medium, reorder, shared, scene_lights), C.c_void_p(stream)))
+            Scene._lit_flags(in_medium, reorder, shared, scene_lights, ray_time),
+            C.c_void_p(stream)))
 
     def resolve_device(self, out_ptr: int, *, stream: int = 0) -> None:
         """rt_film_resolve_device: width*height*3 floats at ``out_ptr``."""

@@ -39,8 +39,9 @@ def _aligned(n: int, dtype) -> np.ndarray:
     return raw[off:off + n * dtype.itemsize].view(dtype)
 
 
-def pack_rays(origins, directions, tmax=None) -> np.ndarray:
-    """(n, 3) origins and directions (and per-ray tmax) as a 16-byte aligned RAY_DTYPE array."""
+def pack_rays(origins, directions, tmax=None, time=None) -> np.ndarray:
+    """(n, 3) origins and directions (and per-ray tmax; ``time``: the rays' times, in ``pad``, read
+    by calls with RT_QUERY_RAY_TIME) as a 16-byte aligned RAY_DTYPE array."""
     o = np.asarray(origins, np.float32)
     d = np.asarray(directions, np.float32)
     if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
@@ -49,7 +50,13 @@ def pack_rays(origins, directions, tmax=None) -> np.ndarray:
     rays["o"], rays["d"] = o, d
     if tmax is not None:
         rays["tmax"] = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
+    if time is not None:
+        rays["pad"] = np.broadcast_to(np.asarray(time, np.float32), (len(o),))
     return rays
+
+
+def _time_flag(time) -> int:
+    return _lib.RT_QUERY_RAY_TIME if time is not None else 0
 
 
 def pack_lights(lights, n: int, shared: bool):
@@ -95,9 +102,15 @@ class Scene:
     """
 
     def __init__(self, file_name: str, device: int = -1, traversal: str = "fast",
-                 devices: Optional[list] = None, smooth: bool = False, instanced: bool = False):
+                 devices: Optional[list] = None, smooth: bool = False, instanced: bool = False,
+                 motion: bool = False):
         h = C.c_void_p()
-        if instanced:  # <Transformations> / <MeshInstance> honoured (rt_scene_load_xml_instanced)
+        if motion:  # rt_scene_load_xml_moving: also <MotionBlur> and a sphere's <Transformations>
+            if smooth or devices is not None or not instanced:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED, "scenes with motion are instanced, "
+                                   "single-device and flat-shaded")
+            check(lib().rt_scene_load_xml_moving(str(file_name).encode(), device, C.byref(h)))
+        elif instanced:  # <Transformations> / <MeshInstance> honoured (rt_scene_load_xml_instanced)
             if smooth or devices is not None:
                 raise _lib.RTError(_lib.RT_E_UNSUPPORTED, "instanced scenes are single-device "
                                    "and flat-shaded")
@@ -119,17 +132,34 @@ class Scene:
     @classmethod
     def create(cls, desc, mesh_smooth=None, vertex_normals=None, vertex_uv=None,
                device: int = -1, instance_mesh=None, instance_material=None,
-               instance_transform=None) -> "Scene":
+               instance_transform=None, instance_velocity=None, sphere_transform=None,
+               sphere_velocity=None) -> "Scene":
         """A scene from an ``rt_scene_desc`` with surface data (rt_scene_create_surface):
         ``mesh_smooth`` one flag per mesh, ``vertex_normals`` (num_vertices, 3) used as given
         (None: the area-weighted normals of the HW3 loader), ``vertex_uv`` (num_vertices, 2).
 
         Or a scene made of instances (rt_scene_create_instanced): ``instance_mesh`` and
         ``instance_material`` (n,) and ``instance_transform`` (n, 4, 4) object -> world; the
-        description's meshes are then bases only.  Not together with surface data."""
+        description's meshes are then bases only.  Not together with surface data.
+
+        Or a scene with motion (rt_scene_create_moving): ``instance_velocity`` (n, 3),
+        ``sphere_transform`` (num_spheres, 4, 4) and ``sphere_velocity`` (num_spheres, 3), each
+        optional, with or without instances."""
         given = [a is not None for a in (instance_mesh, instance_material, instance_transform)]
         if any(given) and not all(given):
             raise ValueError("instance_mesh, instance_material and instance_transform go together")
+        if any(a is not None for a in (instance_velocity, sphere_transform, sphere_velocity)):
+            if mesh_smooth is not None or vertex_normals is not None or vertex_uv is not None:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
+                                   "surface data in scenes with motion is not supported")
+            inst = keep = None
+            if instance_mesh is not None:
+                inst, keep = _instance_desc(instance_mesh, instance_material, instance_transform)
+            mo, keep2 = _motion_desc(desc, inst, instance_velocity, sphere_transform, sphere_velocity)
+            h = C.c_void_p()
+            check(lib().rt_scene_create_moving(C.byref(desc), C.byref(inst) if inst else None,
+                                               C.byref(mo), device, C.byref(h)))
+            return cls._from_handle(h)
         if instance_mesh is not None:
             if mesh_smooth is not None or vertex_normals is not None or vertex_uv is not None:
                 raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
@@ -304,39 +334,43 @@ class Scene:
                                       C.c_void_p(stream)))
 
     # ------------------------------------------------------------------ ray queries
-    def trace_rays(self, origins, directions, *, reorder: bool = False) -> np.ndarray:
+    def trace_rays(self, origins, directions, *, reorder: bool = False, time=None) -> np.ndarray:
         """Closest hit of each ray o + t d (rt_trace_rays): a HIT_DTYPE array with the
         reference's Hit_data::t and normal, the object / material / DFS leaf hit; a miss has
         t = +inf and object = material = leaf = -1.  ``reorder``: group similar rays before
-        tracing (RT_QUERY_REORDER; same results)."""
-        rays = pack_rays(origins, directions)
+        tracing (RT_QUERY_REORDER; same results).  ``time``: the rays' times, a scalar or (n,)
+        (RT_QUERY_RAY_TIME; a scene with motion meets its moving objects where they are then)."""
+        rays = pack_rays(origins, directions, time=time)
         hits = _aligned(len(rays), HIT_DTYPE)
         check(lib().rt_trace_rays(self._h, rays.ctypes.data, len(rays), hits.ctypes.data,
-                                  _lib.RT_QUERY_REORDER if reorder else 0))
+                                  (_lib.RT_QUERY_REORDER if reorder else 0) | _time_flag(time)))
         return hits
 
-    def occluded(self, origins, directions, tmax, *, reorder: bool = False) -> np.ndarray:
+    def occluded(self, origins, directions, tmax, *, reorder: bool = False,
+                 time=None) -> np.ndarray:
         """uint8[n]: 1 where something lies at 0 < t < tmax along the ray (rt_occluded)."""
-        rays = pack_rays(origins, directions, tmax)
+        rays = pack_rays(origins, directions, tmax, time)
         occ = np.zeros(len(rays), np.uint8)
         check(lib().rt_occluded(self._h, rays.ctypes.data, len(rays), occ.ctypes.data,
-                                _lib.RT_QUERY_REORDER if reorder else 0))
+                                (_lib.RT_QUERY_REORDER if reorder else 0) | _time_flag(time)))
         return occ
 
     def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, *, reorder: bool = False,
-                          stream: int = 0) -> None:
+                          stream: int = 0, ray_time: bool = False) -> None:
         """rt_trace_rays_device: n rt_ray records in device memory at ``rays_ptr`` (e.g. a torch
         tensor's ``data_ptr()``) to n rt_ray_hit records at ``hits_ptr``, asynchronously on HIP
         stream ``stream``."""
         check(lib().rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), n, C.c_void_p(hits_ptr),
-                                         _lib.RT_QUERY_REORDER if reorder else 0,
+                                         (_lib.RT_QUERY_REORDER if reorder else 0) |
+                                         (_lib.RT_QUERY_RAY_TIME if ray_time else 0),
                                          C.c_void_p(stream)))
 
     def occluded_device(self, rays_ptr: int, n: int, occ_ptr: int, *, reorder: bool = False,
-                        stream: int = 0) -> None:
+                        stream: int = 0, ray_time: bool = False) -> None:
         """rt_occluded_device: one byte (0 / 1) per ray at ``occ_ptr``."""
         check(lib().rt_occluded_device(self._h, C.c_void_p(rays_ptr), n, C.c_void_p(occ_ptr),
-                                       _lib.RT_QUERY_REORDER if reorder else 0,
+                                       (_lib.RT_QUERY_REORDER if reorder else 0) |
+                                       (_lib.RT_QUERY_RAY_TIME if ray_time else 0),
                                        C.c_void_p(stream)))
 
     # ------------------------------------------------------------------ hit attributes
@@ -344,6 +378,11 @@ class Scene:
     def num_instances(self) -> int:
         """Instances of the scene (rt_scene_num_instances); 0: a flat scene."""
         return lib().rt_scene_num_instances(self._h)
+
+    @property
+    def has_motion(self) -> bool:
+        """The scene has a moving object or a transformed sphere (rt_scene_has_motion)."""
+        return bool(lib().rt_scene_has_motion(self._h))
 
     @property
     def has_smooth(self) -> bool:
@@ -375,73 +414,82 @@ class Scene:
 
     # ------------------------------------------------------------------ radiance queries
     @staticmethod
-    def _radiance_flags(in_medium: bool, reorder: bool) -> int:
+    def _radiance_flags(in_medium: bool, reorder: bool, ray_time: bool = False) -> int:
         return ((_lib.RT_QUERY_IN_MEDIUM if in_medium else 0) |
-                (_lib.RT_QUERY_REORDER if reorder else 0))
+                (_lib.RT_QUERY_REORDER if reorder else 0) |
+                (_lib.RT_QUERY_RAY_TIME if ray_time else 0))
 
     def shade_rays(self, origins, directions, *, depth: Optional[int] = None,
-                   in_medium: bool = False, reorder: bool = False, stats: bool = False):
+                   in_medium: bool = False, reorder: bool = False, stats: bool = False,
+                   time=None):
         """Scene::trace_ray of each ray o + t d (rt_shade_rays): a RADIANCE_DTYPE array with the
         colour ``rgb`` a frame would hold for that ray and the first hit's ``t`` (+inf on a
         miss).  ``depth``: the reference's current_recursion_depth, None = the scene's
         MaxRecursionDepth; a miss returns the background only at that maximum.  ``in_medium``:
         every ray starts inside a dielectric (no local shading at its first hit).  With
-        ``stats`` returns (array, rt_stats of this call)."""
-        rays = pack_rays(origins, directions)
+        ``stats`` returns (array, rt_stats of this call).  ``time``: the rays' times (a scalar or
+        (n,)), which every ray of a ray's tree inherits (RT_QUERY_RAY_TIME)."""
+        rays = pack_rays(origins, directions, time=time)
         out = _aligned(len(rays), RADIANCE_DTYPE)
         st = _lib.rt_stats()
         check(lib().rt_shade_rays(self._h, rays.ctypes.data, len(rays),
                                   -1 if depth is None else int(depth), out.ctypes.data,
-                                  self._radiance_flags(in_medium, reorder), C.byref(st)))
+                                  self._radiance_flags(in_medium, reorder, time is not None),
+                                  C.byref(st)))
         return (out, st) if stats else out
 
     def shade_rays_device(self, rays_ptr: int, n: int, out_ptr: int, *,
                           depth: Optional[int] = None, in_medium: bool = False,
-                          reorder: bool = False, stream: int = 0) -> None:
+                          reorder: bool = False, stream: int = 0, ray_time: bool = False) -> None:
         """rt_shade_rays_device: n rt_ray records in device memory at ``rays_ptr`` to n
         rt_radiance records at ``out_ptr``, asynchronously on HIP stream ``stream``; the ray
         counts go to collect_stats()."""
         check(lib().rt_shade_rays_device(self._h, C.c_void_p(rays_ptr), n,
                                          -1 if depth is None else int(depth), C.c_void_p(out_ptr),
-                                         self._radiance_flags(in_medium, reorder),
+                                         self._radiance_flags(in_medium, reorder, ray_time),
                                          C.c_void_p(stream)))
 
     @staticmethod
-    def _lit_flags(in_medium: bool, reorder: bool, shared: bool, scene_lights: bool) -> int:
-        return (Scene._radiance_flags(in_medium, reorder) |
+    def _lit_flags(in_medium: bool, reorder: bool, shared: bool, scene_lights: bool,
+                   ray_time: bool = False) -> int:
+        return (Scene._radiance_flags(in_medium, reorder, ray_time) |
                 (_lib.RT_QUERY_LIGHTS_SHARED if shared else 0) |
                 (0 if scene_lights else _lib.RT_QUERY_NO_SCENE_LIGHTS))
 
     def shade_rays_lit(self, origins, directions, lights, *, shared: bool = False,
                        scene_lights: bool = True, depth: Optional[int] = None,
-                       in_medium: bool = False, reorder: bool = False, stats: bool = False):
+                       in_medium: bool = False, reorder: bool = False, stats: bool = False,
+                       time=None):
         """``shade_rays`` with each ray's own light samples (rt_shade_rays_lit): ``lights`` is a
         LIGHT_SAMPLE_DTYPE array of shape (n, k), row i lighting ray i's whole tree after the
         scene's point lights — or, with ``shared``, of shape (k,) for every ray.  A record with
         a non-finite ``position`` is no light; ``normal`` 0 0 0 is a point light, any other
         normal an emitter sample whose terms carry dot(-w_i, normal).  ``scene_lights=False``
         leaves the scene's own lights out."""
-        rays = pack_rays(origins, directions)
+        rays = pack_rays(origins, directions, time=time)
         lit, k = pack_lights(lights, len(rays), shared)
         out = _aligned(len(rays), RADIANCE_DTYPE)
         st = _lib.rt_stats()
         check(lib().rt_shade_rays_lit(self._h, rays.ctypes.data, len(rays),
                                       -1 if depth is None else int(depth), lit.ctypes.data, k,
                                       out.ctypes.data,
-                                      self._lit_flags(in_medium, reorder, shared, scene_lights),
+                                      self._lit_flags(in_medium, reorder, shared, scene_lights,
+                                                      time is not None),
                                       C.byref(st)))
         return (out, st) if stats else out
 
     def shade_rays_lit_device(self, rays_ptr: int, n: int, lights_ptr: int, k: int, out_ptr: int, *,
                               shared: bool = False, scene_lights: bool = True,
                               depth: Optional[int] = None, in_medium: bool = False,
-                              reorder: bool = False, stream: int = 0) -> None:
+                              reorder: bool = False, stream: int = 0,
+                              ray_time: bool = False) -> None:
         """rt_shade_rays_lit_device: n rt_ray records and their n x k (shared: k)
         rt_light_sample records in device memory, asynchronously on HIP stream ``stream``."""
         check(lib().rt_shade_rays_lit_device(
             self._h, C.c_void_p(rays_ptr), n, -1 if depth is None else int(depth),
             C.c_void_p(lights_ptr), int(k), C.c_void_p(out_ptr),
-            self._lit_flags(in_medium, reorder, shared, scene_lights), C.c_void_p(stream)))
+            self._lit_flags(in_medium, reorder, shared, scene_lights, ray_time),
+            C.c_void_p(stream)))
 
     def set_radiance_scratch_limit(self, nbytes: int) -> None:
         """Bytes of ray-tree frames one chunk of a recursing radiance query may hold (0: the
@@ -536,6 +584,66 @@ def host_instance_info(desc, instance_mesh, instance_material, instance_transfor
                                            box.ctypes.data_as(C.POINTER(C.c_float)),
                                            top.ctypes.data_as(C.POINTER(C.c_int))))
     return inverse, box, top
+
+
+def _motion_desc(desc, inst, instance_velocity, sphere_transform, sphere_velocity):
+    """An ``rt_motion_desc`` over the three optional arrays, and the arrays it points into."""
+    ni = inst.num_instances if inst is not None else 0
+    ns = desc.num_spheres
+    keep = []
+
+    def arr(a, count, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        if a.size != count:
+            raise ValueError(f"{what} must hold {count} values")
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(C.c_float))
+
+    mo = _lib.rt_motion_desc()
+    mo.struct_size = C.sizeof(_lib.rt_motion_desc)
+    mo.num_instances, mo.num_spheres = ni, ns
+    mo.instance_velocity = arr(instance_velocity, 3 * ni, "instance_velocity")
+    mo.sphere_transform = arr(sphere_transform, 16 * ns, "sphere_transform")
+    mo.sphere_velocity = arr(sphere_velocity, 3 * ns, "sphere_velocity")
+    return mo, keep
+
+
+def host_motion_info(desc, instance_mesh=None, instance_material=None, instance_transform=None,
+                     instance_velocity=None, sphere_transform=None, sphere_velocity=None):
+    """Host-only (rt_host_motion_info_desc): every instance's box, expanded by its velocity
+    (ni, 6), every sphere's inverse matrix (ns, 4, 4) and box (ns, 6), and the top-level DFS
+    position of every top-level object (instances, loose triangles, spheres)."""
+    inst = keep = None
+    if instance_mesh is not None:
+        inst, keep = _instance_desc(instance_mesh, instance_material, instance_transform)
+    mo, keep2 = _motion_desc(desc, inst, instance_velocity, sphere_transform, sphere_velocity)
+    ni, ns = mo.num_instances, mo.num_spheres
+    inst_box = np.zeros((ni, 6), np.float32)
+    inverse = np.zeros((ns, 4, 4), np.float32)
+    box = np.zeros((ns, 6), np.float32)
+    top = np.zeros(ni + desc.num_triangles + ns, np.int32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check(lib().rt_host_motion_info_desc(C.byref(desc), C.byref(inst) if inst else None,
+                                         C.byref(mo), fp(inst_box), fp(inverse), fp(box),
+                                         top.ctypes.data_as(C.POINTER(C.c_int))))
+    return inst_box, inverse, box, top
+
+
+def host_motion_xml(xml_path: str):
+    """Host-only (rt_host_motion_xml): what the motion loader read beside host_instances_xml's
+    arrays — (instance velocity (ni, 3), sphere transform (ns, 4, 4), sphere velocity (ns, 3))."""
+    path = str(xml_path).encode()
+    counts = (C.c_int * 2)()
+    check(lib().rt_host_motion_xml(path, None, None, None, 0, counts))
+    ni, ns = counts[0], counts[1]
+    vel = np.zeros((ni, 3), np.float32)
+    xf = np.zeros((ns, 4, 4), np.float32)
+    svel = np.zeros((ns, 3), np.float32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check(lib().rt_host_motion_xml(path, fp(vel), fp(xf), fp(svel), max(ni, ns), counts))
+    return vel, xf, svel
 
 
 def host_instances_xml(xml_path: str):

@@ -817,6 +817,102 @@ int rt_host_instance_info_desc(const rt_scene_desc* desc, const rt_instance_desc
                                float* inverse16 /*[16 n]*/, float* box6 /*[6 n]*/,
                                int* top_dfs /*[n]*/);
 
+/* ---- Motion blur: ray times, moving instances, transformed and moving spheres ------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_MOTION / rt_motion_version).
+ * HW3's motion blur: a ray carries a TIME, and an instance or sphere with a velocity is met
+ * through the inverse of Translation(time * velocity) * M, built per ray (HW3/include/Ray.h:18,
+ * Mesh.h:75-92, Sphere.h:113-154).  A sphere may also carry a transformation (Sphere.h:76-112, the
+ * static half of the same code).  A motion-blurred image is a film fed with rays that each carry
+ * a time in [0, 1) from the caller's generator; every sample is the reference's bit for bit.
+ *
+ *   time      tau, any finite float (the reference documents [-1, 1] and draws [0, 1)); 0 unless
+ *             the call has RT_QUERY_RAY_TIME, with which rt_ray::pad is the ray's time.  Every ray
+ *             of a ray tree has the time of the tree's first ray: the shadow rays of the scene's
+ *             lights and of the caller's light records, mirror, reflection and transmission rays
+ *             (HW3/src/Scene.cpp:153, 196, 226, 258, 294-304).
+ *   moving instance (velocity != 0; -0 == 0)  (1) the world ray against the instance box by the
+ *             node rule, as for a static instance; (2) delta = tau * velocity per component;
+ *             (3) A = T(delta) * M by Matrix4x4::operator*: every result[i][j] from 0 through
+ *             a[i][k] * r[k][j], k = 0..3, the products with 0 and 1 included; (4) the inverse of A
+ *             by Matrix4x4::invert_matrix; (5) the local ray A^-1.multiply(o),
+ *             A^-1.multiply(d, true), not normalised; (6) the mesh's closest hit for it;
+ *             (7) normal = (A^-1)^T.multiply(n, true).normalize(); (8) the instance's material.
+ *             A static instance (velocity == 0) is met as before.
+ *   boxes     an instance's box is apply_transform(mesh root box, M); a sphere's is center +-
+ *             radius, taken through apply_transform unless its matrix is exactly the identity.
+ *             With velocity != 0 the box (min, max) is then expanded by (min + v, max + v) and by
+ *             (min - v, max - v) (Mesh.h:104-110, Sphere.h:30-36; fmin / fmax folds).  The box does
+ *             not depend on tau: a ray whose time carries the object outside its box misses it at
+ *             the box, as in the reference.  The top-level tree is built over these boxes.
+ *   sphere    identity matrix and zero velocity: the HW2 rule, as ever.  Otherwise the sphere's
+ *             test runs on the local ray, taken through the host-computed inverse of M (zero
+ *             velocity) or through the per-ray inverse of T(tau v) * M; the normal is
+ *             (inverse)^T.multiply((o' + t d' - center).normalize(), true).normalize().  In the
+ *             top-level tree the leaf rule 0 < t < inf applies; a lone sphere reports its own
+ *             answer.  rt_ray_hit: object, leaf and material as a sphere's, pad -1.
+ *   departures  on a scene with motion a ray whose time is not finite is an INVALID ray (a miss,
+ *             not occluded, radiance (0, 0, 0, +inf); a fused film entry still bins its sample,
+ *             black).  A per-ray A with det == 0.0f misses that object (the reference exits).  A
+ *             local ray with a non-finite component, or with all three |d'_i| < 1e-6, misses the
+ *             object, as for instances.
+ *   frames    rt_render*, MSAA frames included, render a scene with motion at tau = 0 for every
+ *             ray (the reference seeds its time generator from the clock; nothing to reproduce).
+ *             A blurred frame is a film.
+ *   entries   as for instanced scenes.  RT_QUERY_RAY_TIME is accepted by rt_trace_rays*,
+ *             rt_occluded*, rt_shade_rays*, rt_shade_rays_lit*, rt_film_shade_rays* and
+ *             rt_film_shade_rays_lit*; on a scene without motion it has no effect and pad is not
+ *             read.  Results do not depend on n, on a ray's position or neighbours, on
+ *             RT_QUERY_REORDER or on the traversal mode.  Loose triangles take neither a
+ *             transformation nor a velocity.
+ *
+ * rt_scene_create_moving: a NULL or trivial motion descriptor (every velocity zero, every sphere
+ * matrix the identity or NULL) gives exactly rt_scene_create_instanced's scene.  The instance
+ * descriptor may be NULL or empty: the top level is then the loose triangles and spheres, and the
+ * description's meshes are unreachable bases.  RT_E_INVALID before any HIP call: a short
+ * struct_size, counts that disagree with the other two descriptors (a count may be 0 when its
+ * arrays are NULL), a non-finite velocity or matrix entry, a singular sphere matrix.  What
+ * rt_scene_create_instanced answers with RT_E_UNSUPPORTED stays RT_E_UNSUPPORTED. */
+#define CENG795_RT_HAS_MOTION 1
+int rt_motion_version(void); /* 1 */
+
+typedef struct rt_motion_desc {
+  size_t struct_size;              /* sizeof(rt_motion_desc)                           */
+  int num_instances;               /* = the instance descriptor's count, or 0          */
+  int num_spheres;                 /* = desc->num_spheres, or 0                        */
+  const float* instance_velocity;  /* fp32[3 ni], or NULL: all zero                    */
+  const float* sphere_transform;   /* fp32[16 ns] row-major object->world, or NULL: identity */
+  const float* sphere_velocity;    /* fp32[3 ns], or NULL: all zero                    */
+} rt_motion_desc;                  /* 40 B */
+int rt_scene_create_moving(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                           const rt_motion_desc* motion, int device, rt_scene** out);
+/* rt_scene_load_xml_instanced plus <MotionBlur>x y z</MotionBlur> on <Mesh>, <MeshInstance> and
+ * <Sphere> and <Transformations> on <Sphere> (composed as the per-object lists are).  A <Mesh>'s
+ * velocity belongs to its instance k; a <MeshInstance> takes its own <MotionBlur>, not its
+ * base's (HW3/src/Scene.cpp:666-760).  <Transformations> on a <Triangle> and plyFile stay
+ * RT_E_UNSUPPORTED.  The other loaders read such files exactly as before. */
+int rt_scene_load_xml_moving(const char* xml_path, int device, rt_scene** out);
+int rt_scene_has_motion(const rt_scene* scene); /* 1: the motion kernels run on it */
+enum { RT_QUERY_RAY_TIME = 32 };   /* rt_ray.pad is the ray's time */
+/* Host-only, touch no HIP API.  rt_host_motion_info_desc: every instance's box (expanded), every
+ * sphere's inverse matrix (row-major 4x4) and box, and the top-level DFS position of every
+ * top-level object (instances, loose triangles, spheres); any output may be NULL.
+ * rt_host_motion_xml: what rt_scene_load_xml_moving read — per instance its velocity, per sphere
+ * its composed matrix and velocity, the first min(n, capacity) of each; any output may be NULL;
+ * counts2 (nullable) = the numbers of instances and spheres.  Returns RT_OK. */
+int rt_host_motion_info_desc(const rt_scene_desc* desc, const rt_instance_desc* instances,
+                             const rt_motion_desc* motion, float* inst_box6 /*[6 ni]*/,
+                             float* sphere_inverse16 /*[16 ns]*/, float* sphere_box6 /*[6 ns]*/,
+                             int* top_dfs /*[ni + triangles + ns]*/);
+int rt_host_motion_xml(const char* xml_path, float* instance_velocity3, float* sphere_transform16,
+                       float* sphere_velocity3, int capacity, int* counts2);
+/* Debug: the device's own per-ray T(tau v) * M and inversion for top-level object `top_object`
+ * (an instance, or a sphere counted after the instances and loose triangles) of a scene with
+ * motion, at n host times: out12[12 i ..] = rows 0..2 of the inverse the walk uses at times[i], or
+ * 12 NaNs where det == 0.  RT_E_INVALID for an object that does not move. */
+int rt_debug_motion_inverse(rt_scene* scene, int top_object, const float* times, long long n,
+                            float* out12);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 

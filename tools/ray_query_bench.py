@@ -126,6 +126,10 @@ def main(argv=None) -> int:
     p.add_argument("--instances", type=int, default=0, metavar="K",
                    help="a generated mesh (--n grid) placed K times as instances against the same "
                         "geometry baked to world space in a flat scene: closest hit, occlusion and radiance")
+    p.add_argument("--moving", action="store_true",
+                   help="with --instances K: a third scene, the instances each with a velocity "
+                        "(rt_scene_create_moving), traced with every ray at time 0 — the static "
+                        "scene's geometry through the motion kernels' per-ray inverses")
     p.add_argument("--dry-run", action="store_true",
                    help="with --radiance --lights or --smooth: write the case list and stop (no GPU)")
     p.add_argument("--check", action="store_true",
@@ -135,8 +139,10 @@ def main(argv=None) -> int:
         p.error("--lights goes with --radiance")
     if a.lights and a.smooth:
         p.error("--lights and --smooth are separate runs")
-    if a.dry_run and not (a.lights or a.smooth):
-        p.error("--dry-run goes with --radiance --lights or with --smooth")
+    if a.moving and not a.instances:
+        p.error("--moving goes with --instances K")
+    if a.dry_run and not (a.lights or a.smooth or (a.instances and a.moving)):
+        p.error("--dry-run goes with --radiance --lights, with --smooth or with --instances K --moving")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles",
                              "smooth_query.json" if a.smooth else
@@ -373,6 +379,15 @@ def instances_main(a) -> int:
     points on it, shuffled) through the instanced scene's two-level walk and through a flat scene
     of the same geometry baked to world space (fp32 vertices: its bits differ, its hits agree up
     to rounding).  Device bytes: what creating each scene took from the device's free memory."""
+    k, g = a.instances, a.n
+    names = ["instanced", "baked"] + (["moving"] if a.moving else [])
+    cases = [(sc, kind, flag) for kind in ("closest", "occluded", "radiance")
+             for flag in (False, True) for sc in names]
+    if a.dry_run:  # the case list, on a machine without a GPU
+        print(f"instances={k} grid={g} moving={int(a.moving)} rays={a.width * a.height}")
+        for sc, kind, flag in cases:
+            print(f"{sc}/{kind}/{'reorder' if flag else 'plain'}")
+        return 0
     import ctypes as C
     import torch
     import ceng795_amd
@@ -380,7 +395,6 @@ def instances_main(a) -> int:
     if not torch.cuda.is_available():
         raise SystemExit("ray_query_bench: no GPU")
     f = np.float32
-    k, g = a.instances, a.n
     rng = np.random.default_rng(a.seed)
     xs = np.linspace(-1, 1, g, dtype=f)
     vx, vy = np.meshgrid(xs, xs)
@@ -451,22 +465,32 @@ def instances_main(a) -> int:
     rad = torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     scenes = {"instanced": inst, "baked": flat}
-    cases = [(sc, kind, flag) for kind in ("closest", "occluded", "radiance")
-             for flag in (False, True) for sc in scenes]
+    moving_bytes = 0
+    if a.moving:  # every instance with a velocity; the rays' times (pad) are 0
+        vel = rng.uniform(0.2, 0.6, size=(k, 3)).astype(f)
+        scenes["moving"], moving_bytes = created(lambda: ceng795_amd.Scene.create(
+            d_inst, instance_mesh=np.zeros(k, np.int32), instance_material=np.zeros(k, np.int32),
+            instance_transform=xf, instance_velocity=vel, device=0))
+        assert scenes["moving"].has_motion
 
     def run(sc, kind, flag):
+        kw = dict(reorder=flag, stream=stream, ray_time=sc == "moving")
         if kind == "closest":
-            scenes[sc].trace_rays_device(rays.data_ptr(), n, hits.data_ptr(), reorder=flag, stream=stream)
+            scenes[sc].trace_rays_device(rays.data_ptr(), n, hits.data_ptr(), **kw)
         elif kind == "radiance":  # one point light: a shadow ray per hit
-            scenes[sc].shade_rays_device(rays.data_ptr(), n, rad.data_ptr(), reorder=flag, stream=stream)
+            scenes[sc].shade_rays_device(rays.data_ptr(), n, rad.data_ptr(), **kw)
         else:
-            scenes[sc].occluded_device(rays.data_ptr(), n, occ.data_ptr(), reorder=flag, stream=stream)
+            scenes[sc].occluded_device(rays.data_ptr(), n, occ.data_ptr(), **kw)
 
     got = {}
     for sc in scenes:
         run(sc, "closest", False)
         torch.cuda.synchronize()
         got[sc] = hits.cpu().numpy().view(ceng795_amd.HIT_DTYPE).copy()
+    if a.moving:  # at time 0 the moving scene's hits are the static scene's (the boxes are larger)
+        same_t = got["moving"]["t"].view(np.uint32) == got["instanced"]["t"].view(np.uint32)
+        same_object = got["moving"]["object"] == got["instanced"]["object"]
+        moving_same = float((same_t & same_object).mean())
     hit_i, hit_b = got["instanced"]["object"] >= 0, got["baked"]["object"] >= 0
     both = hit_i & hit_b
     # the baked scene numbers instance c's faces from c * faces on
@@ -498,6 +522,9 @@ def instances_main(a) -> int:
               "timing": "device events around each call; cases alternated within every round",
               "device_bytes": {"instanced": inst_bytes, "baked": flat_bytes},
               "agreement": agree, "cases": {}}
+    if a.moving:
+        result["device_bytes"]["moving"] = moving_bytes
+        result["agreement"]["moving_equals_instanced_at_time_0"] = moving_same
     for (sc, kind, flag), ms in times.items():
         qq = quartiles(ms)
         qq["mrays_per_s"] = n / qq["ms_median"] / 1e3
@@ -506,6 +533,12 @@ def instances_main(a) -> int:
     result["ratios"] = {f"instanced_over_baked/{kind}/{fl}":
                         c[f"instanced/{kind}/{fl}"]["ms_median"] / c[f"baked/{kind}/{fl}"]["ms_median"]
                         for kind in ("closest", "occluded", "radiance") for fl in ("plain", "reorder")}
+    if a.moving:
+        result["ratios"].update({
+            f"moving_over_instanced/{kind}/{fl}":
+            c[f"moving/{kind}/{fl}"]["ms_median"] / c[f"instanced/{kind}/{fl}"]["ms_median"]
+            for kind in ("closest", "occluded", "radiance") for fl in ("plain", "reorder")})
+        scenes["moving"].close()
     inst.close()
     flat.close()
     write_result(a.out, result)
