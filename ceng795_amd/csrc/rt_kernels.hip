@@ -132,12 +132,10 @@ __device__ __forceinline__ bool lane_in(uint64_t m) { return __builtin_amdgcn_in
 // Lane masks of one fp32 compare, straight from the v_cmp (ballot of a combined boolean makes
 // the compiler round-trip it through a VGPR: v_cndmask + v_cmp per mask).  LLVM FCmp
 // predicates; ordered, so NaN gives false as the C++ operators do.
-enum : int { kFcmpOGT = 2, kFcmpOGE = 3, kFcmpOLT = 4, kFcmpULT = 12 };
+enum : int { kFcmpOGT = 2, kFcmpOGE = 3, kFcmpOLT = 4 };
 __device__ __forceinline__ uint64_t lanes_gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOGT); }
 __device__ __forceinline__ uint64_t lanes_ge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOGE); }
 __device__ __forceinline__ uint64_t lanes_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOLT); }
-// !(a >= b): true for a NaN operand too
-__device__ __forceinline__ uint64_t lanes_nge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpULT); }
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 // v_writelane_b32 (the LLVM intrinsic; clang has no builtin for it): `old` with lane `lane`
 // (wave-uniform) replaced by the wave-uniform `v`.  Ignores EXEC.
@@ -1053,8 +1051,29 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
       Ahi[x] = sk ? RT_INF : Ahi[x];
     }
   }
+  // The lane mask inside the slab test: a lane outside `m` gets the exit plane -inf and a finite
+  // scale on axis 0, once per visit (after the skip selects), so every slot's compare is false
+  // for it and the compare's own mask is the set of entering lanes of `m` — no s_andn2 with the
+  // mask and no 64-bit zero test per slot.  The same set: a lane in `m` keeps its operands, and
+  // the ordered >= equals !(unordered <); outside `m`, f3[0] = fma(h, 1, -inf) = -inf for the
+  // finite fp16 h (the lane's own S[0] may be 1/0 = inf, and h * inf with h = 0 a NaN: hence the
+  // scale), v_min3 ignores a NaN on the other axes, so tf = -inf, and max(tn, 0) >= 0 whatever
+  // tn is (fmaxf drops a NaN tn): -inf >= it is false.  An invalid slot's NaN planes still fail
+  // in every lane.
+  {
+    const bool in = lane_in(m);
+    S[0] = in ? S[0] : 1.0f;
+    Ahi[0] = in ? Ahi[0] : -RT_INF;
+  }
   int nxt = -1;
   uint64_t nm = 0;
+  // The inner-slot mask once more, opaque to the compiler: a slot's leafy and inner paths are two
+  // if-thens on two bits it cannot relate (s_bitcmp0 + s_cbranch_scc each).  Written as one
+  // if / else — or with `continue` out of the leafy branch — the structurizer turns the uniform
+  // two-way branch into a boolean flag in an SGPR pair, set on both sides and tested again at the
+  // join (5 scalar instructions per leafy hit, and a copy of the queue count); DESIGN.md §4.3.
+  unsigned inner_bits = inner;
+  asm("" : "+s"(inner_bits));
 #pragma unroll
   for (int c = 0; c < kWideSlots; c++) {
     // the valid slots come first (check_accel): stop at the first invalid one (its NaN planes
@@ -1073,30 +1092,33 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
     }
     const float tn = __builtin_fmaxf(__builtin_fmaxf(n3[0], n3[1]), n3[2]);
     const float tf = __builtin_fminf(__builtin_fminf(f3[0], f3[1]), f3[2]);
-    // out: !(tf >= max(tn, 0)) — one compare (tn and tf are never NaN on a valid slot: finite
-    // fp16 planes, finite scales, skipped axes at -inf / +inf)
+    // in: tf >= max(tn, 0) — one compare (in a lane of `m`, tn and tf are never NaN on a valid
+    // slot: finite fp16 planes, finite scales, skipped axes at -inf / +inf; a lane outside `m`
+    // fails it, see above)
     // (m holds no lane outside `alive` wherever a visit starts — occluded() folds it in after
     // every flush and pop_live at every pop — so the slots do not mask with it again)
-    const uint64_t hm = m & ~lanes_nge(tf, __builtin_fmaxf(tn, 0.0f));
-    if (!hm) continue;
-    DIAG(dg.ev[kPhSlotHits]++);
-    if (kinds & (kSlotLeafy << c)) {
-      DIAG(dg.ev[kPhLeafyHits]++);
-      const int leaf = leaf_base + (int)((offs >> (4 * c)) & 15u);
-      [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
-      DIAG(dg.ev[kPhPairHits] += pair);
-      // (the shadow kernel keeps the exec-mask pushes: junk writes cost it VGPR spills)
-      batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
-      DIAG(dg.leaves += 1 + pair; dg.leaf_lanes += (1 + pair) * __builtin_popcountll(hm));
-      continue;
-    }
-    const int ch = (inner_base + 2 * __builtin_popcount(inner & ((1u << c) - 1u))) | kWideTag;
-    DIAG(dg.ev[kPhInnerHits]++);
-    if (nxt < 0) {
-      nxt = ch;
-      nm = hm;
-    } else {
-      st.push(ch, hm);
+    const uint64_t hm = lanes_ge(tf, __builtin_fmaxf(tn, 0.0f));
+    if (hm) {
+      DIAG(dg.ev[kPhSlotHits]++);
+      if (kinds & (kSlotLeafy << c)) {
+        DIAG(dg.ev[kPhLeafyHits]++);
+        const int leaf = leaf_base + (int)((offs >> (4 * c)) & 15u);
+        [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
+        DIAG(dg.ev[kPhPairHits] += pair);
+        // (the shadow kernel keeps the exec-mask pushes: junk writes cost it VGPR spills)
+        batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
+        DIAG(dg.leaves += 1 + pair; dg.leaf_lanes += (1 + pair) * __builtin_popcountll(hm));
+      }
+      if (inner_bits & (1u << c)) {  // (a valid slot is leafy or inner)
+        const int ch = (inner_base + 2 * __builtin_popcount(inner & ((1u << c) - 1u))) | kWideTag;
+        DIAG(dg.ev[kPhInnerHits]++);
+        if (nxt < 0) {
+          nxt = ch;
+          nm = hm;
+        } else {
+          st.push(ch, hm);
+        }
+      }
     }
   }
   if (nxt >= 0) {
