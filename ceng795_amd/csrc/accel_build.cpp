@@ -236,17 +236,18 @@ struct Slot {
   Box box;  // exact union of the guard boxes below (a treelet's guard box)
 };
 
-// Writes one wide node's header and slot boxes: origin = the inflated union's lower corner
+// Writes one wide node's header and slot boxes (at[c]: the slot at position c, null = invalid,
+// NaN planes): origin = the inflated union's lower corner
 // (rounded down to fp32), per-axis power-of-two scale with the largest offset <= 32768, each
 // plane rounded outward to fp16 after the margin is applied.  Every step rounds outward
 // (add_down / add_up, float_down, half_dir), so the decoded box o + h 2^k contains the guard
 // boxes with the margin in exact arithmetic, which is what check_accel decides.
-void encode_node(DevNode8& W, const Slot* sl, int n, const double* margin) {
+void encode_node(DevNode8& W, const Slot* const at[kWideSlots], const double* margin) {
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int k = 0; k < n; k++)
-    for (int a = 0; a < 3; a++) {
-      lo[a] = std::min(lo[a], add_down((double)sl[k].box.lo[a], -margin[a]));
-      hi[a] = std::max(hi[a], add_up((double)sl[k].box.hi[a], margin[a]));
+  for (int c = 0; c < kWideSlots; c++)
+    for (int a = 0; at[c] && a < 3; a++) {
+      lo[a] = std::min(lo[a], add_down((double)at[c]->box.lo[a], -margin[a]));
+      hi[a] = std::max(hi[a], add_up((double)at[c]->box.hi[a], margin[a]));
     }
   W.scale = 0;
   int ka[3];
@@ -262,13 +263,13 @@ void encode_node(DevNode8& W, const Slot* sl, int n, const double* margin) {
   }
   for (int c = 0; c < kWideSlots; c++)
     for (int a = 0; a < 3; a++) {
-      if (c >= n) {
+      if (!at[c]) {
         W.box[c][a] = (uint32_t)kHalfNaN | ((uint32_t)kHalfNaN << 16);
         continue;
       }
       const double o = (double)W.origin[a];
-      const double pl = add_down(add_down((double)sl[c].box.lo[a], -margin[a]), -o);
-      const double ph = add_up(add_up((double)sl[c].box.hi[a], margin[a]), -o);
+      const double pl = add_down(add_down((double)at[c]->box.lo[a], -margin[a]), -o);
+      const double ph = add_up(add_up((double)at[c]->box.hi[a], margin[a]), -o);
       const uint16_t l = half_dir(std::ldexp(pl, -ka[a]), false);
       const uint16_t h = half_dir(std::ldexp(ph, -ka[a]), true);
       W.box[c][a] = (uint32_t)l | ((uint32_t)h << 16);
@@ -375,7 +376,7 @@ struct WideCollapse {
 
 // Collapses the binary SAH tree into 8-wide nodes appended to s.nodes (WideCollapse), with
 // every node's inner children allocated contiguously and its treelets' leaves appended to
-// s.leaves in slot order.  Returns the tagged root; s.accel_depth receives the
+// s.leaves in visiting order (slot 7 first).  Returns the tagged root; s.accel_depth receives the
 // traversal-stack bound.
 int collapse_wide(HostScene& s, const SahBuilder& B, int broot, const std::vector<int>& holder,
                   const std::vector<float>& ref_box) {
@@ -395,28 +396,34 @@ int collapse_wide(HostScene& s, const SahBuilder& B, int broot, const std::vecto
     todo.pop_back();
     slots.clear();
     W8.emit(j.bnode, W8.tk[j.bnode], slots);
-    const int n = (int)slots.size();
-    const Slot* sl = slots.data();
+    // kind-sorted positions (rt_internal.h DevNode8): the inner slots from 0 upwards and the
+    // leafy slots from 7 downwards, each kind in emission order, the invalid slots between them
+    const Slot* at[kWideSlots] = {};
+    int inner = 0, leafy = 0;
+    for (const Slot& sl : slots)
+      if (sl.ref >= 0)
+        at[inner++] = &sl;
+      else
+        at[kWideSlots - 1 - leafy++] = &sl;
     DevNode8 W;
     std::memset(&W, 0, sizeof W);
-    encode_node(W, sl, n, s.cull_margin);
-    int inner = 0;
-    for (int k = 0; k < n; k++) inner += sl[k].ref >= 0;
+    encode_node(W, at, s.cull_margin);
     W.inner_base = inner ? (int)s.nodes.size() : 0;
     s.nodes.resize(s.nodes.size() + 2 * (size_t)inner);
     W.leaf_base = (int)s.leaves.size();
+    W.kinds = (int32_t)((uint32_t)inner << kSlotInnerCountShift |
+                        (uint32_t)leafy << kSlotLeafyCountShift);
     std::vector<int> mine;
-    int off = 0, r = 0;
-    for (int k = 0; k < n; k++) {
-      W.kinds |= kSlotValid << k;
-      if (sl[k].ref >= 0) {
-        mine.push_back(W.inner_base + 2 * r++);
-        continue;
-      }
-      const Item& it = items[~sl[k].ref];
-      W.kinds |= kSlotLeafy << k;
-      if (it.pair) W.kinds |= kSlotPair << k;
-      W.offs |= (uint32_t)off << (4 * k);  // <= 14: at most 7 pairs before the last slot
+    for (int c = 0; c < inner; c++) {
+      W.kinds |= kSlotValid << c;
+      mine.push_back(W.inner_base + 2 * c);
+    }
+    int off = 0;
+    for (int c = kWideSlots - 1; c >= kWideSlots - leafy; c--) {
+      const Item& it = items[~at[c]->ref];
+      W.kinds |= (kSlotValid | kSlotLeafy) << c;
+      if (it.pair) W.kinds |= kSlotPair << c;
+      W.offs |= (uint32_t)off << (4 * c);  // <= 14: at most 7 pairs before the last slot
       for (int q = 0; q < (it.pair ? 2 : 1); q++) {
         const int l = it.leaf + q;
         const DevPrim& p = s.prims[l];
@@ -434,10 +441,8 @@ int collapse_wide(HostScene& s, const SahBuilder& B, int broot, const std::vecto
     std::memcpy(&s.nodes[j.wide], &W, sizeof W);
     order.push_back(j.wide);
     kids.push_back(mine);
-    r = 0;
     std::vector<Job> next;
-    for (int k = 0; k < n; k++)
-      if (sl[k].ref >= 0) next.push_back({sl[k].ref, mine[r++]});
+    for (int c = 0; c < inner; c++) next.push_back({at[c]->ref, mine[c]});
     for (auto it = next.rbegin(); it != next.rend(); ++it) todo.push_back(*it);
   }
   // stack bound, children before parents: a visit keeps one entered inner slot and pushes the
@@ -578,6 +583,31 @@ void build_accel(HostScene& s, int K) {
   add_octant_copies(s, nref, nw);
 }
 
+// The slot order the kernels' two runs rely on (rt_internal.h DevNode8): "" when `W` keeps it,
+// else the broken rule.
+std::string wide_slot_order_error(const DevNode8& W) {
+  const unsigned valid = (unsigned)W.kinds & 0xffu, leafy = (unsigned)W.kinds >> 8 & 0xffu;
+  const unsigned pair = (unsigned)W.kinds >> 16 & 0xffu, inner = valid & ~leafy;
+  if (leafy & ~valid) return "leafy flag on an invalid slot";
+  if (pair & ~leafy) return "pair flag on a slot that is not leafy";
+  const int ni = __builtin_popcount(inner), nl = __builtin_popcount(leafy);
+  // (the top byte: the inner count in its low four bits, the leafy count in its high four)
+  if ((unsigned)W.kinds >> kSlotInnerCountShift != ((unsigned)ni | (unsigned)nl << 4))
+    return "slot counts differ from the slot bits";
+  // inner = 2^ni - 1 and leafy = the top nl bits (valid = inner | leafy, so nothing valid lies
+  // between the two runs)
+  if (inner & (inner + 1u)) {
+    const unsigned below_top = (1u << (31 - __builtin_clz(inner))) - 1u;
+    return leafy & below_top ? "leafy slot below an inner one"
+                             : "inner slots not contiguous from slot 0";
+  }
+  if (leafy != (0xffu & ~(0xffu >> nl))) return "leafy slots not contiguous down from slot 7";
+  for (int c = 0; c < kWideSlots; c++)
+    if (!(valid >> c & 1) && W.box[c][0] != (0x7e00u | 0x7e000000u))
+      return "invalid slot without NaN planes";
+  return "";
+}
+
 // Structural invariants of the culling tree the kernels' exactness argument relies on
 // (DESIGN.md §4.2).  Returns "" when they hold, else a description of the first violation.
 std::string check_accel(const HostScene& s, int K, long long stats[4]) {
@@ -633,20 +663,16 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
     nodes++;
     order.push_back(idx);
     stats[2] = std::max<long long>(stats[2], f.depth);
-    int valid = 0, r = 0;
-    const unsigned vbits = (unsigned)W.kinds & 0xffu;
-    if (vbits & (vbits + 1)) return "valid slots not first";  // the kernel stops at the first invalid
+    int valid = 0;
+    const std::string order_err = wide_slot_order_error(W);  // the kernel's two runs rely on it
+    if (!order_err.empty()) return order_err;
     for (int c = 0; c < kWideSlots; c++) {
-      if (!(W.kinds & (kSlotValid << c))) {
-        if (W.box[c][0] != (0x7e00u | 0x7e000000u)) return "invalid slot without NaN planes";
-        continue;
-      }
+      if (!(W.kinds & (kSlotValid << c))) continue;
       valid++;
       double lo[3], hi[3];
       decode_slot(W, c, lo, hi);
       if (!(W.kinds & (kSlotLeafy << c))) {
-        if (W.kinds & (kSlotPair << c)) return "pair flag on an inner slot";
-        const int child = W.inner_base + 2 * r++;
+        const int child = W.inner_base + 2 * c;
         todo.push_back({child | kWideTag, f.depth + 1});
         continue;  // containment checked bottom-up below
       }
@@ -688,7 +714,6 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
     DevNode8 W;
     std::memcpy(&W, &s.nodes[*it], sizeof W);
     double nlo[3] = {INFINITY, INFINITY, INFINITY}, nhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int r = 0;
     for (int c = 0; c < kWideSlots; c++) {
       if (!(W.kinds & (kSlotValid << c))) continue;
       double lo[3], hi[3];
@@ -699,7 +724,7 @@ std::string check_accel(const HostScene& s, int K, long long stats[4]) {
         const float g[6] = {L.g0, L.g1, L.g2, L.g3, L.g4, L.g5};
         for (int a = 0; a < 3; a++) glo[a] = g[a], ghi[a] = g[a + 3];
       } else {
-        const size_t ci = (size_t)(W.inner_base + 2 * r++) * 3;
+        const size_t ci = (size_t)(W.inner_base + 2 * c) * 3;
         for (int a = 0; a < 3; a++) {
           glo[a] = ulo[ci + a];
           ghi[a] = uhi[ci + a];
@@ -757,13 +782,29 @@ void accel_slot_histogram(const HostScene& s, long long hist[kWideSlots + 1]) {
     todo.pop_back();
     DevNode8 W;
     std::memcpy(&W, &s.nodes[idx], sizeof W);
-    int valid = 0, r = 0;
+    int valid = 0;
     for (int c = 0; c < kWideSlots; c++) {
       if (!(W.kinds & (kSlotValid << c))) continue;
       valid++;
-      if (!(W.kinds & (kSlotLeafy << c))) todo.push_back(W.inner_base + 2 * r++);
+      if (!(W.kinds & (kSlotLeafy << c))) todo.push_back(W.inner_base + 2 * c);
     }
     hist[valid]++;
+  }
+}
+
+void accel_kind_histogram(const HostScene& s, long long hist[(kWideSlots + 1) * (kWideSlots + 1)]) {
+  for (int i = 0; i < (kWideSlots + 1) * (kWideSlots + 1); i++) hist[i] = 0;
+  if (s.accel_root < 0) return;
+  std::vector<int> todo{s.accel_root & ~kWideTag};
+  while (!todo.empty()) {
+    const int idx = todo.back();
+    todo.pop_back();
+    DevNode8 W;
+    std::memcpy(&W, &s.nodes[idx], sizeof W);
+    const unsigned leafy = (unsigned)W.kinds >> 8 & 0xffu, inner = (unsigned)W.kinds & ~leafy & 0xffu;
+    for (int c = 0; c < kWideSlots; c++)
+      if (inner >> c & 1) todo.push_back(W.inner_base + 2 * c);
+    hist[__builtin_popcount(inner) * (kWideSlots + 1) + __builtin_popcount(leafy)]++;
   }
 }
 

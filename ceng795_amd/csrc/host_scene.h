@@ -82,6 +82,11 @@ std::string accel_slots_error(size_t ref_slots, size_t wide_slots);
 std::string check_accel(const HostScene& s, int K, long long stats[4]);
 // hist[v] = culling nodes with v valid slots (a tree that passed check_accel).
 void accel_slot_histogram(const HostScene& s, long long hist[kWideSlots + 1]);
+// hist[9 * i + l] = culling nodes with i inner and l leafy slots (a tree that passed check_accel).
+void accel_kind_histogram(const HostScene& s, long long hist[(kWideSlots + 1) * (kWideSlots + 1)]);
+// The slot order of one wide node (rt_internal.h DevNode8), part of check_accel: "" or the
+// broken rule.
+std::string wide_slot_order_error(const DevNode8& W);
 
 // Builds `out` from `desc`; throws std::invalid_argument on a bad description.
 void build_host_scene(const rt_scene_desc& desc, HostScene& out);

@@ -2208,6 +2208,36 @@ int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long l
   });
 }
 
+int rt_host_accel_kind_hist_xml(const char* xml_path, int treelet_leaves, long long* hist81) {
+  if (!xml_path || !hist81)
+    return set_error(RT_E_INVALID, "rt_host_accel_kind_hist_xml: NULL argument");
+  return guarded([&] {
+    XmlSceneStorage st;
+    rt_scene_desc d;
+    load_scene_xml(xml_path, st, d);
+    HostScene h;
+    build_host_scene(d, h);
+    build_accel(h, treelet_leaves);
+    long long stats[4];
+    const std::string err = check_accel(h, treelet_leaves, stats);
+    if (!err.empty()) throw std::invalid_argument("culling tree: " + err);
+    accel_kind_histogram(h, hist81);
+    return RT_OK;
+  });
+}
+
+int rt_host_check_wide_node(const void* node, unsigned long long bytes) {
+  if (!node || bytes != sizeof(DevNode8))
+    return set_error(RT_E_INVALID, "rt_host_check_wide_node: NULL node or not 128 bytes");
+  return guarded([&] {
+    DevNode8 W;
+    std::memcpy(&W, node, sizeof W);
+    const std::string err = wide_slot_order_error(W);
+    if (!err.empty()) throw std::invalid_argument("wide node: " + err);
+    return RT_OK;
+  });
+}
+
 int rt_host_accel_slots_check(long long ref_slots, long long wide_slots) {
   if (ref_slots < 0 || wide_slots < 0)
     return set_error(RT_E_INVALID, "rt_host_accel_slots_check: bad argument");

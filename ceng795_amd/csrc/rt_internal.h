@@ -90,7 +90,10 @@ static_assert(sizeof(DevNode) == 64, "node must be one 64-byte scalar load");
 // `nodes`, referred to as (index of the first slot) | kWideTag.  Slot c is valid when bit c of
 // `kinds` is set; it is then either LEAFY (bit 8 + c: one treelet = a lone leaf, or with bit
 // 16 + c a leaf pair; its leaves are DevLeaf records leaf_base + (offs >> 4c & 15) and the next
-// one) or INNER (a child node: inner_base + 2 * (number of inner slots before c)).  Every slot
+// one) or INNER (a child node: inner_base + 2c).  The slots are sorted by kind: the inner slots
+// lie at 0, 1, ... and the leafy slots at 7, 6, ..., the invalid ones between them, so a visit
+// runs up the inner slots and down the leafy ones and never asks a slot's kind (visit_wide);
+// the top byte of `kinds` holds the two counts.  Every slot
 // carries a CONSERVATIVE box in fp16, relative to `origin` and scaled by 2^k per axis:
 //   plane = origin[a] + h * 2^(scale byte a, signed)
 // rounded outward and inflated by the scene's culling margin (HostScene::cull_margin), so a
@@ -114,12 +117,13 @@ constexpr int kOctantCopies = 8;
 constexpr size_t kMaxNodeSlots = size_t(1) << 26;
 constexpr int kWideSlots = 8;
 enum : int32_t { kSlotValid = 1, kSlotLeafy = 1 << 8, kSlotPair = 1 << 16 };
+constexpr int kSlotInnerCountShift = 24, kSlotLeafyCountShift = 28;  // counts 0..8, 4 bits each
 struct alignas(16) DevNode8 {
   float origin[3];
   uint32_t scale;      // byte a: k_a as a signed byte
-  int32_t inner_base;  // DevNode index of the first inner child (children contiguous, 2 slots each)
-  int32_t leaf_base;   // DevLeaf index of the first leafy slot's first leaf
-  int32_t kinds;       // kSlotValid << c | kSlotLeafy << c | kSlotPair << c
+  int32_t inner_base;  // DevNode index of slot 0's child (children contiguous, 2 slots each)
+  int32_t leaf_base;   // DevLeaf index of the node's first leaf (slot 7's, the first visited)
+  int32_t kinds;       // kSlotValid << c | kSlotLeafy << c | kSlotPair << c | the two counts
   uint32_t offs;       // 4 bits per slot: its first leaf's offset from leaf_base (leafy slots)
   uint32_t box[kWideSlots][3];  // per slot and axis: lo fp16 (bits 0-15), hi fp16 (16-31)
 };

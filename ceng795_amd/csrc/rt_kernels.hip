@@ -1004,8 +1004,9 @@ __device__ __forceinline__ float half_hi(int w) {
 // conservative box (plane t = fma(h, 2^k / d, (origin - o) / d), the entry plane moved earlier
 // and the exit plane later by the ray's own margin 2^-18 |o| / |d| — DESIGN.md §4.2: with the
 // host's margin the test never culls a treelet the reference would enter, so no decision band
-// is needed); the valid slots come first and the visit stops at the first invalid one (whose
-// NaN planes would fail the test anyway).  A leafy slot's leaves go to the leaf queue (the exact
+// is needed); the slots lie sorted by kind, the inner ones from slot 0 upwards and the leafy ones
+// from slot 7 downwards, and the visit runs along each kind until it ends (an invalid slot's NaN
+// planes would fail the test anyway).  A leafy slot's leaves go to the leaf queue (the exact
 // guard decision is taken there); of the entered inner slots the first becomes `node` and the
 // others are pushed.  `alive`: lanes still searching.  Returns false when the walk is over.
 // (Round 5: shadow rays used to enter the nearest slot by the first entering lane's entry
@@ -1067,24 +1068,13 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
   }
   int nxt = -1;
   uint64_t nm = 0;
-  // The inner-slot mask once more, opaque to the compiler: a slot's leafy and inner paths are two
-  // if-thens on two bits it cannot relate (s_bitcmp0 + s_cbranch_scc each).  Written as one
-  // if / else — or with `continue` out of the leafy branch — the structurizer turns the uniform
-  // two-way branch into a boolean flag in an SGPR pair, set on both sides and tested again at the
-  // join (5 scalar instructions per leafy hit, and a copy of the queue count); DESIGN.md §4.3.
-  unsigned inner_bits = inner;
-  asm("" : "+s"(inner_bits));
-#pragma unroll
-  for (int c = 0; c < kWideSlots; c++) {
-    // the valid slots come first (check_accel): stop at the first invalid one (its NaN planes
-    // would fail the test anyway)
-    if (!(kinds & (kSlotValid << c))) break;
-    DIAG(dg.ev[kPhSlotsTested]++);
+  // One slot's slab test on its three plane words: the lanes of `m` that enter the slot.
+  auto slot_lanes = [&](const int (&w3)[3]) -> uint64_t {
     float n3[3], f3[3];
 #pragma unroll
     for (int x = 0; x < 3; x++) {
       // this lane's entry plane into the low half (COHERENT: the copy holds it there)
-      int w = RT_NODE_WORD(8 + 3 * c + x);
+      int w = w3[x];
       if (!COHERENT)
         w = (int)__builtin_amdgcn_alignbit((unsigned)w, (unsigned)w, (unsigned)sh[x]);
       n3[x] = __builtin_fmaf(half_lo(w), S[x], Alo[x]);
@@ -1097,28 +1087,47 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
     // fails it, see above)
     // (m holds no lane outside `alive` wherever a visit starts — occluded() folds it in after
     // every flush and pop_live at every pop — so the slots do not mask with it again)
-    const uint64_t hm = lanes_ge(tf, __builtin_fmaxf(tn, 0.0f));
+    return lanes_ge(tf, __builtin_fmaxf(tn, 0.0f));
+  };
+  // The slots lie sorted by kind (check_accel): the inner slots at 0, 1, ..., the leafy ones at
+  // 7, 6, ..., so the visit is two unrolled runs, each ending at the first slot that is not of
+  // its kind, and a slot's body holds its own kind's code alone: no kind test per entered slot
+  // (round 17: 2 x (s_bitcmp0 + s_cbranch) each) and no rank of the slot among the inner ones
+  // for the child reference (5 SALU per inner hit): slot c's child is inner_base + 2c.
+  const int child0 = inner_base | kWideTag;
+#pragma unroll
+  for (int c = 0; c < kWideSlots; c++) {
+    if (!(inner & (1u << c))) break;
+    DIAG(dg.ev[kPhSlotsTested]++);
+    const int w3[3] = {RT_NODE_WORD(8 + 3 * c), RT_NODE_WORD(9 + 3 * c), RT_NODE_WORD(10 + 3 * c)};
+    const uint64_t hm = slot_lanes(w3);
     if (hm) {
-      DIAG(dg.ev[kPhSlotHits]++);
-      if (kinds & (kSlotLeafy << c)) {
-        DIAG(dg.ev[kPhLeafyHits]++);
-        const int leaf = leaf_base + (int)((offs >> (4 * c)) & 15u);
-        [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
-        DIAG(dg.ev[kPhPairHits] += pair);
-        // (the shadow kernel keeps the exec-mask pushes: junk writes cost it VGPR spills)
-        batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
-        DIAG(dg.leaves += 1 + pair; dg.leaf_lanes += (1 + pair) * __builtin_popcountll(hm));
+      DIAG(dg.ev[kPhSlotHits]++; dg.ev[kPhInnerHits]++);
+      const int ch = child0 + 2 * c;
+      if (nxt < 0) {
+        nxt = ch;
+        nm = hm;
+      } else {
+        st.push(ch, hm);
       }
-      if (inner_bits & (1u << c)) {  // (a valid slot is leafy or inner)
-        const int ch = (inner_base + 2 * __builtin_popcount(inner & ((1u << c) - 1u))) | kWideTag;
-        DIAG(dg.ev[kPhInnerHits]++);
-        if (nxt < 0) {
-          nxt = ch;
-          nm = hm;
-        } else {
-          st.push(ch, hm);
-        }
-      }
+    }
+  }
+#pragma unroll
+  for (int c = kWideSlots - 1; c >= 0; c--) {
+    if (!(kinds & (kSlotLeafy << c))) break;
+    DIAG(dg.ev[kPhSlotsTested]++);
+    const int w3[3] = {RT_NODE_WORD(8 + 3 * c), RT_NODE_WORD(9 + 3 * c), RT_NODE_WORD(10 + 3 * c)};
+    const uint64_t hm = slot_lanes(w3);
+    if (hm) {
+      DIAG(dg.ev[kPhSlotHits]++; dg.ev[kPhLeafyHits]++);
+      const int leaf = leaf_base + (int)((offs >> (4 * c)) & 15u);
+      [[maybe_unused]] const bool pair = (kinds & (kSlotPair << c)) != 0;  // (RT_DIAG counts)
+      DIAG(dg.ev[kPhPairHits] += pair);
+      // (the shadow walk keeps the exec-mask pushes: in the separate shadow kernel junk writes
+      // cost VGPR spills, and in the fused frame kernel they measured 1.4 % slower, round 17,
+      // DESIGN.md §4.3)
+      batch_push_n<!SHADOW>(L, pending, leaf, hm, ((unsigned)kinds >> (16 + c)) & 1u);
+      DIAG(dg.leaves += 1 + pair; dg.leaf_lanes += (1 + pair) * __builtin_popcountll(hm));
     }
   }
   if (nxt >= 0) {

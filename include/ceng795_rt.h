@@ -196,6 +196,15 @@ int rt_host_check_accel_xml(const char* xml_path, int treelet_leaves, long long*
 /* Host-only: builds and checks the culling tree as above, then hist9[v] = its 8-wide nodes with
  * v valid slots (v = 0..8; all zero when the tree is a single treelet). */
 int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long long* hist9);
+/* Host-only: builds and checks the culling tree as above, then hist81[9 * i + l] = its 8-wide
+ * nodes with i inner and l leafy slots (i, l = 0..8). */
+int rt_host_accel_kind_hist_xml(const char* xml_path, int treelet_leaves, long long* hist81);
+/* Host-only, for tests: the slot-order rule of one 8-wide node record (128 bytes)
+ * as the culling-tree check applies it to every node: inner slots contiguous from slot 0, leafy
+ * slots contiguous down from slot 7, nothing valid between them, the two counts in the top byte
+ * of `kinds` equal to the bits, NaN planes in the invalid slots.  RT_E_INVALID with the broken
+ * rule in rt_last_error(). */
+int rt_host_check_wide_node(const void* node, unsigned long long bytes);
 /* Host-only: the size rule a scene's node array must pass (the kernels address culling nodes by
  * 32-bit byte offset, and the culling nodes are stored once per direction-sign octant, DESIGN.md
  * §3): RT_OK when ref_slots reference node slots and wide_slots culling node slots (one copy) fit,
