@@ -4,6 +4,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <array>
 #include <atomic>
@@ -45,6 +46,7 @@ long long read_reset_timeline(unsigned long long* out, long long max_values);
 long long read_reset_phases(unsigned long long* out, long long max_values);
 hipError_t frame_kernel_occupancy(int* out4);
 int launch_cold_order(RenderParams P, hipStream_t stream);
+void set_test_visit_time_exp(int on, int rel);
 hipError_t launch_query(const RenderParams& P, QueryParams Q, const DevNode* nodes, bool occlusion,
                         bool reorder, bool fast, bool deep, bool spheres, const SurfParams* surf,
                         hipStream_t stream);
@@ -2282,6 +2284,20 @@ int rt_host_packet_coords(int tiles_x, int num_sel_tiles, int tile_begin, int ti
     out4[4 * p + 3] = order_slot(P, G, p);
   }
   return G.packets;
+}
+
+int rt_host_visit_time_exp(const float* box6, const float* cam3) {
+  if (!box6 || !cam3) {
+    set_error(RT_E_INVALID, "rt_host_visit_time_exp: NULL argument");
+    return INT_MIN;
+  }
+  return visit_time_exp(box6, cam3);
+}
+
+int rt_test_visit_time_exp(int on, int rel) {
+  if (rel < -200 || rel > 200) return set_error(RT_E_INVALID, "rt_test_visit_time_exp: bad argument");
+  set_test_visit_time_exp(on ? 1 : 0, rel);
+  return RT_OK;
 }
 
 int rt_set_traversal(rt_scene* s, int mode) {

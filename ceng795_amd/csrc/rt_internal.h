@@ -307,9 +307,46 @@ RT_HD inline int div_by(int n, DivMagic m) {
   return (int)(((unsigned long long)(unsigned)n * m.mul) >> m.shift);
 }
 
+// The frame kernel's coherent visits run in scaled time t' = t 2^-E (visit_wide, DESIGN.md
+// §4.2): the slot test's zero bound is the clamp of axis 0's entry plane to [0, 1], which leaves
+// every entry distance below 1 as it is.  E is the launch's: the smallest exponent with 2^E at
+// least kVisitTimeFactor times the larger of the camera's distance to the farthest corner of the
+// culling tree's root box (a primary ray enters every box inside it earlier than that, its
+// direction being a unit vector) and the box's diagonal (a shadow ray starts inside the box).
+// Kept within +-kVisitTimeExpMax, where a reciprocal of any |d| >= 1e-6 (at most 2^20, and at least
+// 1 for a unit vector) times 2^-E stays normal and finite; a box beyond that range, like a
+// distance above 1 of any other cause, only costs culling (the clamp lowers an entry distance).
+// A box or camera that is not finite gives 0.
+constexpr int kVisitTimeFactor = 2, kVisitTimeExpMax = 64;
+RT_HD inline int visit_time_exp(const float* box6, const float* cam3) {
+  double far2 = 0.0, diag2 = 0.0;
+  for (int x = 0; x < 3; x++) {
+    const double lo = box6[x], hi = box6[x + 3], c = cam3[x];
+    if (!(lo - lo == 0.0 && hi - hi == 0.0 && c - c == 0.0)) return 0;  // an inf or a NaN
+    const double a = c - lo < 0 ? lo - c : c - lo, b = c - hi < 0 ? hi - c : c - hi;
+    const double f = a > b ? a : b;
+    far2 += f * f;
+    diag2 += (hi - lo) * (hi - lo);
+  }
+  const double r2 = far2 > diag2 ? far2 : diag2;
+  if (!(r2 > 0.0)) return 0;  // a box and a camera at one point: nothing to scale
+  // the smallest E with 4^E >= kVisitTimeFactor^2 r2 (the doubles hold every fp32 square exactly
+  // enough: a root that rounds up only makes E one larger)
+  const double need = (double)(kVisitTimeFactor * kVisitTimeFactor) * r2;
+  int e = -kVisitTimeExpMax;
+  double p = 1.0;
+  for (int k = 0; k < 2 * kVisitTimeExpMax; k++) p *= 0.5;  // 4^-kVisitTimeExpMax
+  while (e < kVisitTimeExpMax && p < need) {
+    p *= 4.0;
+    e++;
+  }
+  return e;
+}
+
 // What a traversal launch's index arithmetic divides by, worked out once on the host
-// (packet_geom below, called by order_geometry in rt_kernels.hip) instead of by every wave: an
-// argument of its own of the kernels that use it, so RenderParams keeps its layout.
+// (packet_geom below, called by order_geometry in rt_kernels.hip) instead of by every wave, and
+// the frame kernel's time scale: an argument of its own of the kernels that use it, so
+// RenderParams keeps its layout.
 struct PacketGeom {
   DivMagic by_tiles_x;    // a tile's row and column
   DivMagic by_deal_nbx;   // block deal: blocks per block row (deal_blocks_x)
@@ -318,6 +355,7 @@ struct PacketGeom {
   int block_nbx;          // ceil(tiles_x / kBlockW)
   int sel_rows;           // the selection's tile rows, num_sel_tiles / tiles_x (tile_block)
   int packets;            // trace_packets
+  int neg_t_exp;          // -E of the frame kernel's scaled visit time (visit_time_exp)
 };
 
 struct RenderParams {
@@ -416,7 +454,8 @@ RT_HD inline int trace_packets(const RenderParams& P) {
   return ((P.tiles_x + kBlockW - 1) / kBlockW) * ((tiles_y + kBlockH - 1) / kBlockH) * kTraceWaves;
 }
 
-// The PacketGeom of P's tiles_x, num_sel_tiles, tile_block and order_regions.
+// The PacketGeom of P's tiles_x, num_sel_tiles, tile_block and order_regions, and of its camera
+// and culling-tree root box (neg_t_exp).
 RT_HD inline PacketGeom packet_geom(const RenderParams& P) {
   PacketGeom g;
   g.block_nbx = (P.tiles_x + kBlockW - 1) / kBlockW;
@@ -426,6 +465,7 @@ RT_HD inline PacketGeom packet_geom(const RenderParams& P) {
   g.by_regions = div_magic(P.order_regions);
   g.sel_rows = P.tiles_x > 0 ? P.num_sel_tiles / P.tiles_x : 0;
   g.packets = P.tiles_x > 0 ? trace_packets(P) : 0;
+  g.neg_t_exp = P.accel_root >= 0 ? -visit_time_exp(P.accel_box, P.cam_e) : 0;
   return g;
 }
 

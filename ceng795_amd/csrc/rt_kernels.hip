@@ -21,6 +21,9 @@
 // / log are the fp64 ocml functions, matching the reference's double libm islands.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <type_traits>
@@ -96,6 +99,9 @@ struct LaneRay {
   V3 o, d;
   V3 r;       // v_rcp_f32 reciprocals (<= 1 ulp): the approximate slab test only
   V3 m;       // 2^-18 |o| / d per axis: the ray's share of the culling margin (visit_wide)
+  // The COHERENT visit's r and m, in scaled time t' = t 2^-E: r 2^-E and m 2^-E (coherent_ray;
+  // nobody else reads them, and make_ray leaves them unset) — DESIGN.md §4.2.
+  V3 vr, vm;
   bool skip0, skip1, skip2;  // |d_i| < 1e-6: axis ignored (HW2/bounding_box.cpp:21)
   bool quot;  // origin and scene in the shared-reciprocal range (tri_quotients)
   int sh0, sh1, sh2;  // 16 where 1/d_i < 0 (the slot's hi plane is the entry plane), else 0
@@ -121,6 +127,20 @@ __device__ __forceinline__ LaneRay make_ray(V3 o, V3 d, int scene_quot_ok) {
   r.sh1 = (int)((__float_as_uint(r.r.y) >> 27) & 16u);
   r.sh2 = (int)((__float_as_uint(r.r.z) >> 27) & 16u);
   return r;
+}
+
+// The frame kernel's packets: the COHERENT visit's constants of `r`, in the launch's scaled time
+// (neg_e = -E, PacketGeom::neg_t_exp, wave-uniform).  The scaling is by a power of two, so every
+// product and sum of the visit is 2^-E times what it would be at E = 0, bit for bit, while nothing
+// is subnormal (E is kept where the reciprocal of a tested axis stays normal, visit_time_exp; a
+// subnormal plane distance is below 2^(E-126) in t, far inside the margin), and the compares do
+// not change.  r, m, o and d stay as they are for every other reader: the root box's test has an
+// absolute term in its band, and the leaf batch rebuilds its reciprocals from d.
+__device__ __forceinline__ void coherent_ray(LaneRay& r, int neg_e) {
+  r.vr = v3(__builtin_amdgcn_ldexpf(r.r.x, neg_e), __builtin_amdgcn_ldexpf(r.r.y, neg_e),
+            __builtin_amdgcn_ldexpf(r.r.z, neg_e));
+  r.vm = v3(__builtin_amdgcn_ldexpf(r.m.x, neg_e), __builtin_amdgcn_ldexpf(r.m.y, neg_e),
+            __builtin_amdgcn_ldexpf(r.m.z, neg_e));
 }
 
 __device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
@@ -1020,7 +1040,11 @@ __device__ __forceinline__ float half_hi(int w) {
 // skipped axis (SKIP) gets S = 0 and planes -inf / +inf, once per visit.
 // COHERENT (the frame kernel's octant sub-walks): the node belongs to the octant copy of every
 // lane in `m` (octant_walks), whose words already hold the entry plane low — the same halves
-// reach the same fma_mix operands with no v_alignbit and no use of sh.
+// reach the same fma_mix operands with no v_alignbit and no use of sh.  Its plane distances are
+// in the launch's scaled time t 2^-E (coherent_ray: the ray's reciprocal and margin share times
+// 2^-E, every product and sum then scaling exactly), chosen so that every entry distance stays
+// below 1 (visit_time_exp), and the zero of `tf >= max(tn, 0)` is the clamp bit of axis 0's entry
+// fma_mix: a slot costs 6 fma_mix + max3 + min3 + one compare, 9 VALU.
 template <bool SKIP, bool SHADOW, bool DEEP, bool SPHERES, bool COHERENT = false>
 __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode* __restrict__ nodes,
                                            WaveLeafLds& L, int& pending, const LaneRay& r, int& node,
@@ -1035,7 +1059,10 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
   const unsigned offs = (unsigned)a[7];
   const unsigned inner = (unsigned)kinds & ~((unsigned)kinds >> 8) & 0xffu;
   DIAG(dg.nodes++; dg.wide++; dg.node_lanes += __builtin_popcountll(m));
-  const float o[3] = {r.o.x, r.o.y, r.o.z}, rc[3] = {r.r.x, r.r.y, r.r.z}, mg[3] = {r.m.x, r.m.y, r.m.z};
+  // (COHERENT: the reciprocal and the margin share in the launch's scaled time, coherent_ray)
+  const float o[3] = {r.o.x, r.o.y, r.o.z};
+  const float rc[3] = {COHERENT ? r.vr.x : r.r.x, COHERENT ? r.vr.y : r.r.y, COHERENT ? r.vr.z : r.r.z};
+  const float mg[3] = {COHERENT ? r.vm.x : r.m.x, COHERENT ? r.vm.y : r.m.y, COHERENT ? r.vm.z : r.m.z};
   [[maybe_unused]] const int sh[3] = {r.sh0, r.sh1, r.sh2};
   float S[3], Alo[3], Ahi[3];
 #pragma unroll
@@ -1061,6 +1088,11 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
   // scale), v_min3 ignores a NaN on the other axes, so tf = -inf, and max(tn, 0) >= 0 whatever
   // tn is (fmaxf drops a NaN tn): -inf >= it is false.  An invalid slot's NaN planes still fail
   // in every lane.
+  // COHERENT, where the zero bound is axis 0's clamp (slot_lanes): outside `m` tf is -inf as
+  // above, and tn is at least the clamped plane, 0 or more, or a NaN if the clamp lets a NaN
+  // entry plane through and the other two are NaN too — -inf >= either is false.  An invalid
+  // slot's exit planes are not clamped: tf = min3 of three NaN is NaN and fails every lane,
+  // whether the clamp turned the NaN entry plane into 0 or left it.
   {
     const bool in = lane_in(m);
     S[0] = in ? S[0] : 1.0f;
@@ -1079,6 +1111,18 @@ __device__ __forceinline__ bool visit_wide(const RenderParams& P, const DevNode*
         w = (int)__builtin_amdgcn_alignbit((unsigned)w, (unsigned)w, (unsigned)sh[x]);
       n3[x] = __builtin_fmaf(half_lo(w), S[x], Alo[x]);
       f3[x] = __builtin_fmaf(half_hi(w), S[x], Ahi[x]);
+    }
+    // COHERENT: tf >= max(tn, 0) with the zero as the clamp bit of axis 0's v_fma_mix — one
+    // v_max3 where a v_max and a v_max3 stood.  max3(clamp01(n0), n1, n2) = max(n0, n1, n2, 0)
+    // while n0 <= 1, which the launch's time scale sees to (visit_time_exp); a larger n0 enters
+    // the compare as 1, that is earlier, so the slot can only be entered by more lanes, the side
+    // the guard decides exactly.  In a lane of `m` on a valid slot n0 is no NaN
+    // (finite h and S, A finite or, skipped, -inf: clamped to 0).
+    if constexpr (COHERENT) {
+      n3[0] = __builtin_amdgcn_fmed3f(n3[0], 0.0f, 1.0f);
+      const float tn = __builtin_fmaxf(__builtin_fmaxf(n3[0], n3[1]), n3[2]);
+      const float tf = __builtin_fminf(__builtin_fminf(f3[0], f3[1]), f3[2]);
+      return lanes_ge(tf, tn);
     }
     const float tn = __builtin_fmaxf(__builtin_fmaxf(n3[0], n3[1]), n3[2]);
     const float tf = __builtin_fminf(__builtin_fminf(f3[0], f3[1]), f3[2]);
@@ -1369,6 +1413,22 @@ __device__ __forceinline__ const RenderParams& fresh_params(const RenderParams& 
   return *(const RenderParams*)p;
 }
 
+// The frame kernel's scaled-time exponent (PacketGeom::neg_t_exp of its LAST argument), read the
+// same way where a packet forms a ray, so that it is not kept in an SGPR across the walks.
+// FrameKernargs: trace_frame_kernel's parameters in order, for the offset alone.
+struct FrameKernargs {
+  RenderParams P;
+  const DevNode* nodes;
+  const DevLight* lights;
+  PacketGeom G;
+};
+__device__ __forceinline__ int fresh_neg_t_exp() {
+  typedef __attribute__((address_space(4))) const FrameKernargs Args;
+  Args* p = (Args*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p->G.neg_t_exp;
+}
+
 // ------------------------------------------------------------------ render kernels
 // Three phases per packet (trace_frame_kernel): the primary phase finds each pixel's closest
 // hit and leaves its leaf and its point in the wave's LDS block; the shadow phase traces the
@@ -1537,6 +1597,7 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
   DIAG(const unsigned long long s0 = clock_now());
   const PacketPixel q = wave_pixel(P, L);
   LaneRay ray = make_ray(ld3(P.cam_e), primary_dir(P, q.px, q.py), P.quot_ok);
+  if constexpr (FAST) coherent_ray(ray, fresh_neg_t_exp());
   // The camera origin is wave-uniform; left to itself the compiler keeps it in 3 SGPRs and
   // copies it to VGPRs at every node visit (a VALU op takes one SGPR operand, the box
   // coordinate already is one).  Pin it to VGPRs once.
@@ -1648,6 +1709,7 @@ __device__ __forceinline__ void shadow_packet(const RenderParams& P0,
       const V3 wi = normalize_shared(ld, !hit);  // (a lane without a hit traces no shadow ray)
       const float dist = length(ld);
       LaneRay sr = make_ray(pk + wi * P.eps, wi, P.quot_ok);  // p + eps * w_i
+      if constexpr (FAST) coherent_ray(sr, fresh_neg_t_exp());
       const float thr = dist - P.eps;
       const bool any_skip = hit && (sr.skip0 || sr.skip1 || sr.skip2);
       bool occ;
@@ -3038,6 +3100,27 @@ static void with_surface(const SurfParams* surf, F&& f) {
   }
 }
 
+// Tests only (rt_test_visit_time_exp): when on, every frame launch takes 2^E = the largest power
+// of two not above 2^rel times the root box's diagonal, instead of visit_time_exp's — far too
+// small an E makes the slot test's upper clamp bind, which may only cost culling.
+static std::atomic<int> g_test_t_exp_on{0}, g_test_t_exp_rel{0};
+void set_test_visit_time_exp(int on, int rel) {
+  g_test_t_exp_rel.store(rel);
+  g_test_t_exp_on.store(on);
+}
+static int test_visit_time_exp(const RenderParams& P, int e) {
+  if (!g_test_t_exp_on.load() || P.accel_root < 0) return e;
+  double diag2 = 0.0;
+  for (int x = 0; x < 3; x++) {
+    const double w = (double)P.accel_box[x + 3] - (double)P.accel_box[x];
+    diag2 += w * w;
+  }
+  if (!(diag2 > 0.0 && diag2 < 1e300)) return e;
+  int fl = 0;
+  (void)std::frexp(std::sqrt(diag2), &fl);  // diag = f 2^fl, f in [1/2, 1)
+  return std::max(-kVisitTimeExpMax, std::min(kVisitTimeExpMax, fl - 1 + g_test_t_exp_rel.load()));
+}
+
 template <bool FAST, bool DEEP, bool SPHERES>
 static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* marks,
                            const SurfParams* surf, hipStream_t stream) {
@@ -3060,6 +3143,7 @@ static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* 
   int tblocks = 0, per_region = 0;
   PacketGeom G;
   bool ordered = order_geometry(T, G, tblocks, per_region);
+  G.neg_t_exp = -test_visit_time_exp(T, -G.neg_t_exp);
   const size_t tlds = deep_lds_bytes<DEEP>(kTraceWaves);
   int oblocks = ordered ? T.order_regions * T.order_stride : tblocks;
   const RenderParams S = T;

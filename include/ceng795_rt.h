@@ -224,6 +224,15 @@ int rt_host_packet_div(int divisor, int first, int count, int* quot);
 int rt_host_packet_coords(int tiles_x, int num_sel_tiles, int tile_begin, int tile_step,
                           int block_deal, int order_regions, int order_stride, int count,
                           int* out4);
+/* Host-only, for tests: the frame kernel's scaled visit time — the functions the
+ * launch and the kernel themselves run.
+ * rt_host_visit_time_exp: the exponent E a frame launch takes for a culling-tree root box
+ * box6 = {lo xyz, hi xyz} and a camera position cam3; INT_MIN on a NULL argument.
+ * rt_test_visit_time_exp: on != 0 makes every later frame launch of the process take for 2^E the
+ * largest power of two not above 2^rel times the root box's diagonal (frames must not change:
+ * too small an E only costs culling); on == 0 restores the rule. */
+int rt_host_visit_time_exp(const float* box6, const float* cam3);
+int rt_test_visit_time_exp(int on, int rel);
 /* Height of the flattened BVH (levels of internal nodes). */
 int rt_scene_bvh_depth(const rt_scene* scene);
 
