@@ -184,6 +184,11 @@ SIGNATURES = {
     "rt_host_check_wide_node": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "rt_host_visit_time_exp": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_test_visit_time_exp": (C.c_int, [C.c_int, C.c_int]),
+    "rt_host_entry_cuts_xml": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                         C.POINTER(C.c_longlong)]),
+    "rt_host_check_entry_cuts_xml": (C.c_int, [C.c_char_p, C.c_int, C.c_int,
+                                               C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "rt_test_entry_cuts": (C.c_int, [C.c_int]),
     "rt_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "rt_debug_timeline": (C.c_longlong, [C.POINTER(C.c_ulonglong), C.c_longlong]),
     "rt_debug_phases": (C.c_longlong, [C.POINTER(C.c_ulonglong), C.c_longlong]),

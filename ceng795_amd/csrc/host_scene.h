@@ -88,6 +88,34 @@ void accel_kind_histogram(const HostScene& s, long long hist[(kWideSlots + 1) * 
 // broken rule.
 std::string wide_slot_order_error(const DevNode8& W);
 
+// Entry cuts (entry_cuts.cpp): per frame tile of camera c, kEntryCut tagged
+// references to culling nodes of octant copy 0 (-1 pads the unused places) that together hold every
+// leaf a pixel ray of the tile can reach; the frame kernel's primary walk starts at them instead of
+// the root.  Decided on the host from the tile's frustum alone, with no test in the kernel.
+// stats (may be null): see the kEc* indices.
+enum : int {
+  kEcTiles = 0,        // tiles
+  kEcBySize = 0,       // [kEcBySize + n], n = 1 .. kEntryCut: tiles whose cut has n nodes
+  kEcSavedVisits = 6,  // culling nodes above the cuts, summed over the tiles (visits no walk makes)
+  kEcSavedSlots = 7,   // ... and their valid slots
+  kEcByDepth = 8,      // [kEcByDepth + d]: tiles whose shallowest cut node lies d levels below the root
+  kEntryCutDepths = 15,  // (deeper ones count in the last)
+  kEcToRoot = 23,      // tiles the sign / skip rule sent to the root
+  kEntryCutStats = 24
+};
+static_assert(kEntryCut >= 1 && kEntryCut < kEcSavedVisits, "cut sizes 1 .. kEntryCut fit the stats");
+// Whether a scene gets tables at all: it has a culling tree under a node root, and the tree's
+// stack bound plus kEntryCut - 1 fits the `stack_entries` of the kernel instantiation that runs.
+bool entry_cuts_apply(const HostScene& s, int stack_entries);
+std::vector<int> build_entry_cuts(const HostScene& s, const rt_camera& c,
+                                  long long stats[kEntryCutStats]);
+// Every pixel ray of every tile of camera c, walked from the root with visit_wide's per-lane slot
+// test restated on the host: each leafy slot a ray enters must lie under a node of its tile's
+// record.  Returns the number of (ray, slot) violations (-1: the table does not fit the camera)
+// and in first[4] the first one: px, py, node slot, slot.
+long long check_entry_cuts(const HostScene& s, const rt_camera& c, const std::vector<int>& table,
+                           long long first[4]);
+
 // Builds `out` from `desc`; throws std::invalid_argument on a bad description.
 void build_host_scene(const rt_scene_desc& desc, HostScene& out);
 

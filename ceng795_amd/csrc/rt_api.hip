@@ -206,6 +206,8 @@ struct Replica {
   // per camera: its whole frame's cold order (seed_cold_orders), sched_words_for(tiles) words
   // laid out as a stream's `sched` (estimated costs, unit order, snapshot); empty: none
   std::vector<DevBuf<unsigned>> d_cold;
+  // per camera: its entry cuts (seed_entry_cuts), kEntryCut ints per frame tile; empty: none
+  std::vector<DevBuf<int>> d_cuts;
   std::mutex mu;  // ctx pool and stream tables
   std::vector<std::unique_ptr<RenderCtx>> ctx_all;  // every context; the two below point into it
   std::vector<RenderCtx*> ctx_free;
@@ -439,6 +441,41 @@ void seed_cold_orders(const rt_scene* s, Replica& r) {
   hip_check(hipDeviceSynchronize(), "cold orders");
 }
 
+// Every camera's entry cuts on replica r (entry_cuts.cpp), built on the host with
+// the scene like the cold orders: the frame kernel's primary walks of a frame tile start at its
+// record's nodes instead of the root.  Cameras whose frames the frame kernel does not render (ray
+// trees, MSAA) get none, nor does a scene entry_cuts_apply turns down.  A table that cannot be
+// built or uploaded leaves its camera without cuts; the scene is created all the same.
+void seed_entry_cuts(const rt_scene* s, Replica& r) {
+  const HostScene& h = s->host;
+  r.d_cuts = std::vector<DevBuf<int>>(h.cameras.size());
+  if (s->tree_frames() || !entry_cuts_apply(h, s->deep ? max_supported_depth() : kLaneStack - 2))
+    return;
+  for (size_t cam = 0; cam < h.cameras.size(); cam++) {
+    if (h.cameras[cam].num_samples > 1) continue;
+    try {
+      r.d_cuts[cam] = upload(build_entry_cuts(h, h.cameras[cam], nullptr), "upload entry cuts", 0);
+    } catch (const std::exception&) {
+      (void)hipGetLastError();
+      r.d_cuts[cam] = DevBuf<int>();
+    }
+  }
+}
+
+// Tests only (rt_test_entry_cuts): 1 = no launch binds a table.
+static std::atomic<int> g_test_entry_cuts{0};
+
+// The camera's table for a launch whose logical tile rows are image tile rows — rows row0,
+// row0 + 1, ... with row0 on a tile row — from that tile row on; any other selection of rows
+// (strided rows, a band not cut at a tile row) walks from the root.  Tile deals, blocks, records
+// and split tiles keep their frame tile and use it.
+const int* bind_entry_cuts(const Replica& r, int cam, int row0, int row_stride, int tiles_x) {
+  if (g_test_entry_cuts.load() == 1 || row_stride != 1 || row0 % kTile != 0 ||
+      cam >= (int)r.d_cuts.size() || !r.d_cuts[cam].p)
+    return nullptr;
+  return r.d_cuts[cam].p + (size_t)(row0 / kTile) * tiles_x * kEntryCut;
+}
+
 void upload_replica(const rt_scene* s, Replica& r) {
   DeviceGuard g(r.device);
   const HostScene& h = s->host;
@@ -468,6 +505,7 @@ void upload_replica(const rt_scene* s, Replica& r) {
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
+  seed_entry_cuts(s, r);
 }
 
 // Builds the culling tree once on the host, then uploads the scene to every device.  Several
@@ -606,6 +644,7 @@ RenderParams make_params(const rt_scene* s, const Replica& r, int cam, int row0,
     P.cold_order = reinterpret_cast<const int*>(r.d_cold[cam].p) + P.num_sel_tiles;
     P.cold_tiles = P.num_sel_tiles;
   }
+  P.entry_cuts = bind_entry_cuts(r, cam, row0, row_stride, tp.tiles_x);
   return P;
 }
 
@@ -2298,6 +2337,56 @@ int rt_test_visit_time_exp(int on, int rel) {
   if (rel < -200 || rel > 200) return set_error(RT_E_INVALID, "rt_test_visit_time_exp: bad argument");
   set_test_visit_time_exp(on ? 1 : 0, rel);
   return RT_OK;
+}
+
+int rt_test_entry_cuts(int mode) {
+  if (mode != 0 && mode != 1) return set_error(RT_E_INVALID, "rt_test_entry_cuts: bad argument");
+  g_test_entry_cuts.store(mode);
+  return RT_OK;
+}
+
+// The scene file's host scene with its culling tree, and whether it gets entry cuts (as
+// create_from_host and seed_entry_cuts decide it).
+static bool entry_cut_scene(const char* xml_path, int treelet_leaves, int cam, HostScene& h) {
+  XmlSceneStorage st;
+  rt_scene_desc d;
+  load_scene_xml(xml_path, st, d);
+  build_host_scene(d, h);
+  build_accel(h, treelet_leaves);
+  if (h.accel_depth > max_supported_depth()) build_accel(h, 0);
+  if (cam < 0 || cam >= (int)h.cameras.size())
+    throw std::invalid_argument("camera index out of range");
+  const bool deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
+  return entry_cuts_apply(h, deep ? max_supported_depth() : kLaneStack - 2);
+}
+
+int rt_host_entry_cuts_xml(const char* xml_path, int treelet_leaves, int cam, int* out,
+                           long long capacity, long long* stats24) {
+  if (!xml_path) return set_error(RT_E_INVALID, "rt_host_entry_cuts_xml: NULL argument");
+  return guarded([&] {
+    HostScene h;
+    if (stats24) std::fill(stats24, stats24 + kEntryCutStats, 0ll);
+    if (!entry_cut_scene(xml_path, treelet_leaves, cam, h)) return 0;
+    const std::vector<int> table = build_entry_cuts(h, h.cameras[cam], stats24);
+    if (out && capacity >= (long long)table.size())
+      std::memcpy(out, table.data(), table.size() * sizeof(int));
+    return (int)table.size();
+  });
+}
+
+int rt_host_check_entry_cuts_xml(const char* xml_path, int treelet_leaves, int cam,
+                                 long long* violations, long long* first4) {
+  if (!xml_path || !violations)
+    return set_error(RT_E_INVALID, "rt_host_check_entry_cuts_xml: NULL argument");
+  return guarded([&] {
+    HostScene h;
+    *violations = 0;
+    if (!entry_cut_scene(xml_path, treelet_leaves, cam, h)) return 0;
+    const std::vector<int> table = build_entry_cuts(h, h.cameras[cam], nullptr);
+    *violations = check_entry_cuts(h, h.cameras[cam], table, first4);
+    if (*violations < 0) throw std::runtime_error("entry cuts: the table does not fit the camera");
+    return (int)table.size();
+  });
 }
 
 int rt_set_traversal(rt_scene* s, int mode) {

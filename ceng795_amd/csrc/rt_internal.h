@@ -116,6 +116,13 @@ constexpr int kOctantCopies = 8;
 // (accel_build.cpp accel_slots_error)
 constexpr size_t kMaxNodeSlots = size_t(1) << 26;
 constexpr int kWideSlots = 8;
+// Entry cuts (entry_cuts.cpp): node references per frame tile at which the frame
+// kernel's primary walks start — one 16-byte record, one scalar load.  (A/B builds: 1, 2.)
+#ifndef RT_ENTRY_CUT
+#define RT_ENTRY_CUT 4
+#endif
+constexpr int kEntryCut = RT_ENTRY_CUT;
+static_assert(kEntryCut == 1 || kEntryCut == 2 || kEntryCut == 4, "a record is one scalar load");
 enum : int32_t { kSlotValid = 1, kSlotLeafy = 1 << 8, kSlotPair = 1 << 16 };
 constexpr int kSlotInnerCountShift = 24, kSlotLeafyCountShift = 28;  // counts 0..8, 4 bits each
 struct alignas(16) DevNode8 {
@@ -401,7 +408,12 @@ struct RenderParams {
   unsigned msaa_mul[2];
   unsigned long long msaa_seed;
   float* out;
-  void* reserved;  // always null (was the hit records; kept so that no other field moves)
+  // Entry cuts (entry_cuts.cpp; null: every primary walk starts at the root): the camera's table
+  // from the launch's first tile row on, kEntryCut node references per frame tile — record
+  // ty * tiles_x + tx of the packet's tile.  Bound only when the launch's logical tile rows are
+  // image tile rows (rt_api.hip bind_entry_cuts).  (In the place of the hit records' pointer of old,
+  // which had stayed as a null word: no other field moves.)
+  const int* entry_cuts;
   unsigned* occ;  // num_sel_tiles * 64 * occ_words light-occlusion bits: trace_shadow -> shade
   int occ_words;  // ceil(num_lights / 32)
   // heavy-first dispatch (null: off).  tile_cost[sel] holds each selected

@@ -1218,7 +1218,7 @@ template <bool SKIP, bool FAST, bool DEEP, bool SPHERES, bool CAMERA = false, bo
 __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode* __restrict__ nodes,
                                             int* spill, WaveLeafLds& L, const LaneRay& r,
                                             bool active, float& best_t, int& best_leaf, Diag& dg,
-                                            int root_off = 0) {
+                                            int root_off = 0, const int* cut = nullptr) {
   static_assert(!OCT || FAST, "octant copies exist of the culling nodes only");
   if (!OCT) {
     best_t = RT_INF;
@@ -1252,6 +1252,20 @@ __device__ __forceinline__ void closest_hit(const RenderParams& P, const DevNode
   int pending = 0, waiting = 0;  // queued tests; survivors waiting for their guard (wave-uniform)
   if (!OCT) L.key[lane] = kNoHitKey;
   int node = FAST ? P.accel_root + root_off : P.root_ref;
+  // The packet's entry cut (entry_record; the primary sub-walks): the walk starts at the cut's
+  // first node and holds the others on the stack, all with the root box's mask — the host has shown
+  // that no ray of the tile reaches a leaf outside them (entry_cuts.cpp).
+  if constexpr (OCT) {
+    if (cut) {
+      node = cut[0] + root_off;
+#pragma unroll
+      for (int i = 1; i < kEntryCut; i++)
+        if (cut[i] >= 0) st.push(cut[i] + root_off, m);
+      // (the LDS stack's push writes under `lane 0`: folded into these wave-uniform conditions,
+      // that branch made the compiler take the stack pointer for a per-lane value)
+      if constexpr (DEEP) st.sp = uniform(st.sp);
+    }
+  }
   // (an octant sub-walk: the visits' priority is set once and after each flush, and lowered where
   // the walk leaves the loop — no s_setprio pair between two visits that no flush separates,
   // DESIGN.md §4.3 round 14; every other walk keeps the pair around each visit)
@@ -1427,6 +1441,32 @@ __device__ __forceinline__ int fresh_neg_t_exp() {
   Args* p = (Args*)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
   return p->G.neg_t_exp;
+}
+
+// The entry cut of the wave's tile (RenderParams::entry_cuts): one scalar load of the tile's
+// record, its address from the wave's tile in LDS and the kernel arguments read afresh, so that
+// nothing of it is live across a walk.  Without a table, the root alone.
+struct alignas(4 * kEntryCut) EntryRecord {
+  int ref[kEntryCut];
+};
+__device__ __forceinline__ EntryRecord entry_record(const RenderParams& P, const WaveLeafLds& L) {
+  const RenderParams& F = fresh_params(P);
+  EntryRecord rec;
+  rec.ref[0] = F.accel_root;
+#pragma unroll
+  for (int i = 1; i < kEntryCut; i++) rec.ref[i] = -1;
+  if (F.entry_cuts) {
+    const int tile = uniform(L.ty) * F.tiles_x + uniform(L.tx);
+    // (constant address space: the table is read-only for the life of the scene — a scalar load)
+    typedef __attribute__((address_space(4))) const EntryRecord Records;
+    Records* q = (Records*)F.entry_cuts + tile;
+#pragma unroll
+    for (int i = 0; i < kEntryCut; i++) rec.ref[i] = q->ref[i];
+  }
+  // (wave-uniform by construction; said so, since the references feed scalar node loads)
+#pragma unroll
+  for (int i = 0; i < kEntryCut; i++) rec.ref[i] = uniform(rec.ref[i]);
+  return rec;
 }
 
 // ------------------------------------------------------------------ render kernels
@@ -1612,12 +1652,13 @@ __device__ __forceinline__ void primary_packet(const RenderParams& P,
     L.key[lane_id()] = kNoHitKey;
     octant_walks(ray, q.valid, dg, [&](bool mine, int k) {
       const int off = k * P.accel_stride;
+      const EntryRecord cut = entry_record(P, L);  // (per sub-walk: not held across one)
       if (ballot(mine && any_skip))
         closest_hit<true, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, ray, mine, t, leaf,
-                                                           dg, off);
+                                                           dg, off, cut.ref);
       else
         closest_hit<false, FAST, DEEP, SPHERES, true, true>(P, nodes, spill, L, ray, mine, t, leaf,
-                                                            dg, off);
+                                                            dg, off, cut.ref);
     });
     const unsigned long long key = L.key[lane_id()];
     t = __uint_as_float((unsigned)(key >> 32));

@@ -233,6 +233,30 @@ int rt_host_packet_coords(int tiles_x, int num_sel_tiles, int tile_begin, int ti
  * too small an E only costs culling); on == 0 restores the rule. */
 int rt_host_visit_time_exp(const float* box6, const float* cam3);
 int rt_test_visit_time_exp(int on, int rel);
+/* Host-only, for tests and tools: the entry cuts of camera `cam` of a scene file —
+ * per 8x8 frame tile, row-major, RT_ENTRY_CUT_NODES references to culling-tree nodes (tagged node
+ * slots of octant copy 0, -1 in the unused places) at which the frame kernel starts the tile's
+ * primary walk, built by the function scene creation runs.
+ * rt_host_entry_cuts_xml returns the table's length in ints, tiles x RT_ENTRY_CUT_NODES, and
+ * copies it to `out` when capacity holds it (out may be NULL); 0: the scene gets no table (no
+ * culling tree, a root that is a primitive, or a tree too deep for the walk's stack); < 0: an
+ * error.  stats24 (may be NULL): [0] tiles, [n] tiles whose cut has n nodes (n = 1 ..
+ * RT_ENTRY_CUT_NODES), [6] culling nodes above the cuts summed over the tiles (the visits the
+ * walks no longer make) and [7] their valid slots, [8 + d] tiles whose shallowest cut node lies d
+ * levels below the root (d >= 14 in [22]), [23] tiles kept at the root because their frustum
+ * holds a direction with a zero or nearly zero component.
+ * rt_host_check_entry_cuts_xml builds the same table and walks every pixel ray of every tile from
+ * the root with the kernel's per-lane slot test restated on the host; every leafy slot a ray
+ * enters must lie under a node of its tile's record.  *violations = the (ray, slot) pairs that do
+ * not, first4 (may be NULL) = the first one's pixel x, y, node slot and slot.  Returns as above.
+ * rt_test_entry_cuts: mode 1 makes every later launch of the process walk from the root (frames
+ * must not change), 0 restores the default. */
+#define RT_ENTRY_CUT_NODES 4
+int rt_host_entry_cuts_xml(const char* xml_path, int treelet_leaves, int cam, int* out,
+                           long long capacity, long long* stats24);
+int rt_host_check_entry_cuts_xml(const char* xml_path, int treelet_leaves, int cam,
+                                 long long* violations, long long* first4);
+int rt_test_entry_cuts(int mode);
 /* Height of the flattened BVH (levels of internal nodes). */
 int rt_scene_bvh_depth(const rt_scene* scene);
 
