@@ -17,13 +17,17 @@ Python mirror of the reference's render interface (HW2/Scene.h:30-43):
     attr = scene.hit_attributes(origins, directions, hits)  # beta, gamma, uv, both normals
     scene = Scene.create(desc, instance_mesh=..., instance_material=...,
                          instance_transform=...)      # transformed copies of the base meshes (HW3)
+    scene = Scene.create(desc, vertex_uv=uv, textures=[dict(rgb8=image, ...)],
+                         mesh_texture=[0, -1])        # image textures in the library's shading (HW4)
+    scene = Scene("scene.xml", textured=True, images={"floor.png": image})
 
 Rendering runs in libceng795_rt.so's gfx950 kernels; there is no CPU path.
 """
 from .scene import (Scene, CameraInfo, write_png, RAY_DTYPE, HIT_DTYPE, RADIANCE_DTYPE,  # noqa: F401
                     LIGHT_SAMPLE_DTYPE, HIT_ATTR_DTYPE, pack_rays, host_leaf_objects,
                     host_vertex_normals, host_mesh_smooth, host_instance_info,
-                    host_instances_xml, host_motion_info, host_motion_xml)
+                    host_instances_xml, host_motion_info, host_motion_xml, TEX_QUERY_DTYPE,
+                    host_texture_lookup, host_textures_xml)
 from .film import Film  # noqa: F401
 from ._lib import RTError, RT_TRAVERSAL_FAST, RT_TRAVERSAL_REFERENCE  # noqa: F401
 
@@ -31,4 +35,5 @@ __all__ = ["Scene", "Film", "CameraInfo", "write_png", "RTError", "RT_TRAVERSAL_
            "RT_TRAVERSAL_REFERENCE", "RAY_DTYPE", "HIT_DTYPE", "RADIANCE_DTYPE", "LIGHT_SAMPLE_DTYPE",
            "HIT_ATTR_DTYPE", "pack_rays", "host_leaf_objects", "host_vertex_normals",
            "host_mesh_smooth", "host_instance_info", "host_instances_xml",
-           "host_motion_info", "host_motion_xml"]
+           "host_motion_info", "host_motion_xml", "TEX_QUERY_DTYPE", "host_texture_lookup",
+           "host_textures_xml"]

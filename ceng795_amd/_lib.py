@@ -120,6 +120,31 @@ class rt_motion_desc(C.Structure):
 
 RT_ATTR_HIT, RT_ATTR_TRIANGLE, RT_ATTR_SMOOTH = 1, 2, 4  # rt_hit_attr::flags
 
+RT_TEX_NEAREST, RT_TEX_BILINEAR = 0, 1  # rt_texture::interpolation
+RT_TEX_REPLACE_KD, RT_TEX_BLEND_KD, RT_TEX_REPLACE_ALL = 0, 1, 2  # rt_texture::decal
+RT_TEX_REPEAT, RT_TEX_CLAMP = 0, 1  # rt_texture::appearance
+
+
+class rt_texture(C.Structure):
+    _fields_ = [("rgb8", C.POINTER(C.c_ubyte)), ("width", C.c_int), ("height", C.c_int),
+                ("interpolation", C.c_int), ("decal", C.c_int), ("appearance", C.c_int),
+                ("normalizer", C.c_float)]
+
+
+class rt_texture_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("num_textures", C.c_int),
+                ("textures", C.POINTER(rt_texture)), ("mesh_texture", C.POINTER(C.c_int)),
+                ("triangle_texture", C.POINTER(C.c_int)), ("sphere_texture", C.POINTER(C.c_int))]
+
+
+class rt_texture_image(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("rgb8", C.POINTER(C.c_ubyte)), ("width", C.c_int),
+                ("height", C.c_int)]
+
+
+class rt_tex_query(C.Structure):
+    _fields_ = [("texture", C.c_int), ("u", C.c_float), ("v", C.c_float), ("pad", C.c_int)]
+
 
 class rt_hit_attr(C.Structure):
     _fields_ = [("beta", C.c_float), ("gamma", C.c_float), ("uv", C.c_float * 2),
@@ -250,6 +275,22 @@ SIGNATURES = {
     "rt_hit_attributes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                            C.c_void_p, C.c_void_p]),
     "rt_hit_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "rt_textures_version": (C.c_int, []),
+    "rt_scene_create_textured": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_surface_desc),
+                                           C.POINTER(rt_texture_desc), C.c_int,
+                                           C.POINTER(C.c_void_p)]),
+    "rt_scene_num_textures": (C.c_int, [C.c_void_p]),
+    "rt_scene_load_xml_textured": (C.c_int, [C.c_char_p, C.POINTER(rt_texture_image), C.c_int,
+                                             C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_host_textures_xml": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                       C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
+    "rt_texture_lookup_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                           C.c_void_p]),
+    "rt_texture_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "rt_host_texture_lookup_desc": (C.c_int, [C.POINTER(rt_texture_desc), C.c_void_p, C.c_longlong,
+                                              C.c_void_p]),
     "rt_instances_version": (C.c_int, []),
     "rt_scene_create_instanced": (C.c_int, [C.POINTER(rt_scene_desc), C.POINTER(rt_instance_desc),
                                             C.c_int, C.POINTER(C.c_void_p)]),

@@ -59,6 +59,12 @@ struct HostScene {
   std::vector<int> leaf_tri;          // 4 per DFS leaf: i0 i1 i2 flags (kSurfSmooth); a sphere: 0
   std::vector<float> vertex_normals;  // 4 per vertex (smooth scenes)
   std::vector<float> vertex_uv;       // 2 per vertex (scenes with uv)
+  // image textures (build_textures): empty unless some object names a texture.
+  // A textured scene has leaf_tri, with each leaf's texture id + 1 above the smooth bit, and one
+  // material more than the description's: blank_material, all zero, for REPLACE_ALL hits.
+  std::vector<DevTexture> textures;
+  std::vector<uint32_t> texels;       // every texture's texels, 4 bytes each
+  int blank_material = -1;
 };
 
 // The vertex normals of HW3/src/Scene.cpp:690-695 and 870-876 (the rule in ceng795_rt.h) into
@@ -66,6 +72,16 @@ struct HostScene {
 void host_vertex_normals(const rt_scene_desc& desc, float* out);
 // The surface data of a built scene (s made from desc by build_host_scene); surf may be null.
 void build_surface(const rt_scene_desc& desc, const rt_surface_desc* surf, HostScene& s);
+// The textures of a built scene (after build_surface with the same `surf`); tex may be null.
+// Checks the descriptor (std::invalid_argument).  No object with a texture: s is left as it was.
+void build_textures(const rt_scene_desc& desc, const rt_surface_desc* surf,
+                    const rt_texture_desc* tex, HostScene& s);
+// The descriptor's textures, checked, as the device table and the 4-byte texel blob.
+void pack_textures(const rt_texture_desc& tex, std::vector<DevTexture>& table,
+                   std::vector<uint32_t>& texels);
+// tex_get_color for n queries; a texture id out of range gives 0 0 0.
+void host_texture_lookup(const std::vector<DevTexture>& table, const std::vector<uint32_t>& texels,
+                         const rt_tex_query* q, long long n, float* rgb);
 
 // Cuts the reference tree into treelets of <= K leaves (K = 1: lone leaves; 2: also leaf
 // pairs; K <= 0: no culling tree) and appends an 8-wide SAH tree over them.  Leaves the
@@ -208,6 +224,27 @@ struct XmlSceneStorage {
   std::vector<unsigned char> mesh_smooth;
 };
 void load_scene_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc& desc);
+
+// The texture part of a scene file (rt_scene_load_xml_textured; HW4/src/Scene.cpp:690-701,
+// 761-768, 905-911, 1008-1014, 1030-1077): <TexCoordData> as pairs, the root <Textures> block with
+// the reference's defaults, the 1-based <Texture> child of <Mesh>, <Triangle> and <Sphere>.
+// Throws std::domain_error on what textured scenes do not take (perlin, bumpmap="true",
+// <BackgroundTexture>, a textured mesh whose textureOffset differs from its vertexOffset, plyFile).
+struct XmlTextures {
+  std::vector<std::string> image_name;
+  std::vector<int> interpolation, decal, appearance;  // RT_TEX_*
+  std::vector<float> normalizer;
+  std::vector<int> mesh_texture, triangle_texture, sphere_texture;  // 0-based, -1: none
+  std::vector<float> uv;  // 2 per <TexCoordData> pair
+};
+void load_textures_xml(const std::string& path, XmlTextures& out);
+// The descriptor of a loaded file: its textures matched to the caller's image records by name
+// (std::ios_base::failure for a name without one), the per-vertex uv (pairs by vertex id, zeros
+// past the file's; std::domain_error when a textured face needs a pair the file lacks).  `tex`
+// points into xt, records and uv.
+void textures_from_xml(const XmlTextures& xt, const rt_scene_desc& d, const rt_texture_image* images,
+                       int num_images, std::vector<rt_texture>& records, std::vector<float>& uv,
+                       rt_texture_desc& tex);
 
 void camera_from_view(const float pos[3], const float gaze[3], const float up[3],
                       const float np[4], float dist, int w, int h, int ns, rt_camera& c);

@@ -28,7 +28,7 @@
 namespace rt {
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
                          const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
-                         const MotionParams* motion, hipStream_t stream);
+                         const MotionParams* motion, const TexParams* tex, hipStream_t stream);
 hipError_t launch_motion_inverse(const float* fwd, const float* vel, const float* times,
                                  long long n, float* out12, hipStream_t stream);
 int max_supported_depth();
@@ -57,7 +57,8 @@ hipError_t launch_inst_query(const RenderParams& P, QueryParams Q, const InstPar
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
                            bool spheres, const SurfParams* surf, const InstParams* inst,
-                           const MotionParams* motion, hipStream_t stream);
+                           const MotionParams* motion, const TexParams* tex, hipStream_t stream);
+hipError_t launch_texture_lookup(const TexParams& X, const TexLookupParams& A, hipStream_t stream);
 hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, const AttrParams& A,
                                  hipStream_t stream);
 hipError_t launch_film_splat(const FilmParams& F, const hipEvent_t* marks, hipStream_t stream);
@@ -180,6 +181,10 @@ struct Replica {
   DevBuf<int> d_surf_tri;
   DevBuf<float> d_surf_normals, d_surf_uv;
   SurfParams surf{nullptr, nullptr, nullptr, 0};
+  // image textures (HostScene::textures / texels), a textured scene only; `tex` points at them
+  DevBuf<DevTexture> d_tex_table;
+  DevBuf<uint32_t> d_texels;
+  TexParams tex{nullptr, nullptr, 0, -1};
   // an instanced scene: every base mesh's arrays, the mesh and instance tables
   // and the top-level tree; `inst` points at them
   struct MeshBufs {
@@ -228,7 +233,10 @@ struct rt_scene {
   // some mesh is smooth (rt_scene_create_surface): frames take the ray-tree path, as a scene that
   // recurses does, and the ray-tree and closest-hit kernels run their SMOOTH instantiations
   bool smooth = false;
-  bool tree_frames() const { return needs_recursion || smooth || inst != nullptr; }
+  // some object has a texture (rt_scene_create_textured): frames take the ray-tree path too, and
+  // the ray-tree kernels run their TEX instantiations
+  bool textured = false;
+  bool tree_frames() const { return needs_recursion || smooth || textured || inst != nullptr; }
   // made of instances (rt_scene_create_instanced): `host` holds the scene's scalars, materials,
   // lights and cameras and no tree; the ray queries, the radiance queries and the frames (on the
   // ray-tree path, like a smooth scene's) run their INST kernels; nothing that reads the flat
@@ -502,6 +510,11 @@ void upload_replica(const rt_scene* s, Replica& r) {
     r.d_surf_uv = upload(h.vertex_uv, "upload vertex uv", 0);
     r.surf.uv = r.d_surf_uv.p;
   }
+  if (!h.textures.empty()) {
+    r.d_tex_table = upload(h.textures, "upload texture table", 0);
+    r.d_texels = upload(h.texels, "upload texels", 0);
+    r.tex = TexParams{r.d_tex_table.p, r.d_texels.p, (int)h.textures.size(), h.blank_material};
+  }
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
@@ -537,6 +550,7 @@ int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
   s->deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
   for (const DevPrim& p : h.prims) s->has_spheres |= p.kind == kPrimSphere;
   s->smooth = h.smooth;
+  s->textured = !h.textures.empty();
   scene_shading_state(s);
   for (int d : devices) {
     s->rep.push_back(std::make_unique<Replica>());
@@ -732,6 +746,12 @@ const hipEvent_t* timing_marks(rt_scene* s, const RenderParams& P) {
 const SurfParams* smooth_surface(const rt_scene* s) {
   return s->smooth ? &s->rep[0]->surf : nullptr;
 }
+// What the ray-tree launches take: a textured scene's textures (and then its surface data, smooth
+// mesh or not: the TEX instantiations are SMOOTH ones), else null and the surface data as above.
+const TexParams* tree_textures(const rt_scene* s) { return s->textured ? &s->rep[0]->tex : nullptr; }
+const SurfParams* tree_surface(const rt_scene* s) {
+  return s->textured ? &s->rep[0]->surf : smooth_surface(s);
+}
 // What the INST kernels take: an instanced scene's tables (single-device), else null.
 const InstParams* inst_params(const rt_scene* s) { return s->inst ? &s->rep[0]->inst : nullptr; }
 // What the motion kernels take beside them: the scene's motion tables with the call's traversal
@@ -769,7 +789,8 @@ void enqueue_samples(rt_scene* s, const RenderParams& P, int samples, float* d_s
     Q.tile_major = 0;
     Q.out = d_samples + (size_t)k * frame;
     hip_check(launch_render(Q, fast, s->deep, s->has_spheres, timed ? timing_marks(s, Q) : nullptr,
-                            smooth_surface(s), inst_params(s), motion_call(s, 0).get(), stream),
+                            tree_surface(s), inst_params(s), motion_call(s, 0).get(),
+                            tree_textures(s), stream),
               "render launch");
   }
 }
@@ -798,7 +819,8 @@ void enqueue_frame(rt_scene* s, const RenderParams& P, int samples, float* d_sam
   const bool fast = s->mode != RT_TRAVERSAL_REFERENCE;
   if (samples <= 1) {
     hip_check(launch_render(P, fast, s->deep, s->has_spheres, timed ? timing_marks(s, P) : nullptr,
-                            smooth_surface(s), inst_params(s), motion_call(s, 0).get(), stream),
+                            tree_surface(s), inst_params(s), motion_call(s, 0).get(),
+                            tree_textures(s), stream),
               "render launch");
     return;
   }
@@ -1419,8 +1441,8 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
       C.n = std::min(part, R.first + chunk);
       hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
                                 s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres,
-                                smooth_surface(s), inst_params(s), motion_call(s, q.flags).get(),
-                                stream),
+                                tree_surface(s), inst_params(s), motion_call(s, q.flags).get(),
+                                tree_textures(s), stream),
                 "radiance query launch");
     }
   }
@@ -1718,6 +1740,156 @@ int rt_scene_load_xml_surface(const char* xml_path, int device, rt_scene** out) 
 }
 
 int rt_scene_has_smooth(const rt_scene* s) { return s && s->smooth ? 1 : 0; }
+
+int rt_textures_version(void) { return 1; }
+
+int rt_scene_create_textured(const rt_scene_desc* desc, const rt_surface_desc* surface,
+                             const rt_texture_desc* textures, int device, rt_scene** out) {
+  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_textured: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    if (surface && surface->struct_size < sizeof(rt_surface_desc))
+      throw std::invalid_argument("rt_scene_create_textured: rt_surface_desc::struct_size too small");
+    // the whole host build, every check of the three descriptions in it, before any HIP call
+    build_host_scene(*desc, s->host);
+    build_surface(*desc, surface, s->host);
+    build_textures(*desc, surface, textures, s->host);
+    const std::vector<int> devs = single_device(device);
+    return create_from_host(s.get(), devs, false);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_scene_load_xml_textured(const char* xml_path, const rt_texture_image* images, int num_images,
+                               int device, rt_scene** out) {
+  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_textured: NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    XmlSceneStorage st;
+    rt_scene_desc d;
+    load_scene_xml(xml_path, st, d);
+    XmlTextures xt;
+    load_textures_xml(xml_path, xt);
+    std::vector<rt_texture> records;
+    std::vector<float> uv;
+    rt_texture_desc tex;
+    textures_from_xml(xt, d, images, num_images, records, uv, tex);
+    s->host.image_names = st.image_names;
+    build_host_scene(d, s->host);
+    const rt_surface_desc sd{sizeof(rt_surface_desc), st.mesh_smooth.data(), nullptr, uv.data()};
+    build_surface(d, &sd, s->host);
+    build_textures(d, &sd, &tex, s->host);
+    const std::vector<int> devs = single_device(device);
+    return create_from_host(s.get(), devs, false);
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+int rt_host_textures_xml(const char* xml_path, char* names, int* modes3, float* normalizer,
+                         int texture_capacity, int* mesh_texture, int* triangle_texture,
+                         int* sphere_texture, int object_capacity, float* uv2, int uv_capacity,
+                         int* counts5) {
+  if (!xml_path || texture_capacity < 0 || object_capacity < 0 || uv_capacity < 0)
+    return set_error(RT_E_INVALID, "rt_host_textures_xml: bad argument");
+  return guarded([&] {
+    XmlTextures xt;
+    load_textures_xml(xml_path, xt);
+    const int nt = (int)xt.image_name.size();
+    for (int k = 0; k < std::min(nt, texture_capacity); k++) {
+      if (names) std::snprintf(names + 256 * (size_t)k, 256, "%s", xt.image_name[(size_t)k].c_str());
+      if (modes3) {
+        modes3[3 * k] = xt.interpolation[(size_t)k];
+        modes3[3 * k + 1] = xt.decal[(size_t)k];
+        modes3[3 * k + 2] = xt.appearance[(size_t)k];
+      }
+      if (normalizer) normalizer[k] = xt.normalizer[(size_t)k];
+    }
+    auto ids = [&](const std::vector<int>& from, int* to) {
+      if (to) std::copy(from.begin(), from.begin() + std::min((long)from.size(), (long)object_capacity), to);
+    };
+    ids(xt.mesh_texture, mesh_texture);
+    ids(xt.triangle_texture, triangle_texture);
+    ids(xt.sphere_texture, sphere_texture);
+    const long pairs = (long)(xt.uv.size() / 2);
+    if (uv2) std::copy(xt.uv.begin(), xt.uv.begin() + 2 * std::min(pairs, (long)uv_capacity), uv2);
+    if (counts5) {
+      counts5[0] = nt;
+      counts5[1] = (int)xt.mesh_texture.size();
+      counts5[2] = (int)xt.triangle_texture.size();
+      counts5[3] = (int)xt.sphere_texture.size();
+      counts5[4] = (int)pairs;
+    }
+    return RT_OK;
+  });
+}
+
+int rt_scene_num_textures(const rt_scene* s) { return s ? (int)s->host.textures.size() : 0; }
+
+// rt_texture_lookup*' argument rules (those of the other query entries); they need no GPU.
+static void check_tex_lookup_args(const char* fn, const rt_scene* s, const void* q, long long n,
+                                  const void* rgb) {
+  const std::string f(fn);
+  if (n < 0) throw std::invalid_argument(f + ": n < 0");
+  if (n > 0 && (!q || !rgb)) throw std::invalid_argument(f + ": NULL pointer");
+  if ((uintptr_t)q % 16 != 0) throw std::invalid_argument(f + ": q must be 16-byte aligned");
+  if (!s) throw std::invalid_argument(f + ": scene is NULL");
+  if (s->multi) throw std::domain_error(f + ": multi-device scenes are not supported");
+}
+
+int rt_texture_lookup_device(rt_scene* s, const rt_tex_query* d_q, long long n, float* d_rgb,
+                             void* stream) {
+  return guarded([&] {
+    check_tex_lookup_args("rt_texture_lookup_device", s, d_q, n, d_rgb);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    hip_check(launch_texture_lookup(r.tex, TexLookupParams{d_q, d_rgb, n}, (hipStream_t)stream),
+              "texture lookup launch");
+    return RT_OK;
+  });
+}
+
+int rt_texture_lookup(rt_scene* s, const rt_tex_query* q, long long n, float* rgb) {
+  return guarded([&] {
+    check_tex_lookup_args("rt_texture_lookup", s, q, n, rgb);
+    if (n == 0) return RT_OK;
+    Replica& r = *s->rep[0];
+    DeviceGuard g(r.device);
+    CtxLease lease(s, 1);
+    RenderCtx* x = lease.x[0];
+    // the 16-B queries in the ray buffer (32-B records), the 12-B results in the position buffer
+    x->d_rays.reserve(((size_t)n + 1) / 2, "alloc texture queries");
+    x->d_xy.reserve(3 * (size_t)n, "alloc texture colours");
+    hip_check(hipMemcpyAsync(x->d_rays.p, q, (size_t)n * sizeof(rt_tex_query),
+                             hipMemcpyHostToDevice, x->stream), "upload texture queries");
+    hip_check(launch_texture_lookup(r.tex, TexLookupParams{x->d_rays.p, x->d_xy.p, n}, x->stream),
+              "texture lookup launch");
+    hip_check(hipMemcpyAsync(rgb, x->d_xy.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
+                             x->stream), "download texture colours");
+    hip_check(hipStreamSynchronize(x->stream), "synchronize texture lookup");
+    return RT_OK;
+  });
+}
+
+int rt_host_texture_lookup_desc(const rt_texture_desc* textures, const rt_tex_query* q, long long n,
+                                float* rgb) {
+  return guarded([&] {
+    if (!textures) throw std::invalid_argument("rt_host_texture_lookup_desc: textures == NULL");
+    if (n < 0) throw std::invalid_argument("rt_host_texture_lookup_desc: n < 0");
+    if (n > 0 && (!q || !rgb)) throw std::invalid_argument("rt_host_texture_lookup_desc: NULL pointer");
+    std::vector<DevTexture> table;
+    std::vector<uint32_t> texels;
+    pack_textures(*textures, table, texels);
+    host_texture_lookup(table, texels, q, n, rgb);
+    return RT_OK;
+  });
+}
 
 int rt_instances_version(void) { return 1; }
 

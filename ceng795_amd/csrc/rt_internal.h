@@ -619,6 +619,104 @@ struct SurfArg {};
 template <>
 struct SurfArg<true> : SurfParams {};
 
+// Image textures (rt_scene_create_textured).  A textured scene always has the
+// per-leaf record of SurfParams::tri; a leaf's texture id + 1 sits in its flags word above the
+// smooth bit (0: no texture), on sphere leaves too.  The texels of every texture lie in one blob,
+// 4 bytes per texel (R, G, B in the low three bytes), rows of `w` texels, top row first.
+// TexArg<TEX> is what the ray-tree code takes beside SurfArg<true>: nothing in the other
+// instantiations.
+constexpr int kSurfTexShift = 1;  // leaf flags >> kSurfTexShift: texture id + 1
+enum : int32_t { kTexNearest = 0, kTexBilinear = 1 };                     // RT_TEX_NEAREST ...
+enum : int32_t { kTexReplaceKd = 0, kTexBlendKd = 1, kTexReplaceAll = 2 };  // RT_TEX_REPLACE_KD ...
+enum : int32_t { kTexRepeat = 0, kTexClamp = 1 };                         // RT_TEX_REPEAT ...
+constexpr int kTexMaxSide = 16384;
+struct alignas(16) DevTexture {
+  uint32_t offset;  // of its first texel in the blob
+  int32_t w, h;
+  int32_t interpolation, decal, appearance;
+  float normalizer;
+  int32_t pad;
+};
+static_assert(sizeof(DevTexture) == 32, "texture record is two 16-byte words");
+struct TexParams {
+  const DevTexture* table;
+  const uint32_t* texels;
+  int num_textures;
+  int blank_material;  // a material the host appends: no mirror, no transparency (REPLACE_ALL hits)
+};
+template <bool TEX>
+struct TexArg {};
+template <>
+struct TexArg<true> : TexParams {};
+
+// Texture::get_color_at(u, v) (HW4/src/Texture.cpp:57-134) restated line for line: raw channel
+// values 0..255 as floats.  All fp32, every product and sum rounded (every file that includes this
+// compiles with contraction off); fmin / fmax return the operand that is not NaN, so a NaN
+// coordinate becomes 1.  One departure: a term of the clamped bilinear form whose linear texel
+// index lies at or past w * h — where the reference reads past its buffer — is skipped.  One
+// definition for the device's ray trees and lookups and the host's lookup.
+RT_HD inline void tex_get_color(const DevTexture& T, const uint32_t* texels, float u, float v,
+                                float rgb[3]) {
+  if (T.appearance == kTexClamp) {  // :58-60
+    u = __builtin_fmaxf(0.0f, __builtin_fminf(1.0f, u));
+    v = __builtin_fmaxf(0.0f, __builtin_fminf(1.0f, v));
+  } else {  // :62-63
+    u = __builtin_fmaxf(0.0f, __builtin_fminf(1.0f, u - __builtin_floorf(u)));
+    v = __builtin_fmaxf(0.0f, __builtin_fminf(1.0f, v - __builtin_floorf(v)));
+  }
+  const float fw = (float)T.w, fh = (float)T.h;
+  u = u * fw;  // :65-68
+  if (u >= fw) u = u - 1.0f;
+  v = v * fh;
+  if (v >= fh) v = v - 1.0f;
+  const uint32_t w = (uint32_t)T.w, h = (uint32_t)T.h;
+  const uint32_t* tx = texels + T.offset;
+  auto channel = [](uint32_t texel, int c) { return (float)((texel >> (8 * c)) & 255u); };
+  if (T.interpolation == kTexNearest) {  // :71-74
+    const uint32_t t = tx[w * (uint32_t)v + (uint32_t)u];
+    for (int c = 0; c < 3; c++) rgb[c] = channel(t, c);
+    return;
+  }
+  if (T.appearance == kTexRepeat) {  // :77-100
+    const uint32_t p = (uint32_t)u % w, pn = (p + 1) % w;
+    const uint32_t q = (uint32_t)v % h, qn = (q + 1) % h;
+    const float dx = u - (float)p, dy = v - (float)q;
+    const uint32_t t00 = tx[w * q + p], t10 = tx[w * q + pn], t11 = tx[w * qn + pn],
+                   t01 = tx[w * qn + p];
+    for (int c = 0; c < 3; c++) {
+      float x = channel(t00, c) * (1.0f - dx) * (1.0f - dy);
+      x += channel(t10, c) * dx * (1.0f - dy);
+      x += channel(t11, c) * dx * dy;
+      x += channel(t01, c) * (1.0f - dx) * dy;
+      rgb[c] = x;
+    }
+    return;
+  }
+  // :102-129: the reference's guards, texels by linear index
+  const uint32_t p = (uint32_t)u, pn = p + 1, q = (uint32_t)v, qn = (uint32_t)(v + 1.0f);
+  const float dx = u - (float)p, dy = v - (float)q;
+  const uint32_t count = w * h;
+  const bool g10 = pn < w, g11 = qn < h && w * qn + pn < count, g01 = pn < w && qn < h;
+  const uint32_t t00 = tx[w * q + p];
+  const uint32_t t10 = g10 ? tx[w * q + pn] : 0u;
+  const uint32_t t11 = g11 ? tx[w * qn + pn] : 0u;
+  const uint32_t t01 = g01 ? tx[w * qn + p] : 0u;
+  for (int c = 0; c < 3; c++) {
+    float x = channel(t00, c) * (1.0f - dx) * (1.0f - dy);
+    if (g10) x += channel(t10, c) * dx * (1.0f - dy);
+    if (g11) x += channel(t11, c) * dx * dy;
+    if (g01) x += channel(t01, c) * (1.0f - dx) * dy;
+    rgb[c] = x;
+  }
+}
+
+// rt_texture_lookup*: q holds n rt_tex_query records (16 B), rgb 3 n floats.
+struct TexLookupParams {
+  const void* q;
+  float* rgb;
+  long long n;
+};
+
 // Instanced scenes (rt_scene_create_instanced).  The top-level reference tree
 // (top_nodes, DevNode records whose leaf children are ~top-level DFS position) holds the
 // instances and the loose primitives; top_prims[pos] is the loose primitive at that position, or

@@ -442,6 +442,94 @@ __device__ __forceinline__ V3 triangle_normal(const SurfArg<SMOOTH>& S, const De
 // a build without surface data, and one SurfArg<true> in the SMOOTH ones.
 __device__ __forceinline__ SurfArg<false> surf_of() { return {}; }
 __device__ __forceinline__ const SurfArg<true>& surf_of(const SurfArg<true>& s) { return s; }
+// ... and in the TEX ones a TexArg<true> after it.
+__device__ __forceinline__ const SurfArg<true>& surf_of(const SurfArg<true>& s, const TexArg<true>&) {
+  return s;
+}
+__device__ __forceinline__ TexArg<false> tex_of() { return {}; }
+__device__ __forceinline__ TexArg<false> tex_of(const SurfArg<true>&) { return {}; }
+__device__ __forceinline__ const TexArg<true>& tex_of(const SurfArg<true>&, const TexArg<true>& t) {
+  return t;
+}
+
+// ------------------------------------------------------------------ textures
+// Image textures.  Both functions are out of line, as phong_pow_f64 is: they
+// run once per hit after the walk, and inlined into the 20 TEX instantiations ocml's fp64 acos and
+// atan2 and the lookup's four cases would set those kernels' register budgets and build time.
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// Sphere.cpp:100-105: (u, v) of the point center + lc on a sphere of `radius`.
+__device__ __attribute__((noinline)) f2 sphere_uv_f64(float lx, float ly, float lz, float radius) {
+  const float theta = (float)acos((double)(ly / radius));
+  const float phi = (float)atan2((double)lz, (double)lx);
+  f2 uv;
+  uv.x = (float)((M_PI - (double)phi) / (2 * M_PI));
+  uv.y = (float)((double)theta / M_PI);
+  return uv;
+}
+
+// Texture::get_color_at of texture `id` (in range: the host checked the leaf records): the raw
+// colour, and in w the texture's decal mode.
+__device__ __attribute__((noinline)) f4 tex_color(const DevTexture* __restrict__ table,
+                                                  const uint32_t* __restrict__ texels, int id,
+                                                  float u, float v) {
+  const DevTexture T = table[id];
+  float rgb[3];
+  tex_get_color(T, texels, u, v, rgb);
+  return (f4){rgb[0], rgb[1], rgb[2], __int_as_float(T.decal)};
+}
+
+// Hit_data of a hit on `leaf` in a textured scene: the normal as triangle_normal / the sphere rule
+// give it, and HW4's texture step (HW4/src/Scene.cpp:154-170).  kd: the diffuse colour the light
+// loops take — the material's, or on a textured leaf tex / normalizer (REPLACE_KD) or
+// ((tex / normalizer) + kd) / 2 (BLEND_KD).  all: a REPLACE_ALL texture; kd is then the raw texel,
+// the ray's whole colour.  One tri_barycentrics serves the smooth normal and the (u, v) of
+// Mesh_triangle.cpp:107-111.
+__device__ __forceinline__ void textured_hit(const SurfArg<true>& S, const TexArg<true>& X,
+                                             const DevPrim& pr, int leaf, const LaneRay& r, V3 p,
+                                             V3 flat, const DevMaterial* __restrict__ mats, V3& n,
+                                             V3& kd, bool& all) {
+  const i4 tr = reinterpret_cast<const i4*>(S.tri)[leaf];
+  const int id = (tr.w >> kSurfTexShift) - 1;
+  float u = 0.0f, v = 0.0f;
+  if (pr.kind == kPrimTriangle) {
+    n = flat;
+    if ((tr.w & kSurfSmooth) || id >= 0) {
+      float beta, gamma;
+      tri_barycentrics(pr, r, beta, gamma);
+      if (tr.w & kSurfSmooth) n = smooth_normal(S, tr, beta, gamma);
+      if (id >= 0) {
+        const f2* uv = reinterpret_cast<const f2*>(S.uv);
+        const f2 a = uv[tr.x], b = uv[tr.y], c = uv[tr.z];
+        u = (a.x + beta * (b.x - a.x)) + gamma * (c.x - a.x);
+        v = (a.y + beta * (b.y - a.y)) + gamma * (c.y - a.y);
+      }
+    }
+  } else {
+    const V3 lc = p - ld3(pr.v0);
+    n = normalize(lc);
+    if (id >= 0) {
+      const f2 s = sphere_uv_f64(lc.x, lc.y, lc.z, pr.a1[0]);
+      u = s.x;
+      v = s.y;
+    }
+  }
+  kd = ld3(mats[pr.material].diffuse);
+  all = false;
+  if (id >= 0) {
+    const f4 c = tex_color(X.table, X.texels, id, u, v);
+    const V3 tex = v3(c.x, c.y, c.z);
+    const int decal = __float_as_int(c.w);
+    if (decal == kTexReplaceAll) {
+      all = true;
+      kd = tex;
+    } else {
+      const float nz = X.table[id].normalizer;
+      const V3 tc = v3(tex.x / nz, tex.y / nz, tex.z / nz);
+      kd = decal == kTexBlendKd ? (tc + kd) / 2.0f : tc;
+    }
+  }
+}
 
 // ------------------------------------------------------------------ traversal stack
 // Wave-uniform (node, lane-mask) entries.  DEEP == false: entry i lives in VGPR lane i
@@ -2358,16 +2446,25 @@ __device__ __forceinline__ bool inst_occluded(const RenderParams& P, const InstA
 // not finite is absent; a light no shading lane of the wave has is skipped wave-wide.  A record
 // with a non-zero normal is a sample of an emitter: both terms carry dot(-w_i, normal)
 // (HW3/src/Scene.cpp:207-218), chosen per lane behind a select.
-template <bool FAST, bool DEEP, bool SPHERES, bool LIT = false, typename Inst = NoInst>
+// TEX: `kd` is the lane's diffuse colour in place of the material's.
+template <bool FAST, bool DEEP, bool SPHERES, bool LIT = false, typename Inst = NoInst,
+          bool TEX = false>
 __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* __restrict__ nodes,
                                           const DevPrim* __restrict__ prims,
                                           const DevMaterial* __restrict__ mats,
                                           const DevLight* __restrict__ lights, int* spill, WaveLeafLds& L,
                                           bool shade, V3 o, V3 p, V3 n, int mat, Diag& dg,
                                           unsigned long long& shadow_rays, const f4* own = nullptr,
-                                          int own_k = 0, const Inst& inst = Inst{}) {
+                                          int own_k = 0, const Inst& inst = Inst{},
+                                          [[maybe_unused]] V3 kd = V3{}) {
   V3 color = v3(0.0f, 0.0f, 0.0f);
   const DevMaterial& m = mats[shade ? mat : 0];
+  auto diffuse = [&]() {
+    if constexpr (TEX)
+      return kd;
+    else
+      return ld3(m.diffuse);
+  };
   if (shade) color = color + ld3(m.ambient) * ld3(P.ambient);
   const V3 w0 = shade ? normalize(o - p) : v3(0, 0, 0);
   for (int li = 0; li < P.num_lights; li++) {
@@ -2390,7 +2487,7 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
     if (shade && !occ) {
       const V3 I = ld3(lt.intensity);
       const float d2 = dist * dist;
-      color = color + ((ld3(m.diffuse) * I) * dot(n, wi)) / d2;
+      color = color + ((diffuse() * I) * dot(n, wi)) / d2;
       const float cos_s = __builtin_fmaxf(dot(n, normalize(w0 + wi)), 0.0f);
       const float pw = (float)pow((double)cos_s, (double)m.phong_exponent);
       color = color + ((ld3(m.specular) * I) * pw) / d2;
@@ -2427,7 +2524,7 @@ __device__ __forceinline__ V3 local_color(const RenderParams& P, const DevNode* 
         const bool point = (en.x == 0.0f) & (en.y == 0.0f) & (en.z == 0.0f);
         const float ic = dot(v3(-wi.x, -wi.y, -wi.z), en);
         const float d2 = dist * dist;
-        const V3 kd = ld3(m.diffuse) * I, ks = ld3(m.specular) * I;
+        const V3 kd = diffuse() * I, ks = ld3(m.specular) * I;
         color = color + ((point ? kd : kd * ic) * dot(n, wi)) / d2;
         const float cos_s = __builtin_fmaxf(dot(n, normalize(w0 + wi)), 0.0f);
         // the same (float)pow((double), (double)), out of line: a second inlined copy costs the
@@ -2456,8 +2553,10 @@ struct TreeCounts {
 // LIT: the lane's own light records join every local shading of its tree (local_color).
 // SMOOTH: the scene has a smooth mesh; a hit on one of its faces takes the interpolated vertex
 // normal (triangle_normal) wherever Hit_data::normal is read.
+// TEX: the scene has textures (SPHERES and SMOOTH are then both set, the leaf's flags deciding);
+// a hit on a textured leaf takes HW4's texture step (textured_hit).
 template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE = true, bool LIT = false,
-          bool SMOOTH = false, typename Inst = NoInst>
+          bool SMOOTH = false, typename Inst = NoInst, bool TEX = false>
 __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* __restrict__ nodes,
                                          const DevPrim* __restrict__ prims,
                                          const float* __restrict__ normals,
@@ -2467,7 +2566,9 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
                                          bool medium, int depth, bool active, float& t_first,
                                          TreeCounts& cnt, const SurfArg<SMOOTH>& surf,
                                          const f4* own = nullptr, int own_k = 0,
-                                         const Inst& inst = Inst{}) {
+                                         const Inst& inst = Inst{},
+                                         [[maybe_unused]] const TexArg<TEX>& tex = TexArg<TEX>{}) {
+  static_assert(!TEX || (SPHERES && SMOOTH && !Inst::on), "TEX: flat scenes, SPHERES and SMOOTH set");
   auto frame = [&](int level) {
     return FrameRef{frames + (size_t)level * kFrFields * stride, stride};
   };
@@ -2500,9 +2601,15 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
     first = false;
     V3 p = v3(0, 0, 0), n = v3(0, 0, 0);
     int mat = 0;
+    [[maybe_unused]] V3 kd = v3(0, 0, 0);   // TEX: the hit's diffuse colour, or its REPLACE_ALL texel
+    [[maybe_unused]] bool replace_all = false;
     if (hit) {
       p = ray.o + ray.d * t;
-      if constexpr (Inst::motion) {
+      if constexpr (TEX) {
+        const DevPrim& pr = prims[leaf];
+        textured_hit(surf, tex, pr, leaf, ray, p, ld3(normals + 4 * leaf), mats, n, kd, replace_all);
+        mat = replace_all ? tex.blank_material : pr.material;
+      } else if constexpr (Inst::motion) {
         const MotionHit h = motion_hit(inst.T, inst.M, ray, inst.tau, t, leaf, mesh_leaf);
         n = h.n;
         mat = h.material;
@@ -2525,9 +2632,17 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
         mat = pr.material;
       }
     }
-    const V3 local = local_color<FAST, DEEP, SPHERES, LIT, Inst>(
-        P, nodes, prims, mats, lights, spill, L, hit && !medium, ray.o, p, n, mat, dg, n_shadow, own,
-        own_k, inst);
+    V3 local;
+    if constexpr (TEX) {  // a REPLACE_ALL hit is its texel and nothing else (Scene.cpp:156-159)
+      local = local_color<FAST, DEEP, SPHERES, LIT, Inst, true>(
+          P, nodes, prims, mats, lights, spill, L, hit && !medium && !replace_all, ray.o, p, n, mat,
+          dg, n_shadow, own, own_k, inst, kd);
+      if (replace_all) local = kd;
+    } else {
+      local = local_color<FAST, DEEP, SPHERES, LIT, Inst>(
+          P, nodes, prims, mats, lights, spill, L, hit && !medium, ray.o, p, n, mat, dg, n_shadow,
+          own, own_k, inst);
+    }
     if constexpr (!RECURSE) {  // the one ray of the tree (a miss: Scene.cpp:96-99)
       if (hit)
         out = local;
@@ -2660,7 +2775,7 @@ __device__ __forceinline__ V3 trace_tree(const RenderParams& P, const DevNode* _
   return out;
 }
 
-template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename Inst = NoInst>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename Inst = NoInst, bool TEX = false>
 __device__ __forceinline__ void recursive_packet(const RenderParams& P,
                                                  const DevNode* __restrict__ nodes,
                                                  const DevPrim* __restrict__ prims,
@@ -2669,7 +2784,8 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
                                                  const DevLight* __restrict__ lights, int sel,
                                                  int* spill, WaveLeafLds& L,
                                                  const SurfArg<SMOOTH>& surf,
-                                                 const Inst& inst = Inst{}) {
+                                                 const Inst& inst = Inst{},
+                                                 const TexArg<TEX>& tex = TexArg<TEX>{}) {
   const PacketPixel q = packet_pixel(P, sel);
   const size_t lanes_total = (size_t)P.num_sel_tiles * (kTile * kTile);
   const size_t g = (size_t)sel * (kTile * kTile) + q.lane;
@@ -2677,9 +2793,10 @@ __device__ __forceinline__ void recursive_packet(const RenderParams& P,
   float t_first;
   TreeCounts cnt;
   // the camera's pixel ray at the scene's maximum depth
-  const V3 out = trace_tree<FAST, DEEP, SPHERES, true, false, SMOOTH, Inst>(
+  const V3 out = trace_tree<FAST, DEEP, SPHERES, true, false, SMOOTH, Inst, TEX>(
       P, nodes, prims, normals, mats, lights, spill, L, P.frames + g, lanes_total, ld3(P.cam_e),
-      primary_dir(P, q.px, q.py), false, P.max_depth, q.valid, t_first, cnt, surf, nullptr, 0, inst);
+      primary_dir(P, q.px, q.py), false, P.max_depth, q.valid, t_first, cnt, surf, nullptr, 0, inst,
+      tex);
   const unsigned long long n_hits = cnt.hits, n_shadow = cnt.shadow, n_secondary = cnt.secondary;
   if (q.valid) {
     float* o;
@@ -3000,19 +3117,21 @@ __global__ __launch_bounds__(kTraceWaves * 64) RT_FRAME_OCCUPANCY void trace_fra
   TL_END(0);
 }
 
-template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, typename... Surf>
+template <bool FAST, bool DEEP, bool SPHERES, bool SMOOTH, bool TEX, typename... Surf>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void recursive_kernel(
     RenderParams P, const DevNode* __restrict__ nodes, const DevPrim* __restrict__ prims,
     const float* __restrict__ normals, const DevMaterial* __restrict__ mats,
     const DevLight* __restrict__ lights, Surf... surf) {
-  static_assert(sizeof...(Surf) == (SMOOTH ? 1 : 0), "SMOOTH kernels take one SurfArg<true>");
+  static_assert(sizeof...(Surf) == (TEX ? 2 : SMOOTH ? 1 : 0),
+                "SMOOTH kernels take one SurfArg<true>, TEX kernels a TexArg<true> after it");
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kWavesPerBlock];
   const int sel = packet_index<kWavesPerBlock>();
   if (sel >= P.num_sel_tiles) return;
   int* spill = DEEP ? deep_stack + ((int)threadIdx.x >> 6) * kDeepWords * kDeepStack : nullptr;
-  recursive_packet<FAST, DEEP, SPHERES, SMOOTH>(P, nodes, prims, normals, mats, lights, sel, spill,
-                                                leaf_lds[threadIdx.x >> 6], surf_of(surf...));
+  recursive_packet<FAST, DEEP, SPHERES, SMOOTH, NoInst, TEX>(
+      P, nodes, prims, normals, mats, lights, sel, spill, leaf_lds[threadIdx.x >> 6],
+      surf_of(surf...), NoInst{}, tex_of(surf...));
 }
 
 // recursive_kernel for an instanced scene: the same packets and ray trees, every
@@ -3140,6 +3259,15 @@ static void with_surface(const SurfParams* surf, F&& f) {
     f(std::false_type{});
   }
 }
+// The two trailing arguments of a TEX launch (a textured scene always has surface data).
+struct TexLaunch {
+  SurfArg<true> surf;
+  TexArg<true> tex;
+  TexLaunch(const SurfParams& s, const TexParams& t) {
+    static_cast<SurfParams&>(surf) = s;
+    static_cast<TexParams&>(tex) = t;
+  }
+};
 
 // Tests only (rt_test_visit_time_exp): when on, every frame launch takes 2^E = the largest power
 // of two not above 2^rel times the root box's diagonal, instead of visit_time_exp's — far too
@@ -3164,17 +3292,24 @@ static int test_visit_time_exp(const RenderParams& P, int e) {
 
 template <bool FAST, bool DEEP, bool SPHERES>
 static void launch_variant(const RenderParams& P, int blocks, const hipEvent_t* marks,
-                           const SurfParams* surf, hipStream_t stream) {
+                           const SurfParams* surf, const TexParams* tex, hipStream_t stream) {
   const DevNode* nodes = P.nodes;
   const DevLight* lights = P.lights;
   if (P.frames) {  // recursive scenes: one kernel walks each pixel's ray tree
     const size_t lds = deep_lds_bytes<DEEP>(kWavesPerBlock);
     mark(marks, 0, stream);
-    with_surface(surf, [&](auto sm, auto... arg) {
-      hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, SPHERES, decltype(sm)::value>), dim3(blocks),
+    if (tex) {  // a textured scene: the TEX kernels, SPHERES and SMOOTH set whatever it holds
+      const TexLaunch a(*surf, *tex);
+      hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, true, true, true>), dim3(blocks),
                          dim3(kWavesPerBlock * 64), lds, stream, P, nodes, P.prims, P.normals,
-                         P.materials, lights, arg...);
-    });
+                         P.materials, lights, a.surf, a.tex);
+    } else {
+      with_surface(surf, [&](auto sm, auto... arg) {
+        hipLaunchKernelGGL((recursive_kernel<FAST, DEEP, SPHERES, decltype(sm)::value, false>),
+                           dim3(blocks), dim3(kWavesPerBlock * 64), lds, stream, P, nodes, P.prims,
+                           P.normals, P.materials, lights, arg...);
+      });
+    }
     mark(marks, 1, stream);
     mark(marks, 2, stream);
     mark(marks, 3, stream);
@@ -3684,13 +3819,15 @@ constexpr int kRadianceWaves = RT_RADIANCE_WAVES;
 // LIT (rt_shade_rays_lit_device): the ray's own light records, found by the
 // ray's index in the caller's batch (its result slot), not by its place in the chunk or in the
 // reordered order; shared records sit at index 0 for every ray.  LitArg<false> is empty.
-template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE, bool LIT, bool SMOOTH, typename... Surf>
+template <bool FAST, bool DEEP, bool SPHERES, bool RECURSE, bool LIT, bool SMOOTH, bool TEX,
+          typename... Surf>
 __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void query_radiance_kernel(
     RenderParams P, QueryParams Q, RadianceParams R, const DevNode* __restrict__ nodes,
     const DevPrim* __restrict__ prims, const float* __restrict__ normals,
     const DevMaterial* __restrict__ mats, const DevLight* __restrict__ lights, LitArg<LIT> lit,
     Surf... surf) {
-  static_assert(sizeof...(Surf) == (SMOOTH ? 1 : 0), "SMOOTH kernels take one SurfArg<true>");
+  static_assert(sizeof...(Surf) == (TEX ? 2 : SMOOTH ? 1 : 0),
+                "SMOOTH kernels take one SurfArg<true>, TEX kernels a TexArg<true> after it");
   extern __shared__ __attribute__((aligned(16))) int deep_stack[];
   __shared__ WaveLeafLds leaf_lds[kRadianceWaves];
   const long long slot = (long long)blockIdx.x * (kRadianceWaves * 64) + threadIdx.x;  // in the chunk
@@ -3709,10 +3846,10 @@ __global__ __launch_bounds__(kRadianceWaves * 64) RT_RADIANCE_OCCUPANCY void que
     own = reinterpret_cast<const f4*>(lit.lights) + 3 * (size_t)ray * (size_t)lit.k;
     own_k = lit.k;
   }
-  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE, LIT, SMOOTH>(
+  const V3 c = trace_tree<FAST, DEEP, SPHERES, RECURSE, LIT, SMOOTH, NoInst, TEX>(
       P, nodes, prims, normals, mats, lights, spill, L, RECURSE ? R.frames + slot : nullptr,
       (size_t)R.lanes, q.o, q.d, R.in_medium != 0, R.depth, q.valid, t, cnt, surf_of(surf...), own,
-      own_k);
+      own_k, NoInst{}, tex_of(surf...));
   if (i < Q.n) {
     // Pixel::add_color(color, 1) onto a zeroed pixel; an invalid ray: (0, 0, 0, +inf)
     const f4 out = {0.0f + c.x, 0.0f + c.y, 0.0f + c.z, t};
@@ -4055,7 +4192,7 @@ hipError_t launch_query_sort(QueryParams Q, hipStream_t stream) {
 hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const RadianceParams& R,
                            const LitParams* lit, const DevNode* nodes, bool fast, bool deep,
                            bool spheres, const SurfParams* surf, const InstParams* inst,
-                           const MotionParams* motion, hipStream_t stream) {
+                           const MotionParams* motion, const TexParams* tex, hipStream_t stream) {
   if (Q.n <= R.first) return hipSuccess;
   const dim3 grid((unsigned)((Q.n - R.first + kRadianceWaves * 64 - 1) / (kRadianceWaves * 64)));
   if (inst && motion) {  // a scene with motion: its own kernels
@@ -4111,11 +4248,18 @@ hipError_t launch_radiance(const RenderParams& P, const QueryParams& Q, const Ra
     const size_t lds = deep_lds_bytes<D>(kRadianceWaves);
     auto launch = [&](auto re, auto li, auto arg) {
       constexpr bool RE = decltype(re)::value, LI = decltype(li)::value;
-      with_surface(surf, [&](auto sm, auto... sarg) {
-        hipLaunchKernelGGL((query_radiance_kernel<F, D, S, RE, LI, decltype(sm)::value>), grid,
+      if (tex) {  // a textured scene: the TEX kernels, SPHERES and SMOOTH set whatever it holds
+        const TexLaunch a(*surf, *tex);
+        hipLaunchKernelGGL((query_radiance_kernel<F, D, true, RE, LI, true, true>), grid,
                            dim3(kRadianceWaves * 64), lds, stream, P, Q, R, nodes, P.prims,
-                           P.normals, P.materials, P.lights, arg, sarg...);
-      });
+                           P.normals, P.materials, P.lights, arg, a.surf, a.tex);
+      } else {
+        with_surface(surf, [&](auto sm, auto... sarg) {
+          hipLaunchKernelGGL((query_radiance_kernel<F, D, S, RE, LI, decltype(sm)::value, false>),
+                             grid, dim3(kRadianceWaves * 64), lds, stream, P, Q, R, nodes, P.prims,
+                             P.normals, P.materials, P.lights, arg, sarg...);
+        });
+      }
     };
     using T = std::true_type;
     using N = std::false_type;
@@ -4202,6 +4346,35 @@ hipError_t launch_hit_attributes(const RenderParams& P, const SurfParams& S, con
     C.n = A.n - done < kQueryMaxLaunch ? A.n - done : kQueryMaxLaunch;
     hipLaunchKernelGGL(hit_attr_kernel, dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, stream,
                        P, S, C);
+  }
+  return hipGetLastError();
+}
+
+// rt_texture_lookup* (DESIGN.md §4.18): a lane per query, one 16-B load, tex_get_color as the ray
+// trees run it, three stores.  A texture id outside [0, X.num_textures) gives 0 0 0 and reads
+// nothing.
+__global__ __launch_bounds__(256) void tex_lookup_kernel(TexParams X, TexLookupParams A) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  const f4 q = reinterpret_cast<const f4*>(A.q)[i];
+  const int id = __float_as_int(q.x);
+  float rgb[3] = {0.0f, 0.0f, 0.0f};
+  if (id >= 0 && id < X.num_textures) tex_get_color(X.table[id], X.texels, q.y, q.z, rgb);
+  float* o = A.rgb + 3 * i;
+  o[0] = rgb[0];
+  o[1] = rgb[1];
+  o[2] = rgb[2];
+}
+
+hipError_t launch_texture_lookup(const TexParams& X, const TexLookupParams& A, hipStream_t stream) {
+  if (A.n <= 0) return hipSuccess;
+  for (long long done = 0; done < A.n; done += kQueryMaxLaunch) {  // (32-bit grids)
+    TexLookupParams C;
+    C.q = static_cast<const char*>(A.q) + (size_t)done * 16;
+    C.rgb = A.rgb + 3 * (size_t)done;
+    C.n = A.n - done < kQueryMaxLaunch ? A.n - done : kQueryMaxLaunch;
+    hipLaunchKernelGGL(tex_lookup_kernel, dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, stream,
+                       X, C);
   }
   return hipGetLastError();
 }
@@ -4320,8 +4493,9 @@ hipError_t launch_motion_inverse(const float* fwd, const float* vel, const float
 
 hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spheres,
                          const hipEvent_t* marks, const SurfParams* surf, const InstParams* inst,
-                         const MotionParams* motion, hipStream_t stream) {
+                         const MotionParams* motion, const TexParams* tex, hipStream_t stream) {
   if (P.num_sel_tiles <= 0) return hipSuccess;
+  if (tex && (!surf || !P.frames || inst)) return hipErrorInvalidValue;
   const int blocks = (P.num_sel_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
   if (inst && motion) {  // a scene with motion: every ray of the frame at time 0
     if (!P.frames) return hipErrorInvalidValue;
@@ -4350,7 +4524,7 @@ hipError_t launch_render(const RenderParams& P, bool fast, bool deep, bool spher
   }
   dispatch_variant(use_fast(P, fast), deep, spheres, [&](auto fa, auto de, auto sp) {
     launch_variant<decltype(fa)::value, decltype(de)::value, decltype(sp)::value>(
-        P, blocks, marks, surf, stream);
+        P, blocks, marks, surf, tex, stream);
   });
   return hipGetLastError();
 }

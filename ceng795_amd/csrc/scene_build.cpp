@@ -680,6 +680,123 @@ void build_surface(const rt_scene_desc& d, const rt_surface_desc* surf, HostScen
   if (surf->vertex_uv) s.vertex_uv.assign(surf->vertex_uv, surf->vertex_uv + 2 * nv);
 }
 
+void pack_textures(const rt_texture_desc& tex, std::vector<DevTexture>& table,
+                   std::vector<uint32_t>& texels) {
+  table.clear();
+  texels.clear();
+  if (tex.struct_size < sizeof(rt_texture_desc)) fail("rt_texture_desc::struct_size too small");
+  if (tex.num_textures < 0) fail("negative texture count");
+  if (tex.num_textures && !tex.textures) fail("textures == NULL");
+  size_t total = 0;
+  for (int k = 0; k < tex.num_textures; k++) {
+    const rt_texture& t = tex.textures[k];
+    const std::string name = "texture " + std::to_string(k);
+    if (!t.rgb8) fail(name + ": rgb8 == NULL");
+    if (t.width < 1 || t.width > kTexMaxSide || t.height < 1 || t.height > kTexMaxSide)
+      fail(name + ": width and height must lie in 1 .. " + std::to_string(kTexMaxSide));
+    if (t.interpolation != RT_TEX_NEAREST && t.interpolation != RT_TEX_BILINEAR)
+      fail(name + ": unknown interpolation");
+    if (t.decal != RT_TEX_REPLACE_KD && t.decal != RT_TEX_BLEND_KD && t.decal != RT_TEX_REPLACE_ALL)
+      fail(name + ": unknown decal mode");
+    if (t.appearance != RT_TEX_REPEAT && t.appearance != RT_TEX_CLAMP)
+      fail(name + ": unknown appearance");
+    if (!std::isfinite(t.normalizer) || t.normalizer == 0.0f)
+      fail(name + ": normalizer must be finite and not 0");
+    total += (size_t)t.width * (size_t)t.height;
+    if (total >= (size_t(1) << 31)) fail("textures of 2^31 texels or more are not supported");
+  }
+  table.reserve((size_t)tex.num_textures);
+  texels.reserve(total);
+  for (int k = 0; k < tex.num_textures; k++) {
+    const rt_texture& t = tex.textures[k];
+    DevTexture d{};
+    d.offset = (uint32_t)texels.size();
+    d.w = t.width;
+    d.h = t.height;
+    d.interpolation = t.interpolation;
+    d.decal = t.decal;
+    d.appearance = t.appearance;
+    d.normalizer = t.normalizer;
+    table.push_back(d);
+    const size_t count = (size_t)t.width * (size_t)t.height;
+    for (size_t i = 0; i < count; i++) {
+      const unsigned char* p = t.rgb8 + 3 * i;
+      texels.push_back((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+    }
+  }
+}
+
+void host_texture_lookup(const std::vector<DevTexture>& table, const std::vector<uint32_t>& texels,
+                         const rt_tex_query* q, long long n, float* rgb) {
+  for (long long i = 0; i < n; i++) {
+    float* o = rgb + 3 * i;
+    o[0] = o[1] = o[2] = 0.0f;
+    if (q[i].texture >= 0 && q[i].texture < (int)table.size())
+      tex_get_color(table[(size_t)q[i].texture], texels.data(), q[i].u, q[i].v, o);
+  }
+}
+
+void build_textures(const rt_scene_desc& d, const rt_surface_desc* surf,
+                    const rt_texture_desc* tex, HostScene& s) {
+  s.textures.clear();
+  s.texels.clear();
+  s.blank_material = -1;
+  if (!tex) return;
+  std::vector<DevTexture> table;
+  std::vector<uint32_t> texels;
+  pack_textures(*tex, table, texels);
+  const bool has_uv = surf && surf->vertex_uv;
+  bool any = false;
+  auto ids = [&](const int* list, int count, const char* what, bool needs_uv) {
+    if (!list) return;
+    for (int k = 0; k < count; k++) {
+      if (list[k] < -1 || list[k] >= tex->num_textures)
+        fail(std::string(what) + ": texture id out of range");
+      if (list[k] >= 0) {
+        if (needs_uv && !has_uv)
+          fail(std::string(what) + ": a textured mesh or triangle needs surface->vertex_uv");
+        any = true;
+      }
+    }
+  };
+  ids(tex->mesh_texture, d.num_meshes, "mesh_texture", true);
+  ids(tex->triangle_texture, d.num_triangles, "triangle_texture", true);
+  ids(tex->sphere_texture, d.num_spheres, "sphere_texture", false);
+  if (!any) return;  // exactly rt_scene_create_surface's scene
+  long long faces = 0;
+  std::vector<long long> mesh_end;
+  for (int m = 0; m < d.num_meshes; m++) {
+    faces += d.mesh_face_count[m];
+    mesh_end.push_back(faces);
+  }
+  const bool fresh = s.leaf_tri.empty();  // no surface data: only the vertex ids and the texture
+  if (fresh) s.leaf_tri.assign(4 * s.leaf_src.size(), 0);
+  for (size_t k = 0; k < s.leaf_src.size(); k++) {
+    const LeafSource& l = s.leaf_src[k];
+    int id = -1;
+    if (l.kind == kPrimTriangle) {
+      if (fresh) {
+        const int rec[3] = {l.i0, l.i1, l.i2};
+        std::memcpy(&s.leaf_tri[4 * k], rec, sizeof rec);
+      }
+      if (l.object < faces) {
+        const size_t m = std::upper_bound(mesh_end.begin(), mesh_end.end(), (long long)l.object) -
+                         mesh_end.begin();
+        if (tex->mesh_texture) id = tex->mesh_texture[m];
+      } else if (tex->triangle_texture) {
+        id = tex->triangle_texture[l.object - faces];
+      }
+    } else if (tex->sphere_texture) {
+      id = tex->sphere_texture[l.object - faces - d.num_triangles];
+    }
+    s.leaf_tri[4 * k + 3] |= (id + 1) << kSurfTexShift;
+  }
+  s.textures = std::move(table);
+  s.texels = std::move(texels);
+  s.blank_material = (int)s.materials.size();
+  s.materials.push_back(DevMaterial{});
+}
+
 std::string dump_bvh(const HostScene& s) {
   std::ostringstream os;
   auto hex = [](float f) {

@@ -7,6 +7,7 @@
 // reader (xml_dom.h).
 #include <locale.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cerrno>
 #include <climits>
@@ -317,6 +318,121 @@ void load_scene_xml(const std::string& path, XmlSceneStorage& st, rt_scene_desc&
   d.sphere_center = st.sphere_center.data();
   d.sphere_radius = st.sphere_radius.data();
   d.sphere_material = st.sphere_material.data();
+}
+
+// The texture part of a scene file (HW4/src/Scene.cpp:690-701, 761-768, 905-911, 1008-1014,
+// 1030-1077), read in a pass of its own so that load_scene_xml reads every file as before.
+void load_textures_xml(const std::string& path, XmlTextures& out) {
+  auto unsupported = [](const std::string& what) {
+    throw std::domain_error("scene xml: " + what + " is not supported in textured scenes");
+  };
+  out = XmlTextures{};
+  const std::unique_ptr<Node> root = parse_xml_file(path);
+  if (root->first("BackgroundTexture")) unsupported("<BackgroundTexture>");
+  std::stringstream ss;  // one shared stream, as the reference's
+  if (const Node* tc = root->first("TexCoordData")) {  // Scene.cpp:690-701: pairs
+    ss << node_text(tc, "TexCoordData") << std::endl;
+    float u, v;
+    while (!(ss >> u).eof()) {
+      ss >> v;
+      out.uv.insert(out.uv.end(), {u, v});
+    }
+    ss.clear();
+  }
+  if (const Node* block = root->first("Textures")) {  // Scene.cpp:1030-1077
+    for (const Node* t : block->each("Texture")) {
+      const std::string name = node_text(t->first("ImageName"), "ImageName");
+      if (name == "perlin") unsupported("the perlin texture");
+      if (t->bool_attr("bumpmap", false)) unsupported("bumpmap=\"true\"");
+      auto text = [&](const char* tag, const char* fallback) {
+        const Node* c = t->first(tag);
+        return std::string(c ? node_text(c, tag) : fallback);
+      };
+      const std::string interpolation = text("Interpolation", "bilinear");
+      const std::string decal = text("DecalMode", "blend_kd");
+      const std::string appearance = text("Appearance", "clamp");
+      ss << text("Normalizer", "255.0") << std::endl;
+      ss << text("ScalingFactor", "1.0") << std::endl;
+      float normalizer = 255.0f, scaling = 1.0f;
+      ss >> normalizer >> scaling;
+      out.image_name.push_back(name);
+      // Texture.h's to_*: anything but the named values is the last one
+      out.interpolation.push_back(interpolation == "nearest" ? RT_TEX_NEAREST : RT_TEX_BILINEAR);
+      out.decal.push_back(decal == "replace_kd" ? RT_TEX_REPLACE_KD
+                          : decal == "blend_kd" ? RT_TEX_BLEND_KD : RT_TEX_REPLACE_ALL);
+      out.appearance.push_back(appearance == "repeat" ? RT_TEX_REPEAT : RT_TEX_CLAMP);
+      out.normalizer.push_back(normalizer);
+    }
+    ss.clear();
+  }
+  const Node* objs = root->first("Objects");
+  if (!objs) throw std::runtime_error("scene xml: missing <Objects>");
+  auto texture_of = [&](const Node* object) {  // 1-based <Texture>, -1 without one
+    int id = 0;
+    if (const Node* c = object->first("Texture")) {
+      ss << node_text(c, "Texture") << std::endl;
+      ss >> id;
+    }
+    ss.clear();
+    return id - 1;
+  };
+  for (const Node* m : objs->each("Mesh")) {
+    const Node* faces = m->first("Faces");
+    if (faces && faces->attr("plyFile")) unsupported("plyFile");
+    const int id = texture_of(m);
+    // uv is kept per vertex id, so a mesh's texture coordinates must start where its vertices do
+    if (id >= 0 && faces &&
+        faces->int_attr("textureOffset", 0) != faces->int_attr("vertexOffset", 0))
+      unsupported("a textured mesh whose textureOffset differs from its vertexOffset");
+    out.mesh_texture.push_back(id);
+  }
+  for (const Node* t : objs->each("Triangle")) out.triangle_texture.push_back(texture_of(t));
+  for (const Node* s : objs->each("Sphere")) out.sphere_texture.push_back(texture_of(s));
+}
+
+void textures_from_xml(const XmlTextures& xt, const rt_scene_desc& d, const rt_texture_image* images,
+                       int num_images, std::vector<rt_texture>& records, std::vector<float>& uv,
+                       rt_texture_desc& tex) {
+  if (num_images < 0 || (num_images && !images))
+    throw std::invalid_argument("rt_scene_load_xml_textured: bad image list");
+  if ((int)xt.mesh_texture.size() != d.num_meshes ||
+      (int)xt.triangle_texture.size() != d.num_triangles ||
+      (int)xt.sphere_texture.size() != d.num_spheres)
+    throw std::runtime_error("scene xml: object lists changed between the two passes");
+  records.clear();
+  for (size_t k = 0; k < xt.image_name.size(); k++) {
+    const rt_texture_image* found = nullptr;
+    for (int i = 0; i < num_images && !found; i++)
+      if (images[i].name && xt.image_name[k] == images[i].name) found = &images[i];
+    if (!found) throw std::ios_base::failure("no image record for texture " + xt.image_name[k]);
+    records.push_back(rt_texture{found->rgb8, found->width, found->height, xt.interpolation[k],
+                                 xt.decal[k], xt.appearance[k], xt.normalizer[k]});
+  }
+  // every vertex id of a textured face needs its pair
+  const long long pairs = (long long)(xt.uv.size() / 2);
+  auto need = [&](const int* ids, size_t count) {
+    for (size_t i = 0; i < count; i++)
+      if (ids[i] >= pairs)
+        throw std::domain_error("scene xml: fewer <TexCoordData> pairs than a textured face's "
+                                "vertex ids need");
+  };
+  size_t face = 0;
+  for (int m = 0; m < d.num_meshes; m++) {
+    const size_t count = 3 * (size_t)d.mesh_face_count[m];
+    if (xt.mesh_texture[(size_t)m] >= 0) need(d.mesh_faces + face, count);
+    face += count;
+  }
+  for (int t = 0; t < d.num_triangles; t++)
+    if (xt.triangle_texture[(size_t)t] >= 0) need(d.triangle_indices + 3 * (size_t)t, 3);
+  uv.assign(2 * (size_t)std::max(0, d.num_vertices), 0.0f);
+  std::copy(xt.uv.begin(), xt.uv.begin() + (long)std::min(uv.size(), xt.uv.size()), uv.begin());
+  tex = rt_texture_desc{};
+  tex.struct_size = sizeof(rt_texture_desc);
+  tex.num_textures = (int)records.size();
+  tex.textures = records.data();
+  tex.mesh_texture = xt.mesh_texture.data();
+  tex.triangle_texture = xt.triangle_texture.data();
+  tex.sphere_texture = xt.sphere_texture.data();
 }
 
 }  // namespace rt

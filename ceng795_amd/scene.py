@@ -23,6 +23,9 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("object", np.int32), ("material", np.i
 HIT_ATTR_DTYPE = np.dtype([("beta", np.float32), ("gamma", np.float32), ("uv", np.float32, 2),
                            ("shading_normal", np.float32, 3), ("flags", np.int32),
                            ("geometric_normal", np.float32, 3), ("pad", np.int32)])
+# rt_tex_query, 16 bytes
+TEX_QUERY_DTYPE = np.dtype([("texture", np.int32), ("u", np.float32), ("v", np.float32),
+                            ("pad", np.int32)])
 # rt_radiance, 16 bytes
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
 # rt_light_sample, 48 bytes: a non-finite position = no light; normal 0 0 0 = a point light
@@ -57,6 +60,108 @@ def pack_rays(origins, directions, tmax=None, time=None) -> np.ndarray:
 
 def _time_flag(time) -> int:
     return _lib.RT_QUERY_RAY_TIME if time is not None else 0
+
+
+def texture_desc(textures, mesh_texture=None, triangle_texture=None, sphere_texture=None, counts=None):
+    """An ``rt_texture_desc`` for ``textures``, a list of dicts ``rgb8`` ((h, w, 3) uint8),
+    ``interpolation``, ``decal``, ``appearance`` (RT_TEX_* values; defaults bilinear, blend_kd,
+    clamp: the reference's) and ``normalizer`` (255), and the three per-object id lists (None:
+    no object of that kind has a texture).  ``counts``: the description's (meshes, triangles,
+    spheres), checked against the lists.  Returns (desc, the arrays it points into)."""
+    keep = []
+    recs = (_lib.rt_texture * max(1, len(textures)))()
+    for k, t in enumerate(textures):
+        px = np.ascontiguousarray(t["rgb8"], np.uint8)
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("rgb8 must be an (h, w, 3) uint8 array")
+        keep.append(px)
+        recs[k].rgb8 = px.ctypes.data_as(C.POINTER(C.c_ubyte))
+        recs[k].height, recs[k].width = int(px.shape[0]), int(px.shape[1])
+        recs[k].interpolation = int(t.get("interpolation", _lib.RT_TEX_BILINEAR))
+        recs[k].decal = int(t.get("decal", _lib.RT_TEX_BLEND_KD))
+        recs[k].appearance = int(t.get("appearance", _lib.RT_TEX_CLAMP))
+        recs[k].normalizer = float(t.get("normalizer", 255.0))
+    keep.append(recs)
+    d = _lib.rt_texture_desc()
+    d.struct_size = C.sizeof(_lib.rt_texture_desc)
+    d.num_textures = len(textures)
+    d.textures = recs
+    for i, (name, ids) in enumerate((("mesh_texture", mesh_texture),
+                                     ("triangle_texture", triangle_texture),
+                                     ("sphere_texture", sphere_texture))):
+        if ids is None:
+            continue
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if counts is not None and a.size != counts[i]:
+            raise ValueError(f"{name} must hold {counts[i]} ids")
+        keep.append(a)
+        setattr(d, name, a.ctypes.data_as(C.POINTER(C.c_int)))
+    return d, keep
+
+
+def _texture_images(images: dict):
+    """rt_texture_image records for {name: (h, w, 3) uint8 array}, and what they point into."""
+    keep = []
+    recs = (_lib.rt_texture_image * max(1, len(images)))()
+    for k, (name, px) in enumerate(images.items()):
+        px = np.ascontiguousarray(px, np.uint8)
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("an image must be an (h, w, 3) uint8 array")
+        keep.append(px)
+        recs[k].name = str(name).encode()
+        recs[k].rgb8 = px.ctypes.data_as(C.POINTER(C.c_ubyte))
+        recs[k].height, recs[k].width = int(px.shape[0]), int(px.shape[1])
+    return recs, keep
+
+
+def host_textures_xml(xml_path: str) -> dict:
+    """Host-only (rt_host_textures_xml): what the textured loader read from a scene file —
+    ``textures`` (a list of dicts: name, interpolation, decal, appearance, normalizer),
+    ``mesh_texture`` / ``triangle_texture`` / ``sphere_texture`` (0-based ids, -1: none) and ``uv``
+    (the <TexCoordData> pairs, (n, 2) float32)."""
+    path = str(xml_path).encode()
+    counts = (C.c_int * 5)()
+    check(lib().rt_host_textures_xml(path, None, None, None, 0, None, None, None, 0, None, 0,
+                                     counts))
+    nt, nm, ntri, ns, nuv = list(counts)
+    names = C.create_string_buffer(256 * max(1, nt))
+    modes = np.zeros((max(1, nt), 3), np.int32)
+    norm = np.zeros(max(1, nt), np.float32)
+    cap = max(1, nm, ntri, ns)
+    ids = [np.full(cap, -9, np.int32) for _ in range(3)]
+    uv = np.zeros((max(1, nuv), 2), np.float32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check(lib().rt_host_textures_xml(path, names, ip(modes), fp(norm), nt, ip(ids[0]), ip(ids[1]),
+                                     ip(ids[2]), cap, fp(uv), nuv, counts))
+    textures = [dict(name=names.raw[256 * k:256 * (k + 1)].split(b"\0")[0].decode(),
+                     interpolation=int(modes[k, 0]), decal=int(modes[k, 1]),
+                     appearance=int(modes[k, 2]), normalizer=float(norm[k])) for k in range(nt)]
+    return dict(textures=textures, mesh_texture=ids[0][:nm].copy(),
+                triangle_texture=ids[1][:ntri].copy(), sphere_texture=ids[2][:ns].copy(),
+                uv=uv[:nuv].copy())
+
+
+def _tex_queries(texture, u, v) -> np.ndarray:
+    u = np.asarray(u, np.float32).reshape(-1)
+    v = np.asarray(v, np.float32).reshape(-1)
+    if u.shape != v.shape:
+        raise ValueError("u and v must hold the same number of values")
+    q = _aligned(len(u), TEX_QUERY_DTYPE)
+    q["texture"] = np.broadcast_to(np.asarray(texture, np.int32), (len(u),))
+    q["u"], q["v"] = u, v
+    return q
+
+
+def host_texture_lookup(textures, texture, u, v) -> np.ndarray:
+    """rt_host_texture_lookup_desc: Texture::get_color_at of ``textures[texture]`` (a list as
+    ``Scene.create`` takes it) at (u, v) on the host, no GPU: (n, 3) float32 raw channel values;
+    a texture id out of range gives zeros."""
+    d, keep = texture_desc(textures)
+    q = _tex_queries(texture, u, v)
+    out = np.zeros((len(q), 3), np.float32)
+    check(lib().rt_host_texture_lookup_desc(C.byref(d), q.ctypes.data, len(q), out.ctypes.data))
+    return out
 
 
 def pack_lights(lights, n: int, shared: bool):
@@ -103,9 +208,16 @@ class Scene:
 
     def __init__(self, file_name: str, device: int = -1, traversal: str = "fast",
                  devices: Optional[list] = None, smooth: bool = False, instanced: bool = False,
-                 motion: bool = False):
+                 motion: bool = False, textured: bool = False, images: Optional[dict] = None):
         h = C.c_void_p()
-        if motion:  # rt_scene_load_xml_moving: also <MotionBlur> and a sphere's <Transformations>
+        if textured:  # <Textures>, <TexCoordData>, <Texture> honoured (rt_scene_load_xml_textured)
+            if instanced or motion or devices is not None:
+                raise _lib.RTError(_lib.RT_E_UNSUPPORTED, "textured scenes are single-device, "
+                                   "without instances and without motion")
+            recs, keep = _texture_images(images or {})
+            check(lib().rt_scene_load_xml_textured(str(file_name).encode(), recs, len(images or {}),
+                                                   device, C.byref(h)))
+        elif motion:  # rt_scene_load_xml_moving: also <MotionBlur> and a sphere's <Transformations>
             if smooth or devices is not None or not instanced:
                 raise _lib.RTError(_lib.RT_E_UNSUPPORTED, "scenes with motion are instanced, "
                                    "single-device and flat-shaded")
@@ -133,7 +245,8 @@ class Scene:
     def create(cls, desc, mesh_smooth=None, vertex_normals=None, vertex_uv=None,
                device: int = -1, instance_mesh=None, instance_material=None,
                instance_transform=None, instance_velocity=None, sphere_transform=None,
-               sphere_velocity=None) -> "Scene":
+               sphere_velocity=None, textures=None, mesh_texture=None, triangle_texture=None,
+               sphere_texture=None) -> "Scene":
         """A scene from an ``rt_scene_desc`` with surface data (rt_scene_create_surface):
         ``mesh_smooth`` one flag per mesh, ``vertex_normals`` (num_vertices, 3) used as given
         (None: the area-weighted normals of the HW3 loader), ``vertex_uv`` (num_vertices, 2).
@@ -144,7 +257,18 @@ class Scene:
 
         Or a scene with motion (rt_scene_create_moving): ``instance_velocity`` (n, 3),
         ``sphere_transform`` (num_spheres, 4, 4) and ``sphere_velocity`` (num_spheres, 3), each
-        optional, with or without instances."""
+        optional, with or without instances.
+
+        ``textures`` (rt_scene_create_textured, with surface data or without): a list of dicts
+        (``texture_desc``), and ``mesh_texture`` / ``triangle_texture`` / ``sphere_texture``, one
+        texture id per object, -1 for none.  Not together with instances or motion."""
+        textured = any(a is not None for a in (textures, mesh_texture, triangle_texture,
+                                               sphere_texture))
+        if textured and any(a is not None for a in (instance_mesh, instance_material,
+                                                    instance_transform, instance_velocity,
+                                                    sphere_transform, sphere_velocity)):
+            raise _lib.RTError(_lib.RT_E_UNSUPPORTED,
+                               "textures in instanced scenes or scenes with motion are not supported")
         given = [a is not None for a in (instance_mesh, instance_material, instance_transform)]
         if any(given) and not all(given):
             raise ValueError("instance_mesh, instance_material and instance_transform go together")
@@ -186,6 +310,13 @@ class Scene:
                                   "vertex_normals")
         surf.vertex_uv = arr(vertex_uv, np.float32, 2 * desc.num_vertices, C.c_float, "vertex_uv")
         h = C.c_void_p()
+        if textured:
+            td, keep_tex = texture_desc(textures or [], mesh_texture, triangle_texture,
+                                        sphere_texture,
+                                        (desc.num_meshes, desc.num_triangles, desc.num_spheres))
+            check(lib().rt_scene_create_textured(C.byref(desc), C.byref(surf), C.byref(td), device,
+                                                 C.byref(h)))
+            return cls._from_handle(h)
         check(lib().rt_scene_create_surface(C.byref(desc), C.byref(surf), device, C.byref(h)))
         return cls._from_handle(h)
 
@@ -229,6 +360,20 @@ class Scene:
     @property
     def device_count(self) -> int:
         return lib().rt_scene_device_count(self._h)
+
+    @property
+    def num_textures(self) -> int:
+        """rt_scene_num_textures: 0 for an untextured scene."""
+        return lib().rt_scene_num_textures(self._h)
+
+    def texture_lookup(self, texture, u, v) -> np.ndarray:
+        """rt_texture_lookup: Texture::get_color_at of the scene's texture ``texture`` (one id, or
+        one per query) at (u, v) on the GPU: (n, 3) float32 raw channel values; a texture id out
+        of range gives zeros."""
+        q = _tex_queries(texture, u, v)
+        out = np.zeros((len(q), 3), np.float32)
+        check(lib().rt_texture_lookup(self._h, q.ctypes.data, len(q), out.ctypes.data))
+        return out
 
     @property
     def bvh_depth(self) -> int:

@@ -955,6 +955,133 @@ int rt_host_motion_xml(const char* xml_path, float* instance_velocity3, float* s
 int rt_debug_motion_inverse(rt_scene* scene, int top_object, const float* times, long long n,
                             float* out12);
 
+/* ---- Textures: image textures on the diffuse colour inside every ray tree ----------------------
+ *
+ * New symbols within ABI 7 (test for them with CENG795_RT_HAS_TEXTURES / rt_textures_version);
+ * rt_scene_desc, rt_surface_desc, rt_ray_hit and rt_hit_attr keep their layouts.  rt_hit_attributes
+ * tells a caller with its own shading where a ray hit; these put HW4's image textures into the
+ * library's shading, so a textured floor is lit by the scene's lights and shadow rays, shows in a
+ * mirror and through glass, and feeds films and light samples.
+ *
+ *   value     HW2's Scene::trace_ray, as every entry has it, with HW4's texture step at each hit
+ *             (HW4/src/Scene.cpp:149-171, Texture.cpp:44-134): HW4's rule placed over HW2's loop,
+ *             as smooth shading is HW3's.  It is not bit parity with the HW4 program.
+ *   scenes    rt_scene_create_textured is rt_scene_create_surface with an rt_texture_desc beside
+ *             the two descriptions: the textures, and per mesh, loose triangle and sphere a texture
+ *             id (-1: none; a NULL list: none).  A NULL texture descriptor, or one in which no
+ *             object names a texture, gives exactly rt_scene_create_surface's scene, byte for byte
+ *             in every result.  Pixels are copied at creation.  Smooth meshes and the caller's own
+ *             BVH (bvh_*) combine with textures as they do with surface data.  RT_E_INVALID before
+ *             any HIP call: a short struct_size, a texture id outside [-1, num_textures), a size,
+ *             mode or normalizer out of range, a NULL rgb8, a textured mesh or loose triangle
+ *             without surface->vertex_uv (spheres need no uv).  There is no _multi, instanced or
+ *             moving variant.
+ *   (u, v)    triangle (Mesh_triangle.cpp:107-111): uva, uvb, uvc the vertex_uv of the leaf's three
+ *             vertex ids, beta and gamma those of the smooth normal above (re-derived once per hit):
+ *               u = (uva.x + beta * (uvb.x - uva.x)) + gamma * (uvc.x - uva.x),  v alike in .y
+ *             every operation a rounded fp32 operation, no contraction.  This is HW4's expression,
+ *             not the ((uv0*w) + (uv1*beta)) + (uv2*gamma) of rt_hit_attr::uv, which stays as it
+ *             is: the two can differ in the last bit.
+ *             sphere (Sphere.cpp:100-105), lc = (o + d * t) - center in fp32:
+ *               theta = (float)acos((double)(lc.y / radius)); phi = (float)atan2((double)lc.z, (double)lc.x)
+ *               u = (float)((M_PI - (double)phi) / (2 * M_PI));  v = (float)((double)theta / M_PI)
+ *             acos and atan2 are fp64 islands like pow: libm's on the host, ocml's on the device.
+ *   lookup    Texture::get_color_at(u, v), Texture.cpp:57-134, all fp32, raw channel values 0..255:
+ *             clamp: u = fmax(0, fmin(1, u)); repeat: u = fmax(0, fmin(1, u - floor(u))) (a NaN
+ *             becomes 1); u = u * width, minus 1.0f if u >= width; v alike with height.  Nearest:
+ *             texel (row (unsigned)v, column (unsigned)u).  Bilinear, repeat: p = (unsigned)u % w,
+ *             pn = (p+1) % w, q, qn alike, dx = u - p, dy = v - q; per channel
+ *             T[q][p]*(1-dx)*(1-dy) += T[q][pn]*dx*(1-dy) += T[qn][pn]*dx*dy += T[qn][p]*(1-dx)*dy,
+ *             products left to right, each += rounded.  Bilinear, clamp: p = (unsigned)u,
+ *             pn = p + 1, q = (unsigned)v, qn = (unsigned)(v + 1.0f), texels by LINEAR index
+ *             w*row + column with the reference's own guards: pn < w adds index w*q+pn;  qn < h
+ *             adds index w*qn+pn (with pn == w that is the first texel of row qn + 1: kept);
+ *             pn < w && qn < h adds index w*qn+p.  One departure: a term whose linear index is
+ *             >= w*h, where the reference reads past its buffer, is skipped.
+ *   shading   tex = lookup(u, v) at a hit on a textured object.  RT_TEX_REPLACE_ALL: the ray's
+ *             colour is tex (raw, 0..255) and nothing else — no ambient, no light, no shadow ray
+ *             counted, no mirror or refraction ray, in_medium or not (Scene.cpp:156-159); the hit
+ *             still counts as a primary hit and reports t.  Otherwise kd' = tex / normalizer per
+ *             channel (RT_TEX_REPLACE_KD) or ((tex / normalizer) + kd) / 2.0f (RT_TEX_BLEND_KD),
+ *             true divisions, and kd' takes the place of material.diffuse in the scene's light
+ *             loop and the light-sample loop of that hit; ambient, specular, mirror, transparency
+ *             and Beer's law keep the material's values.  HW4's has_diffuse / has_specular skips
+ *             are not taken over: HW2's loop has none, and its shadow-ray count is the one counted.
+ *             Untextured objects of a textured scene shade exactly as before.
+ *   entries   rt_shade_rays*, rt_shade_rays_lit*, rt_film_shade_rays*, rt_film_shade_rays_lit*,
+ *             rt_render* and MSAA frames shade with textures; rt_trace_rays*, rt_occluded* and
+ *             rt_hit_attributes* report what they report today.  A textured scene renders its
+ *             frames on the ray-tree path and behaves like a recursing scene elsewhere:
+ *             rt_scene_records_ok is 0, RT_TILE_RECORDS is refused, rt_tile_costs has nothing.
+ *             Both traversal modes and RT_QUERY_REORDER give the same bits; results do not depend
+ *             on n, position or neighbours.
+ *   rt_texture_lookup*  the lookup alone, one record per query: rgb[3 i ..] = lookup of texture
+ *             q[i].texture at (q[i].u, q[i].v); a texture id out of range gives 0 0 0 and reads
+ *             nothing.  d_q: 16-byte aligned; n == 0 launches nothing; n < 0 or a NULL pointer with
+ *             n > 0 is RT_E_INVALID before any HIP call.  rt_host_texture_lookup_desc runs the
+ *             same function on the host for a descriptor (checked as scene creation checks it)
+ *             and touches no HIP API. */
+#define CENG795_RT_HAS_TEXTURES 1
+int rt_textures_version(void); /* 1 */
+
+enum { RT_TEX_NEAREST = 0, RT_TEX_BILINEAR = 1 };
+enum { RT_TEX_REPLACE_KD = 0, RT_TEX_BLEND_KD = 1, RT_TEX_REPLACE_ALL = 2 };
+enum { RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 1 };
+typedef struct rt_texture {
+  const unsigned char* rgb8;  /* height rows of width texels, 3 bytes each, tightly packed, top row
+                                 first (stbi_load(..., 3)) */
+  int width, height;          /* 1 .. 16384 each */
+  int interpolation, decal, appearance;
+  float normalizer;           /* finite, != 0; the reference's default is 255 */
+} rt_texture;
+typedef struct rt_texture_desc {
+  size_t struct_size;           /* sizeof(rt_texture_desc) */
+  int num_textures;
+  const rt_texture* textures;
+  const int* mesh_texture;      /* [num_meshes]    -1: none; NULL: none */
+  const int* triangle_texture;  /* [num_triangles] */
+  const int* sphere_texture;    /* [num_spheres]   */
+} rt_texture_desc;
+int rt_scene_create_textured(const rt_scene_desc* desc, const rt_surface_desc* surface /* may be NULL */,
+                             const rt_texture_desc* textures, int device, rt_scene** out);
+int rt_scene_num_textures(const rt_scene* scene);  /* 0: an untextured scene */
+
+typedef struct rt_tex_query { int texture; float u, v; int pad; } rt_tex_query; /* 16 B */
+int rt_texture_lookup_device(rt_scene* scene, const rt_tex_query* d_q, long long n,
+                             float* d_rgb /* 3 n */, void* hip_stream);
+int rt_texture_lookup(rt_scene* scene, const rt_tex_query* q, long long n, float* rgb);
+int rt_host_texture_lookup_desc(const rt_texture_desc* textures, const rt_tex_query* q, long long n,
+                                float* rgb);
+
+/* Scene files.  rt_scene_load_xml_textured is rt_scene_load_xml_surface plus (HW4/src/Scene.cpp:
+ * 690-701, 761-768, 905-911, 1008-1014, 1030-1077): <TexCoordData>, read as pairs; the root
+ * <Textures> block: <ImageName>, <Interpolation> (default bilinear; anything but "nearest" is
+ * bilinear), <DecalMode> (default blend_kd; anything but "replace_kd" or "blend_kd" is
+ * replace_all), <Appearance> (default clamp; anything but "repeat" is clamp), <Normalizer>
+ * (default 255.0); and a 1-based <Texture> child of <Mesh>, <Triangle> and <Sphere>.  The library
+ * decodes no image files: the caller passes the decoded images, matched to <ImageName> by string;
+ * a name without a record is RT_E_IO.  RT_E_UNSUPPORTED with a message: ImageName "perlin",
+ * bumpmap="true", <BackgroundTexture>, a textured mesh whose textureOffset differs from its
+ * vertexOffset (uv is kept per vertex id), fewer uv pairs than a textured face's vertex ids need,
+ * plyFile.  Every other loader reads such files exactly as before.
+ * rt_host_textures_xml (host-only, touches no HIP API) reports what was parsed: per texture
+ * (the first min(textures, texture_capacity)) its name (names: texture_capacity x 256 chars,
+ * NUL-terminated), interpolation / decal / appearance (modes3: 3 ints each) and normalizer; each
+ * object list's 0-based texture ids (-1: none; the first min(count, object_capacity) of each); the
+ * first min(pairs, uv_capacity) <TexCoordData> pairs; counts5 = textures, meshes, triangles,
+ * spheres, uv pairs.  Any output may be NULL. */
+typedef struct rt_texture_image {
+  const char* name;
+  const unsigned char* rgb8;  /* as rt_texture::rgb8 */
+  int width, height;
+} rt_texture_image;
+int rt_scene_load_xml_textured(const char* xml_path, const rt_texture_image* images, int num_images,
+                               int device, rt_scene** out);
+int rt_host_textures_xml(const char* xml_path, char* names, int* modes3, float* normalizer,
+                         int texture_capacity, int* mesh_texture, int* triangle_texture,
+                         int* sphere_texture, int object_capacity, float* uv2, int uv_capacity,
+                         int* counts5);
+
 /* PNG output as HW2/main.cpp:43-57: per channel clamp(int(c), 0, 255), alpha 255. */
 int rt_write_png(const char* path, const float* rgb, int width, int height);
 
