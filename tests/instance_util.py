@@ -12,7 +12,9 @@ and one per loose primitive, and restates in numpy fp32 what lies between them:
 
 A ray's hit is the lexicographic minimum of (t, top-level DFS leaf) over the objects it may
 reach; under an instance the oracle's own closest hit of the local ray.  Every operation is one
-numpy float32 operation, so every intermediate rounds once, as in the reference's SSE build."""
+numpy float32 operation, so every intermediate rounds once, as in the reference's SSE build.
+Checked against goldens from HW3's compiled code, every ray and every field
+(tests/test_ref_hw34_host.py)."""
 from __future__ import annotations
 
 import ctypes as C

@@ -8,7 +8,8 @@ step over all rays at once.  The geometry is the oracle's: the hit from
 OracleScene.intersect_rays, the material through rq_util.object_list, every shadow decision from
 intersect_rays of the shadow ray with 0 < t < dist - eps.  test_lit_query_host.py earns it the
 right to judge the emitter term: fed a scene's own point lights it equals OracleScene.shade_rays
-bit for bit.
+bit for bit.  The emitter term itself is checked against a golden from HW3's compiled code: an
+<AreaLight> whose every sample is its position (tests/test_ref_hw34_host.py).
 
 Below it: light records, variant scenes with another light list, and the device launch."""
 from __future__ import annotations

@@ -3,6 +3,9 @@
 The oracle knows one normal per triangle, so the judge of a smooth scene is a restatement outside
 it, in the manner of lit_util: numpy float32 arithmetic (one rounding per operation, never
 contracted), the oracle's operation order, `math.pow` / `exp` / `log` for the fp64 calls.
+It is HW3's smooth normal under HW2's trace_ray and HW2's Mesh, and is checked against goldens from
+HW3's compiled code (tests/test_ref_hw34_host.py; DESIGN.md §4.19: HW3 itself has the other sign in
+Beer's law and normalises every mesh normal once more in its identity Mesh_instance).
 
   vertex_normals  the HW3 loader's area-weighted vertex normals (HW3/src/Scene.cpp:690-695,
                   870-876), a sequential loop.

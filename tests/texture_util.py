@@ -2,7 +2,9 @@
 
 The oracle knows no textures, so the judge is a restatement outside it, in the manner of
 smooth_util and lit_util: numpy float32 arithmetic (one rounding per operation, never contracted),
-written from the HW4 sources, not from the kernel.
+checked against goldens from the HW4 sources' compiled code (tests/test_ref_hw34_host.py; DESIGN.md
+§4.19 names the departures: Beer's sign, the normals of plain meshes and spheres, the read past the
+image, and textured loose triangles, which HW4 does not have).
 
   lookup       Texture::get_color_at (HW4/src/Texture.cpp:57-134), scalar fp32 steps in its order.
   sphere_uv    Sphere.cpp:100-105 with np.arccos / np.arctan2 on float64; also whether one of its
