@@ -3,6 +3,7 @@
 #ifndef CENG795_HOST_SCENE_H_
 #define CENG795_HOST_SCENE_H_
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -245,6 +246,97 @@ void load_textures_xml(const std::string& path, XmlTextures& out);
 void textures_from_xml(const XmlTextures& xt, const rt_scene_desc& d, const rt_texture_image* images,
                        int num_images, std::vector<rt_texture>& records, std::vector<float>& uv,
                        rt_texture_desc& tex);
+
+// ---- scene assembly (scene_assemble.cpp): the one place that decides which kind
+// of scene a set of descriptors denotes and builds everything creation derives on the host.  No
+// HIP: the C ABI's creation entries run it before their first HIP call.
+
+// What a creation entry was given.  Everything but `desc` may be null.
+struct SceneInputs {
+  const char* entry = "";  // the entry's name, for messages
+  const rt_scene_desc* desc = nullptr;
+  const rt_surface_desc* surface = nullptr;
+  const rt_texture_desc* textures = nullptr;
+  const rt_instance_desc* instances = nullptr;
+  const rt_motion_desc* motion = nullptr;
+  const std::vector<std::string>* image_names = nullptr;  // per camera (scene files)
+};
+
+// What creation derives from them.
+struct SceneHost {
+  HostScene host;
+  // made of instances (rt_scene_create_instanced): `host` holds the scene's scalars, materials,
+  // lights and cameras and no tree; the ray queries, the radiance queries and the frames (on the
+  // ray-tree path, like a smooth scene's) run their INST kernels; nothing that reads the flat
+  // tree takes such a scene (hit attributes, pixel records, the BVH dump)
+  std::unique_ptr<InstHost> inst;
+  bool deep = false;  // the flat tree needs more stack than a lane's (tree_deep)
+  bool needs_recursion = false;  // some material is a mirror or a dielectric, and max_depth > 0
+  bool has_spheres = false;
+  // some mesh is smooth (rt_scene_create_surface): frames take the ray-tree path, as a scene that
+  // recurses does, and the ray-tree and closest-hit kernels run their SMOOTH instantiations
+  bool smooth = false;
+  // some object has a texture (rt_scene_create_textured): frames take the ray-tree path too, and
+  // the ray-tree kernels run their TEX instantiations
+  bool textured = false;
+  size_t most = 1;  // pixel records of the largest camera frame (whole tiles)
+};
+
+// Fills `out` (a fresh one) from `in`.  Checks the descriptors' struct_size and counts, then
+// decides by the rules of ceng795_rt.h: no instance and trivial motion give the flat scene (with
+// its surface data and textures, if any), instances and trivial motion the two-level scene,
+// anything else the scene with motion.  A flat scene gets its culling tree (none when that tree
+// would be deeper than max_tree_depth, the kernels' largest stack).  Throws what the build_*
+// functions throw; std::invalid_argument for a scene of 2^26 primitives or more or a reference
+// tree deeper than max_tree_depth; std::domain_error for instances or motion together with
+// surface data or textures, which no entry can express.
+void assemble_scene(const SceneInputs& in, int max_tree_depth, SceneHost& out);
+
+// struct_size and num_instances of an instance descriptor (null: nothing to check);
+// std::invalid_argument with `fn` in front.
+void check_instance_desc(const char* fn, const rt_instance_desc* in);
+
+// What the six scene-file entries differ in.
+struct SceneFileOptions {
+  bool shading_mode = false;  // honour the meshes' shadingMode (rt_scene_load_xml_surface)
+  bool textures = false;      // ... and the file's textures, with the caller's images
+  bool instances = false;     // every <Mesh> an instance, and the <MeshInstance>s
+  bool motion = false;        // ... and <MotionBlur>, the spheres' <Transformations>
+  const rt_texture_image* images = nullptr;
+  int num_images = 0;
+};
+// A loaded scene file: `in` points into the rest, so the object stays where it is.
+struct SceneFile {
+  XmlSceneStorage st;
+  XmlInstances xi;
+  XmlTextures xt;
+  std::vector<rt_texture> records;
+  std::vector<float> uv;
+  rt_scene_desc desc;
+  rt_surface_desc surface;
+  rt_texture_desc textures;
+  rt_instance_desc instances;
+  rt_motion_desc motion;
+  SceneInputs in;
+};
+void load_scene_file(const char* entry, const std::string& path, const SceneFileOptions& opt,
+                     SceneFile& out);
+
+// Whether the flat tree (with its culling tree) needs the kernels' deep instantiations, and
+// whether its frames get entry cuts: entry_cuts_apply with the stack of the instantiation that runs.
+bool tree_deep(const HostScene& h);
+bool scene_entry_cuts_apply(const HostScene& h, int max_tree_depth);
+
+// The flat scene of a scene file, for the rt_host_* entries: load_flat_scene without a culling
+// tree, flat_host_scene with build_accel(treelet_leaves)'s.  stats4 given: checked with check_accel
+// (std::invalid_argument "culling tree: ..." when it fails).  max_tree_depth > 0: without the
+// culling tree when it is deeper, as assemble_scene does.
+void load_flat_scene(const std::string& xml_path, HostScene& out);
+void flat_host_scene(const std::string& xml_path, int treelet_leaves, int max_tree_depth,
+                     long long stats4[4], HostScene& out);
+
+// `text` as the file `path`; false when the file cannot be opened.
+bool write_text_file(const char* path, const std::string& text);
 
 void camera_from_view(const float pos[3], const float gaze[3], const float up[3],
                       const float np[4], float dist, int w, int h, int ns, rt_camera& c);

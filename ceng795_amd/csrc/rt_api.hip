@@ -168,14 +168,18 @@ constexpr size_t kTimingPending = 256;
 // the calls that run there.
 struct Replica {
   int device = 0;
-  DevBuf<DevNode> d_nodes;
-  DevBuf<DevPrim> d_prims;
-  DevBuf<DevLeaf> d_leaves;
-  DevBuf<float> d_normals;
-  DevBuf<DevAncestry> d_anc;
+  // One tree's arrays (upload_tree): the flat scene's, or a base mesh's.
+  struct TreeBufs {
+    DevBuf<DevNode> nodes;
+    DevBuf<DevPrim> prims;
+    DevBuf<DevLeaf> leaves;
+    DevBuf<float> normals;
+    DevBuf<DevAncestry> anc;
+    DevBuf<int> leaf_object;  // per DFS leaf: its object index (rt_ray_hit::object)
+  };
+  TreeBufs d_tree;  // the flat scene's (an instanced scene: empty)
   DevBuf<DevMaterial> d_mats;
   DevBuf<DevLight> d_lights;
-  DevBuf<int> d_leaf_object;  // per DFS leaf: its object index (rt_ray_hit::object)
   // surface data (HostScene::leaf_tri / vertex_normals / vertex_uv), each only when the scene
   // has it; `surf` points at them
   DevBuf<int> d_surf_tri;
@@ -187,15 +191,7 @@ struct Replica {
   TexParams tex{nullptr, nullptr, 0, -1};
   // an instanced scene: every base mesh's arrays, the mesh and instance tables
   // and the top-level tree; `inst` points at them
-  struct MeshBufs {
-    DevBuf<DevNode> nodes;
-    DevBuf<DevPrim> prims;
-    DevBuf<DevLeaf> leaves;
-    DevBuf<float> normals;
-    DevBuf<DevAncestry> anc;
-    DevBuf<int> leaf_object;
-  };
-  std::vector<MeshBufs> d_mesh;
+  std::vector<TreeBufs> d_mesh;
   DevBuf<DevMesh> d_mesh_table;
   DevBuf<DevInstance> d_instances;
   DevBuf<DevNode> d_top_nodes;
@@ -224,25 +220,10 @@ struct Replica {
   unsigned long long tick = 0;  // lookups of `streams` (LRU order)
 };
 
-struct rt_scene {
-  HostScene host;
+// What assemble_scene derived on the host (host, inst, deep, ... most), and the scene's devices.
+struct rt_scene : SceneHost {
   int mode = RT_TRAVERSAL_FAST;
-  bool deep = false;
-  bool needs_recursion = false;
-  bool has_spheres = false;
-  // some mesh is smooth (rt_scene_create_surface): frames take the ray-tree path, as a scene that
-  // recurses does, and the ray-tree and closest-hit kernels run their SMOOTH instantiations
-  bool smooth = false;
-  // some object has a texture (rt_scene_create_textured): frames take the ray-tree path too, and
-  // the ray-tree kernels run their TEX instantiations
-  bool textured = false;
   bool tree_frames() const { return needs_recursion || smooth || textured || inst != nullptr; }
-  // made of instances (rt_scene_create_instanced): `host` holds the scene's scalars, materials,
-  // lights and cameras and no tree; the ray queries, the radiance queries and the frames (on the
-  // ray-tree path, like a smooth scene's) run their INST kernels; nothing that reads the flat
-  // tree takes such a scene (hit attributes, pixel records, the BVH dump)
-  std::unique_ptr<InstHost> inst;
-  size_t most = 1;         // pixel records of the largest camera frame (whole tiles)
   unsigned long long msaa_seed = 0;
   // bytes of ray-tree frames one chunk of a radiance query may hold (rt_set_radiance_scratch_limit)
   std::atomic<size_t> radiance_limit{kRadianceDefaultLimit};
@@ -457,8 +438,7 @@ void seed_cold_orders(const rt_scene* s, Replica& r) {
 void seed_entry_cuts(const rt_scene* s, Replica& r) {
   const HostScene& h = s->host;
   r.d_cuts = std::vector<DevBuf<int>>(h.cameras.size());
-  if (s->tree_frames() || !entry_cuts_apply(h, s->deep ? max_supported_depth() : kLaneStack - 2))
-    return;
+  if (s->tree_frames() || !scene_entry_cuts_apply(h, max_supported_depth())) return;
   for (size_t cam = 0; cam < h.cameras.size(); cam++) {
     if (h.cameras[cam].num_samples > 1) continue;
     try {
@@ -484,19 +464,23 @@ const int* bind_entry_cuts(const Replica& r, int cam, int row0, int row_stride, 
   return r.d_cuts[cam].p + (size_t)(row0 / kTile) * tiles_x * kEntryCut;
 }
 
-void upload_replica(const rt_scene* s, Replica& r) {
-  DeviceGuard g(r.device);
-  const HostScene& h = s->host;
-  // +64 B: the kernels may fetch a record with one 64-byte scalar load past its 48 bytes
-  constexpr size_t kPad = 64;
-  r.d_nodes = upload(h.nodes, "upload nodes", kPad);
-  r.d_prims = upload(h.prims, "upload prims", kPad);
-  r.d_leaves = upload(h.leaves, "upload culling leaves", kPad);
-  r.d_normals = upload(h.normals, "upload normals", kPad);
-  r.d_anc = upload(h.ancestry, "upload ancestry", kPad);
-  r.d_mats = upload(h.materials, "upload materials", kPad);
-  r.d_lights = upload(h.lights, "upload lights", kPad);
-  r.d_leaf_object = upload(h.leaf_object, "upload leaf objects", 0);
+// One tree's arrays on the current device (`mesh`: a base mesh's, in the allocation labels).
+// +64 B: the kernels may fetch a record with one 64-byte scalar load past its 48 bytes
+constexpr size_t kPad = 64;
+Replica::TreeBufs upload_tree(const HostScene& h, bool mesh) {
+  Replica::TreeBufs b;
+  b.nodes = upload(h.nodes, mesh ? "upload mesh nodes" : "upload nodes", kPad);
+  b.prims = upload(h.prims, mesh ? "upload mesh prims" : "upload prims", kPad);
+  b.leaves = upload(h.leaves, mesh ? "upload mesh culling leaves" : "upload culling leaves", kPad);
+  b.normals = upload(h.normals, mesh ? "upload mesh normals" : "upload normals", kPad);
+  b.anc = upload(h.ancestry, mesh ? "upload mesh ancestry" : "upload ancestry", kPad);
+  b.leaf_object = upload(h.leaf_object, mesh ? "upload mesh leaf objects" : "upload leaf objects", 0);
+  return b;
+}
+
+// The flat scene's tree, surface data and textures.
+void upload_flat(const HostScene& h, Replica& r) {
+  r.d_tree = upload_tree(h, false);
   r.surf.num_leaves = (int)h.prims.size();
   if (!h.leaf_tri.empty()) {
     r.d_surf_tri = upload(h.leaf_tri, "upload leaf vertex ids", 0);
@@ -515,43 +499,79 @@ void upload_replica(const rt_scene* s, Replica& r) {
     r.d_texels = upload(h.texels, "upload texels", 0);
     r.tex = TexParams{r.d_tex_table.p, r.d_texels.p, (int)h.textures.size(), h.blank_material};
   }
+}
+
+// An instanced scene's: every base mesh's arrays, the tables that point at them and the top-level
+// tree.
+void upload_instanced(const InstHost& ih, Replica& r) {
+  std::vector<DevMesh> table(ih.meshes.size());
+  r.d_mesh.resize(ih.meshes.size());
+  for (size_t m = 0; m < ih.meshes.size(); m++) {
+    const HostScene& h = ih.meshes[m];
+    Replica::TreeBufs& b = r.d_mesh[m];
+    b = upload_tree(h, true);
+    DevMesh& dm = table[m];
+    std::memset(&dm, 0, sizeof dm);
+    dm.nodes = b.nodes.p;
+    dm.leaves = b.leaves.p;
+    dm.prims = b.prims.p;
+    dm.anc = b.anc.p;
+    dm.normals = b.normals.p;
+    dm.leaf_object = b.leaf_object.p;
+    dm.root_kind = h.root_kind;
+    dm.root_ref = h.root_ref;
+    // (the rule of use_fast in rt_kernels.hip: a culling tree only over a node root)
+    const bool culled = h.accel_root >= 0 && h.root_kind == kRootNode && !h.leaves.empty();
+    dm.accel_root = culled ? h.accel_root : -1;
+    dm.accel_stride = h.accel_stride;
+    std::memcpy(dm.root_box, h.root_box, sizeof dm.root_box);
+    std::memcpy(dm.accel_box, h.accel_box, sizeof dm.accel_box);
+    dm.quot_ok = h.quot_ok;
+    dm.leaf_base = ih.mesh_leaf_base[m];
+    dm.object_base = ih.mesh_object_base[m];
+  }
+  r.d_mesh_table = upload(table, "upload mesh table", kPad);
+  r.d_instances = upload(ih.instances, "upload instances", kPad);
+  r.d_top_nodes = upload(ih.top_nodes, "upload top-level nodes", kPad);
+  r.d_top_prims = upload(ih.top_prims, "upload top-level primitives", kPad);
+  r.d_top_normals = upload(ih.top_normals, "upload top-level normals", kPad);
+  r.d_top_info = upload(ih.top_info, "upload top-level objects", 0);
+  r.inst.top_nodes = r.d_top_nodes.p;
+  r.inst.top_prims = r.d_top_prims.p;
+  r.inst.top_normals = r.d_top_normals.p;
+  r.inst.top_info = r.d_top_info.p;
+  r.inst.instances = r.d_instances.p;
+  r.inst.meshes = r.d_mesh_table.p;
+  r.inst.top_root_kind = ih.top_root_kind;
+  r.inst.top_quot_ok = ih.top_quot_ok;
+  std::memcpy(r.inst.top_box, ih.top_box, sizeof r.inst.top_box);
+  if (ih.has_motion) {  // (a table may be empty: nothing of that kind moves, and nothing reads it)
+    r.d_motion_instances = upload(ih.motion_instances, "upload moving instances", kPad);
+    r.d_motion_spheres = upload(ih.motion_spheres, "upload moving spheres", kPad);
+    r.motion.instances = r.d_motion_instances.p;
+    r.motion.spheres = r.d_motion_spheres.p;
+  }
+}
+
+// The scene on replica r's device: its trees, then what every kind of scene has.  (An instanced
+// scene gets no cold orders and no entry cuts: its frames are ray trees.)
+void upload_replica(const rt_scene* s, Replica& r) {
+  DeviceGuard g(r.device);
+  if (s->inst)
+    upload_instanced(*s->inst, r);
+  else
+    upload_flat(s->host, r);
+  r.d_mats = upload(s->host.materials, "upload materials", kPad);
+  r.d_lights = upload(s->host.lights, "upload lights", kPad);
   r.d_counters.reserve(kCounterAlloc, "alloc counters");
   hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
   seed_cold_orders(s, r);
   seed_entry_cuts(s, r);
 }
 
-// Builds the culling tree once on the host, then uploads the scene to every device.  Several
-// devices: one RCCL communicator each, for the framebuffer gather (render_multi).
-// What the materials and cameras decide (flat and instanced scenes alike): whether a ray tree can
-// recurse, and the largest frame.
-void scene_shading_state(rt_scene* s) {
-  const HostScene& h = s->host;
-  for (const DevMaterial& m : h.materials) {
-    const bool mirror = m.mirror[0] != 0 || m.mirror[1] != 0 || m.mirror[2] != 0;
-    const bool glass = m.transparency[0] != 0 || m.transparency[1] != 0 || m.transparency[2] != 0;
-    if ((mirror || glass) && h.max_depth > 0) s->needs_recursion = true;
-  }
-  for (const rt_camera& c : h.cameras) {
-    const size_t tiles = (size_t)((c.width + kTile - 1) / kTile) * ((c.height + kTile - 1) / kTile);
-    s->most = std::max(s->most, tiles * kTile * kTile);
-  }
-}
-
-int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
-  build_accel(s->host, kDefaultTreeletLeaves);
-  if (s->host.accel_depth > max_supported_depth()) build_accel(s->host, 0);
-  const HostScene& h = s->host;
-  if (h.prims.size() >= (size_t(1) << 26))  // leaf indices share a 32-bit queue word with a lane
-    throw std::invalid_argument("scenes of 2^26 primitives or more are not supported");
-  if (h.depth > max_supported_depth())
-    throw std::invalid_argument("BVH deeper than " + std::to_string(max_supported_depth()) +
-                                " levels is not supported");
-  s->deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
-  for (const DevPrim& p : h.prims) s->has_spheres |= p.kind == kPrimSphere;
-  s->smooth = h.smooth;
-  s->textured = !h.textures.empty();
-  scene_shading_state(s);
+// The assembled scene on every device of the list.  `multi`: frames go through render_multi, with
+// one RCCL communicator per device for the framebuffer gather.
+void upload_scene(rt_scene* s, const std::vector<int>& devices, bool multi) {
   for (int d : devices) {
     s->rep.push_back(std::make_unique<Replica>());
     s->rep.back()->device = d;
@@ -568,7 +588,6 @@ int create_from_host(rt_scene* s, const std::vector<int>& devices, bool multi) {
                  "ncclCommInitAll");
     }
   }
-  return RT_OK;
 }
 
 std::vector<int> device_list(int device_count, const int* devices) {
@@ -603,10 +622,10 @@ RenderParams scene_params(const rt_scene* s, const Replica& r) {
   const HostScene& h = s->host;
   RenderParams P;
   std::memset(&P, 0, sizeof P);
-  P.nodes = r.d_nodes.p;
-  P.leaves = r.d_leaves.p;
-  P.prims = r.d_prims.p;
-  P.normals = r.d_normals.p;
+  P.nodes = r.d_tree.nodes.p;
+  P.leaves = r.d_tree.leaves.p;
+  P.prims = r.d_tree.prims.p;
+  P.normals = r.d_tree.normals.p;
   P.materials = r.d_mats.p;
   P.lights = r.d_lights.p;
   P.num_lights = (int)h.lights.size();
@@ -621,7 +640,7 @@ RenderParams scene_params(const rt_scene* s, const Replica& r) {
   P.accel_stride = h.accel_stride;
   P.quot_ok = s->inst ? s->inst->top_quot_ok : h.quot_ok;  // (instanced: the loose triangles')
   std::memcpy(P.accel_box, h.accel_box, sizeof P.accel_box);
-  P.anc = r.d_anc.p;
+  P.anc = r.d_tree.anc.p;
   P.occ_words = occ_words(h);
   return P;
 }
@@ -1248,32 +1267,69 @@ StreamScratch* scratch_for(rt_scene* s, Replica& r, void* stream, std::unique_lo
   return r.streams.back().get();
 }
 
-int load_xml_into(rt_scene* s, const char* xml_path, const std::vector<int>* devices,
-                  int device_count, const int* device_ids, bool surface = false) {
-  return guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
-    s->host.image_names = st.image_names;
-    build_host_scene(d, s->host);
-    if (surface) {  // rt_scene_load_xml_surface: the meshes' shadingMode, computed normals, no uv
-      const rt_surface_desc sd{sizeof(rt_surface_desc), st.mesh_smooth.data(), nullptr, nullptr};
-      build_surface(d, &sd, s->host);
-    }
-    std::vector<int> devs;
-    if (devices) {
-      devs = *devices;
-    } else {
-      devs = device_list(device_count, device_ids);
-    }
-    return create_from_host(s, devs, devices == nullptr);
-  });
-}
+// Where a creation entry puts its scene: on one device (< 0: the current one), or, `multi`, on a
+// list of them (`ids` null: 0 .. count - 1).
+struct DeviceChoice {
+  int device = -1;
+  int count = 0;
+  const int* ids = nullptr;
+  bool multi = false;
+};
 
-std::vector<int> single_device(int device) {
+std::vector<int> resolve_devices(const DeviceChoice& c) {
+  if (c.multi) return device_list(c.count, c.ids);
+  int device = c.device;
   if (device < 0) hip_check(hipGetDevice(&device), "hipGetDevice");
   return {device};
 }
+
+// Every rt_scene_create* / rt_scene_load_xml* entry: the NULL checks (`given`:
+// the entry's description or path), what `fill` makes of the entry's arguments (a description
+// entry sets f.in, a scene-file entry loads f), the whole host build, and only then the first HIP
+// call: the devices, the upload.
+template <typename Fill>
+int create_scene(const char* entry, bool given, const DeviceChoice& where, rt_scene** out,
+                 Fill&& fill) {
+  if (!given || !out) return set_error(RT_E_INVALID, std::string(entry) + ": NULL argument");
+  *out = nullptr;
+  auto s = std::make_unique<rt_scene>();
+  const int rc = guarded([&] {
+    SceneFile f;
+    f.in.entry = entry;
+    fill(f);
+    assemble_scene(f.in, max_supported_depth(), *s);
+    upload_scene(s.get(), resolve_devices(where), where.multi);
+    return RT_OK;
+  });
+  if (rc != RT_OK) return rc;
+  *out = s.release();
+  return RT_OK;
+}
+
+// A description entry: the descriptors as they came (all but `desc` may be null).
+int create_from_desc(const char* entry, const DeviceChoice& where, rt_scene** out,
+                     const rt_scene_desc* desc, const rt_surface_desc* surface = nullptr,
+                     const rt_texture_desc* textures = nullptr,
+                     const rt_instance_desc* instances = nullptr,
+                     const rt_motion_desc* motion = nullptr) {
+  return create_scene(entry, desc != nullptr, where, out, [&](SceneFile& f) {
+    f.in.desc = desc;
+    f.in.surface = surface;
+    f.in.textures = textures;
+    f.in.instances = instances;
+    f.in.motion = motion;
+  });
+}
+
+// A scene-file entry: the descriptors load_scene_file makes of the file.
+int create_from_file(const char* entry, const DeviceChoice& where, rt_scene** out,
+                     const char* xml_path, const SceneFileOptions& opt) {
+  return create_scene(entry, xml_path != nullptr, where, out,
+                      [&](SceneFile& f) { load_scene_file(entry, xml_path, opt, f); });
+}
+
+DeviceChoice on_device(int device) { return {device, 0, nullptr, false}; }
+DeviceChoice on_devices(int count, const int* ids) { return {-1, count, ids, true}; }
 
 // Argument rules shared by the ray-query and radiance-query entries; they need no GPU.
 void check_query_args(const char* fn, const rt_scene* s, const void* rays, long long n,
@@ -1337,7 +1393,7 @@ QueryParams query_params(const rt_scene* s, const Replica& r) {
   const HostScene& h = s->host;
   QueryParams Q;
   std::memset(&Q, 0, sizeof Q);
-  Q.leaf_object = r.d_leaf_object.p;
+  Q.leaf_object = r.d_tree.leaf_object.p;
   const float* root_box = s->inst ? s->inst->top_box : h.root_box;
   if (s->inst ? s->inst->top_root_kind == kTopNode : h.root_kind == kRootNode)
     for (int a = 0; a < 3; a++) {
@@ -1377,7 +1433,7 @@ void enqueue_hits(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet& ws
                 "query launch");
       continue;
     }
-    hip_check(launch_query(P, Q, r.d_nodes.p, OCCLUSION, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
+    hip_check(launch_query(P, Q, r.d_tree.nodes.p, OCCLUSION, reorder, s->mode != RT_TRAVERSAL_REFERENCE,
                            s->deep, s->has_spheres, smooth_surface(s), stream),
               "query launch");
   }
@@ -1439,7 +1495,7 @@ void enqueue_radiance(rt_scene* s, const Replica& r, const QueryCall& q, WorkSet
     for (R.first = 0; R.first < part; R.first += chunk) {
       QueryParams C = Q;
       C.n = std::min(part, R.first + chunk);
-      hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_nodes.p,
+      hip_check(launch_radiance(P, C, R, q.lit.k > 0 ? &lit : nullptr, r.d_tree.nodes.p,
                                 s->mode != RT_TRAVERSAL_REFERENCE, s->deep, s->has_spheres,
                                 tree_surface(s), inst_params(s), motion_call(s, q.flags).get(),
                                 tree_textures(s), stream),
@@ -1649,94 +1705,37 @@ int rt_camera_from_view(const float position[3], const float gaze[3], const floa
   return RT_OK;
 }
 
+// (its messages name rt_scene_create)
 int rt_scene_create_multi(const rt_scene_desc* desc, int device_count, const int* devices,
                           rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    const std::vector<int> devs = device_list(device_count, devices);
-    build_host_scene(*desc, s->host);
-    return create_from_host(s.get(), devs, true);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create", on_devices(device_count, devices), out, desc);
 }
 
 int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    const std::vector<int> devs = single_device(device);
-    build_host_scene(*desc, s->host);
-    return create_from_host(s.get(), devs, false);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create", on_device(device), out, desc);
 }
 
 int rt_scene_load_xml(const char* xml_path, int device, rt_scene** out) {
-  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  std::vector<int> devs;
-  int rc = guarded([&] {
-    devs = single_device(device);
-    return RT_OK;
-  });
-  if (rc == RT_OK) rc = load_xml_into(s.get(), xml_path, &devs, 0, nullptr);
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_file("rt_scene_load_xml", on_device(device), out, xml_path, {});
 }
 
 int rt_scene_load_xml_multi(const char* xml_path, int device_count, const int* devices,
                             rt_scene** out) {
-  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_multi: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = load_xml_into(s.get(), xml_path, nullptr, device_count, devices);
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_file("rt_scene_load_xml_multi", on_devices(device_count, devices), out,
+                          xml_path, {});
 }
 
 int rt_surface_version(void) { return 1; }
 
 int rt_scene_create_surface(const rt_scene_desc* desc, const rt_surface_desc* surface, int device,
                             rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_surface: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    if (surface && surface->struct_size < sizeof(rt_surface_desc))
-      throw std::invalid_argument("rt_scene_create_surface: rt_surface_desc::struct_size too small");
-    const std::vector<int> devs = single_device(device);
-    build_host_scene(*desc, s->host);
-    build_surface(*desc, surface, s->host);
-    return create_from_host(s.get(), devs, false);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create_surface", on_device(device), out, desc, surface);
 }
 
 int rt_scene_load_xml_surface(const char* xml_path, int device, rt_scene** out) {
-  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_surface: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  std::vector<int> devs;
-  int rc = guarded([&] {
-    devs = single_device(device);
-    return RT_OK;
-  });
-  if (rc == RT_OK) rc = load_xml_into(s.get(), xml_path, &devs, 0, nullptr, true);
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  SceneFileOptions opt;
+  opt.shading_mode = true;
+  return create_from_file("rt_scene_load_xml_surface", on_device(device), out, xml_path, opt);
 }
 
 int rt_scene_has_smooth(const rt_scene* s) { return s && s->smooth ? 1 : 0; }
@@ -1745,50 +1744,17 @@ int rt_textures_version(void) { return 1; }
 
 int rt_scene_create_textured(const rt_scene_desc* desc, const rt_surface_desc* surface,
                              const rt_texture_desc* textures, int device, rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_textured: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    if (surface && surface->struct_size < sizeof(rt_surface_desc))
-      throw std::invalid_argument("rt_scene_create_textured: rt_surface_desc::struct_size too small");
-    // the whole host build, every check of the three descriptions in it, before any HIP call
-    build_host_scene(*desc, s->host);
-    build_surface(*desc, surface, s->host);
-    build_textures(*desc, surface, textures, s->host);
-    const std::vector<int> devs = single_device(device);
-    return create_from_host(s.get(), devs, false);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create_textured", on_device(device), out, desc, surface,
+                          textures);
 }
 
 int rt_scene_load_xml_textured(const char* xml_path, const rt_texture_image* images, int num_images,
                                int device, rt_scene** out) {
-  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_textured: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
-    XmlTextures xt;
-    load_textures_xml(xml_path, xt);
-    std::vector<rt_texture> records;
-    std::vector<float> uv;
-    rt_texture_desc tex;
-    textures_from_xml(xt, d, images, num_images, records, uv, tex);
-    s->host.image_names = st.image_names;
-    build_host_scene(d, s->host);
-    const rt_surface_desc sd{sizeof(rt_surface_desc), st.mesh_smooth.data(), nullptr, uv.data()};
-    build_surface(d, &sd, s->host);
-    build_textures(d, &sd, &tex, s->host);
-    const std::vector<int> devs = single_device(device);
-    return create_from_host(s.get(), devs, false);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  SceneFileOptions opt;
+  opt.textures = true;
+  opt.images = images;
+  opt.num_images = num_images;
+  return create_from_file("rt_scene_load_xml_textured", on_device(device), out, xml_path, opt);
 }
 
 int rt_host_textures_xml(const char* xml_path, char* names, int* modes3, float* normalizer,
@@ -1897,138 +1863,16 @@ int rt_scene_num_instances(const rt_scene* s) {
   return s && s->inst ? (int)s->inst->instances.size() : 0;
 }
 
-static void check_instance_desc(const char* fn, const rt_instance_desc* in) {
-  if (in && in->struct_size < sizeof(rt_instance_desc))
-    throw std::invalid_argument(std::string(fn) + ": rt_instance_desc::struct_size too small");
-  if (in && in->num_instances < 0)
-    throw std::invalid_argument(std::string(fn) + ": num_instances < 0");
-}
-
-// The instanced scene on its device: every base mesh's arrays, the tables that point at them and
-// the top-level tree.
-static void upload_instanced(rt_scene* s, Replica& r) {
-  DeviceGuard g(r.device);
-  const InstHost& ih = *s->inst;
-  constexpr size_t kPad = 64;  // (as upload_replica)
-  std::vector<DevMesh> table(ih.meshes.size());
-  r.d_mesh.resize(ih.meshes.size());
-  for (size_t m = 0; m < ih.meshes.size(); m++) {
-    const HostScene& h = ih.meshes[m];
-    Replica::MeshBufs& b = r.d_mesh[m];
-    b.nodes = upload(h.nodes, "upload mesh nodes", kPad);
-    b.prims = upload(h.prims, "upload mesh prims", kPad);
-    b.leaves = upload(h.leaves, "upload mesh culling leaves", kPad);
-    b.normals = upload(h.normals, "upload mesh normals", kPad);
-    b.anc = upload(h.ancestry, "upload mesh ancestry", kPad);
-    b.leaf_object = upload(h.leaf_object, "upload mesh leaf objects", 0);
-    DevMesh& dm = table[m];
-    std::memset(&dm, 0, sizeof dm);
-    dm.nodes = b.nodes.p;
-    dm.leaves = b.leaves.p;
-    dm.prims = b.prims.p;
-    dm.anc = b.anc.p;
-    dm.normals = b.normals.p;
-    dm.leaf_object = b.leaf_object.p;
-    dm.root_kind = h.root_kind;
-    dm.root_ref = h.root_ref;
-    // (the rule of use_fast in rt_kernels.hip: a culling tree only over a node root)
-    const bool culled = h.accel_root >= 0 && h.root_kind == kRootNode && !h.leaves.empty();
-    dm.accel_root = culled ? h.accel_root : -1;
-    dm.accel_stride = h.accel_stride;
-    std::memcpy(dm.root_box, h.root_box, sizeof dm.root_box);
-    std::memcpy(dm.accel_box, h.accel_box, sizeof dm.accel_box);
-    dm.quot_ok = h.quot_ok;
-    dm.leaf_base = ih.mesh_leaf_base[m];
-    dm.object_base = ih.mesh_object_base[m];
-  }
-  r.d_mesh_table = upload(table, "upload mesh table", kPad);
-  r.d_instances = upload(ih.instances, "upload instances", kPad);
-  r.d_top_nodes = upload(ih.top_nodes, "upload top-level nodes", kPad);
-  r.d_top_prims = upload(ih.top_prims, "upload top-level primitives", kPad);
-  r.d_top_normals = upload(ih.top_normals, "upload top-level normals", kPad);
-  r.d_top_info = upload(ih.top_info, "upload top-level objects", 0);
-  r.d_mats = upload(s->host.materials, "upload materials", kPad);
-  r.d_lights = upload(s->host.lights, "upload lights", kPad);
-  r.inst.top_nodes = r.d_top_nodes.p;
-  r.inst.top_prims = r.d_top_prims.p;
-  r.inst.top_normals = r.d_top_normals.p;
-  r.inst.top_info = r.d_top_info.p;
-  r.inst.instances = r.d_instances.p;
-  r.inst.meshes = r.d_mesh_table.p;
-  r.inst.top_root_kind = ih.top_root_kind;
-  r.inst.top_quot_ok = ih.top_quot_ok;
-  std::memcpy(r.inst.top_box, ih.top_box, sizeof r.inst.top_box);
-  if (ih.has_motion) {  // (a table may be empty: nothing of that kind moves, and nothing reads it)
-    r.d_motion_instances = upload(ih.motion_instances, "upload moving instances", kPad);
-    r.d_motion_spheres = upload(ih.motion_spheres, "upload moving spheres", kPad);
-    r.motion.instances = r.d_motion_instances.p;
-    r.motion.spheres = r.d_motion_spheres.p;
-  }
-  r.d_counters.reserve(kCounterAlloc, "alloc counters");
-  hip_check(hipMemset(r.d_counters.p, 0, sizeof(unsigned long long) * kCounterAlloc), "zero counters");
-}
-
-// An instanced scene from its host parts: s->inst is built.  (Not through create_from_host: there
-// is no flat tree to cull or upload, `deep` stays false — build_instanced refuses deeper trees —
-// and there are no cold orders, which only the fused frame kernel reads.)
-static int create_instanced(rt_scene* s, int device) {
-  const std::vector<int> devs = single_device(device);
-  s->has_spheres = s->inst->has_spheres;
-  scene_shading_state(s);
-  s->rep.push_back(std::make_unique<Replica>());
-  s->rep.back()->device = devs[0];
-  upload_instanced(s, *s->rep.back());
-  return RT_OK;
-}
-
 int rt_scene_create_instanced(const rt_scene_desc* desc, const rt_instance_desc* instances,
                               int device, rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_instanced: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    check_instance_desc("rt_scene_create_instanced", instances);
-    if (!instances || instances->num_instances == 0) {  // rt_scene_create's scene
-      const std::vector<int> devs = single_device(device);
-      build_host_scene(*desc, s->host);
-      return create_from_host(s.get(), devs, false);
-    }
-    s->inst = std::make_unique<InstHost>();
-    build_host_globals(*desc, s->host);
-    build_instanced(*desc, *instances, kDefaultTreeletLeaves, *s->inst);
-    return create_instanced(s.get(), device);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create_instanced", on_device(device), out, desc, nullptr,
+                          nullptr, instances);
 }
 
 int rt_scene_load_xml_instanced(const char* xml_path, int device, rt_scene** out) {
-  if (!xml_path || !out)
-    return set_error(RT_E_INVALID, "rt_scene_load_xml_instanced: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    XmlSceneStorage st;
-    XmlInstances xi;
-    rt_scene_desc d;
-    load_instances_xml(xml_path, st, d, xi);
-    s->host.image_names = st.image_names;
-    if (xi.mesh.empty()) {  // no <Mesh>: rt_scene_load_xml's scene
-      const std::vector<int> devs = single_device(device);
-      build_host_scene(d, s->host);
-      return create_from_host(s.get(), devs, false);
-    }
-    const rt_instance_desc in{sizeof(rt_instance_desc), (int)xi.mesh.size(), xi.mesh.data(),
-                              xi.material.data(), xi.transform.data()};
-    s->inst = std::make_unique<InstHost>();
-    build_host_globals(d, s->host);
-    build_instanced(d, in, kDefaultTreeletLeaves, *s->inst);
-    return create_instanced(s.get(), device);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  SceneFileOptions opt;
+  opt.instances = true;
+  return create_from_file("rt_scene_load_xml_instanced", on_device(device), out, xml_path, opt);
 }
 
 int rt_host_instances_xml(const char* xml_path, int* mesh, int* material, float* transform16,
@@ -2089,67 +1933,14 @@ int rt_scene_has_motion(const rt_scene* s) { return s && s->inst && s->inst->has
 
 int rt_scene_create_moving(const rt_scene_desc* desc, const rt_instance_desc* instances,
                            const rt_motion_desc* motion, int device, rt_scene** out) {
-  if (!desc || !out) return set_error(RT_E_INVALID, "rt_scene_create_moving: NULL argument");
-  *out = nullptr;
-  bool trivial = false;
-  const int checked = guarded([&] {
-    check_instance_desc("rt_scene_create_moving", instances);
-    trivial = motion_trivial(*desc, instances, motion);
-    return RT_OK;
-  });
-  if (checked != RT_OK) return checked;
-  if (trivial) return rt_scene_create_instanced(desc, instances, device, out);
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    s->inst = std::make_unique<InstHost>();
-    build_host_globals(*desc, s->host);
-    build_moving(*desc, instances, motion, kDefaultTreeletLeaves, *s->inst);
-    return create_instanced(s.get(), device);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  return create_from_desc("rt_scene_create_moving", on_device(device), out, desc, nullptr, nullptr,
+                          instances, motion);
 }
-
-namespace {
-// The motion descriptor of what load_instances_xml(..., motion) read.
-rt_motion_desc xml_motion_desc(const XmlInstances& xi, const rt_scene_desc& d) {
-  return rt_motion_desc{sizeof(rt_motion_desc), (int)xi.mesh.size(), d.num_spheres,
-                        xi.velocity.data(), xi.sphere_transform.data(), xi.sphere_velocity.data()};
-}
-}  // namespace
 
 int rt_scene_load_xml_moving(const char* xml_path, int device, rt_scene** out) {
-  if (!xml_path || !out) return set_error(RT_E_INVALID, "rt_scene_load_xml_moving: NULL argument");
-  *out = nullptr;
-  auto s = std::make_unique<rt_scene>();
-  const int rc = guarded([&] {
-    XmlSceneStorage st;
-    XmlInstances xi;
-    rt_scene_desc d;
-    load_instances_xml(xml_path, st, d, xi, true);
-    s->host.image_names = st.image_names;
-    const rt_instance_desc in{sizeof(rt_instance_desc), (int)xi.mesh.size(), xi.mesh.data(),
-                              xi.material.data(), xi.transform.data()};
-    const rt_motion_desc mo = xml_motion_desc(xi, d);
-    if (motion_trivial(d, &in, &mo)) {  // rt_scene_load_xml_instanced's scene
-      if (xi.mesh.empty()) {
-        build_host_scene(d, s->host);
-        return create_from_host(s.get(), single_device(device), false);
-      }
-      s->inst = std::make_unique<InstHost>();
-      build_host_globals(d, s->host);
-      build_instanced(d, in, kDefaultTreeletLeaves, *s->inst);
-      return create_instanced(s.get(), device);
-    }
-    s->inst = std::make_unique<InstHost>();
-    build_host_globals(d, s->host);
-    build_moving(d, &in, &mo, kDefaultTreeletLeaves, *s->inst);
-    return create_instanced(s.get(), device);
-  });
-  if (rc != RT_OK) return rc;
-  *out = s.release();
-  return RT_OK;
+  SceneFileOptions opt;
+  opt.instances = opt.motion = true;
+  return create_from_file("rt_scene_load_xml_moving", on_device(device), out, xml_path, opt);
 }
 
 int rt_host_motion_xml(const char* xml_path, float* instance_velocity3, float* sphere_transform16,
@@ -2335,27 +2126,23 @@ int rt_scene_dump_bvh(const rt_scene* s, const char* path) {
   if (!s || !path) return set_error(RT_E_INVALID, "rt_scene_dump_bvh: NULL argument");
   if (s->inst)
     return set_error(RT_E_UNSUPPORTED, "rt_scene_dump_bvh: not for instanced scenes");
-  FILE* f = std::fopen(path, "w");
-  if (!f) return set_error(RT_E_IO, std::string("cannot open ") + path);
-  const std::string d = dump_bvh(s->host);
-  std::fwrite(d.data(), 1, d.size(), f);
-  std::fclose(f);
+  if (!write_text_file(path, dump_bvh(s->host)))
+    return set_error(RT_E_IO, std::string("cannot open ") + path);
   return RT_OK;
+}
+
+// The host dump entries' file (inside `guarded`).
+static void write_dump(const HostScene& h, const char* out_path) {
+  if (!write_text_file(out_path, dump_bvh(h)))
+    throw std::ios_base::failure(std::string("cannot open ") + out_path);
 }
 
 int rt_host_dump_bvh_xml(const char* xml_path, const char* out_path) {
   if (!xml_path || !out_path) return set_error(RT_E_INVALID, "rt_host_dump_bvh_xml: NULL argument");
   return guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
     HostScene h;
-    build_host_scene(d, h);
-    FILE* f = std::fopen(out_path, "w");
-    if (!f) throw std::ios_base::failure(std::string("cannot open ") + out_path);
-    const std::string text = dump_bvh(h);
-    std::fwrite(text.data(), 1, text.size(), f);
-    std::fclose(f);
+    load_flat_scene(xml_path, h);
+    write_dump(h, out_path);
     return RT_OK;
   });
 }
@@ -2365,11 +2152,7 @@ int rt_host_dump_bvh_desc(const rt_scene_desc* desc, const char* out_path) {
   return guarded([&] {
     HostScene h;
     build_host_scene(*desc, h);
-    FILE* f = std::fopen(out_path, "w");
-    if (!f) throw std::ios_base::failure(std::string("cannot open ") + out_path);
-    const std::string text = dump_bvh(h);
-    std::fwrite(text.data(), 1, text.size(), f);
-    std::fclose(f);
+    write_dump(h, out_path);
     return RT_OK;
   });
 }
@@ -2391,14 +2174,8 @@ void rt_host_free(void* p) {
 int rt_host_check_accel_xml(const char* xml_path, int treelet_leaves, long long* stats4) {
   if (!xml_path || !stats4) return set_error(RT_E_INVALID, "rt_host_check_accel_xml: NULL argument");
   return guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
     HostScene h;
-    build_host_scene(d, h);
-    build_accel(h, treelet_leaves);
-    const std::string err = check_accel(h, treelet_leaves, stats4);
-    if (!err.empty()) throw std::invalid_argument("culling tree: " + err);
+    flat_host_scene(xml_path, treelet_leaves, 0, stats4, h);
     return RT_OK;
   });
 }
@@ -2407,15 +2184,9 @@ int rt_host_accel_slot_hist_xml(const char* xml_path, int treelet_leaves, long l
   if (!xml_path || !hist9)
     return set_error(RT_E_INVALID, "rt_host_accel_slot_hist_xml: NULL argument");
   return guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
     HostScene h;
-    build_host_scene(d, h);
-    build_accel(h, treelet_leaves);
     long long stats[4];
-    const std::string err = check_accel(h, treelet_leaves, stats);
-    if (!err.empty()) throw std::invalid_argument("culling tree: " + err);
+    flat_host_scene(xml_path, treelet_leaves, 0, stats, h);
     accel_slot_histogram(h, hist9);
     return RT_OK;
   });
@@ -2425,15 +2196,9 @@ int rt_host_accel_kind_hist_xml(const char* xml_path, int treelet_leaves, long l
   if (!xml_path || !hist81)
     return set_error(RT_E_INVALID, "rt_host_accel_kind_hist_xml: NULL argument");
   return guarded([&] {
-    XmlSceneStorage st;
-    rt_scene_desc d;
-    load_scene_xml(xml_path, st, d);
     HostScene h;
-    build_host_scene(d, h);
-    build_accel(h, treelet_leaves);
     long long stats[4];
-    const std::string err = check_accel(h, treelet_leaves, stats);
-    if (!err.empty()) throw std::invalid_argument("culling tree: " + err);
+    flat_host_scene(xml_path, treelet_leaves, 0, stats, h);
     accel_kind_histogram(h, hist81);
     return RT_OK;
   });
@@ -2517,19 +2282,13 @@ int rt_test_entry_cuts(int mode) {
   return RT_OK;
 }
 
-// The scene file's host scene with its culling tree, and whether it gets entry cuts (as
-// create_from_host and seed_entry_cuts decide it).
+// The scene file's host scene with its culling tree as creation builds it, and whether it gets
+// entry cuts (as seed_entry_cuts decides it).
 static bool entry_cut_scene(const char* xml_path, int treelet_leaves, int cam, HostScene& h) {
-  XmlSceneStorage st;
-  rt_scene_desc d;
-  load_scene_xml(xml_path, st, d);
-  build_host_scene(d, h);
-  build_accel(h, treelet_leaves);
-  if (h.accel_depth > max_supported_depth()) build_accel(h, 0);
+  flat_host_scene(xml_path, treelet_leaves, max_supported_depth(), nullptr, h);
   if (cam < 0 || cam >= (int)h.cameras.size())
     throw std::invalid_argument("camera index out of range");
-  const bool deep = std::max(h.depth, h.accel_depth) > kLaneStack - 2;
-  return entry_cuts_apply(h, deep ? max_supported_depth() : kLaneStack - 2);
+  return scene_entry_cuts_apply(h, max_supported_depth());
 }
 
 int rt_host_entry_cuts_xml(const char* xml_path, int treelet_leaves, int cam, int* out,

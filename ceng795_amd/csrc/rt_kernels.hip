@@ -720,7 +720,7 @@ constexpr int kPushJunk = 66;
 constexpr int kSurvivorCap = 64;
 
 // A queue entry is one 32-bit word: the owner lane above kQueueLeafBits, the leaf (DevLeaf or
-// DFS index, < 2^26: rt_api.hip refuses larger scenes) below.
+// DFS index, < 2^26: assemble_scene refuses larger scenes) below.
 constexpr int kQueueLeafBits = 26;
 constexpr unsigned kQueueLeafMask = (1u << kQueueLeafBits) - 1u;
 struct WaveLeafLds {
